@@ -49,6 +49,10 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
                   reported leg, getrusage), cores busy on average, the cores the rank was allowed (``--cores-per-gpu K``
                   pins every rank to K cores of its own before anything touches HIP: the budget an 8-GPU node leaves a rank)
   em, configs1_pv the other two workloads (see above)
+
+``--dump-outputs DIR`` also writes what the last timed step of each workload computed (the calls, and per gene the
+search's last step or the EM's abundances) as float64 arrays ``DIR/<workload>_<array>.npy``: the inputs are seeded, so the
+files of two builds run with the same arguments compare one for one.
 """
 from __future__ import annotations
 
@@ -187,14 +191,45 @@ class PinnedRecords:
 
 
 # ------------------------------------------------------------------------------------------ steps
-def run_steps(items, dev, dindex, gidx, inputs, method, depth=None, threads=None, resident=None, stats=None):
+def step_outputs(typer, calls, gidx) -> dict:
+    """What a caller of the typing path receives for one sample, as float64 arrays (``--dump-outputs``): the calls as
+    ordinals of the index's alleles (-1: a gene without a call), and per gene either the last copy-number step of the
+    search (likelihood of every kept candidate set, its alleles and their fractions; ``*_offsets``: where each gene's
+    part starts) or the EM's abundance and read count of every allele of the index."""
+    import numpy as np
+    ordinal = {a: i for i, a in enumerate(a for t in gidx.tables for a in t.alleles)}
+    out = {"calls": np.array([ordinal.get(a, -1) for a in calls], dtype=np.float64)}
+    results = [r for r in typer._result.values() if len(r)]
+    if results and hasattr(results[0][-1], "prob"):          # EM reports: (allele, count, prob) of the alleles reads named
+        prob, count = np.zeros(len(ordinal)), np.zeros(len(ordinal))
+        for report in results:
+            for rec in report:
+                prob[ordinal[rec.allele]], count[ordinal[rec.allele]] = rec.prob, rec.count
+        out.update(allele_prob=prob, allele_count=count)
+        return out
+    value, alleles, fraction = [], [], []
+    for steps in results:
+        last = steps[-1]
+        value.append(np.asarray(last.value, dtype=np.float64))
+        alleles.append(np.asarray(last.allele_id, dtype=np.float64).ravel())
+        fraction.append(np.asarray(last.fraction, dtype=np.float64).ravel())
+    for key, parts in (("value", value), ("allele_id", alleles), ("fraction", fraction)):
+        out[key] = np.concatenate(parts) if parts else np.zeros(0)
+    out["value_offsets"] = np.cumsum([0] + [len(p) for p in value]).astype(np.float64)
+    out["allele_offsets"] = np.cumsum([0] + [len(p) for p in alleles]).astype(np.float64)     # of allele_id and fraction
+    return out
+
+
+def run_steps(items, dev, dindex, gidx, inputs, method, depth=None, threads=None, resident=None, stats=None,
+              outputs=None):
     """Types the samples ``inputs[k % len(inputs)]`` for k in ``items``: pinned records -> HBM -> tabulation ->
     typing -> calls, through the package's sample pipeline -- ``cohort.stagedSamples`` (copy and tabulation of the next
     samples on their own contexts while the current ones are typed) feeding ``cohort.typeSamples`` (the typing lanes),
     the same two calls ``kir_graph_amd.main`` makes for the samples of a cohort.  Every copy, tabulation and typing of
     the listed samples starts and ends inside this call.  ``resident``: the records of the distinct samples already in
     HBM (one device buffer per entry of ``inputs``) -- a step then starts at the tabulation.  ``stats`` (a dict):
-    receives what the value table and the searches did over these samples."""
+    receives what the value table and the searches did over these samples.  ``outputs`` (a dict): receives
+    ``step_outputs`` of the last item."""
     from kir_graph_amd import cohort
     from kir_graph_amd.engine import Tabulation
     from kir_graph_amd.hisat2 import SampleData
@@ -236,6 +271,8 @@ def run_steps(items, dev, dindex, gidx, inputs, method, depth=None, threads=None
             stats["samples_repeated_pass"] = stats.get("samples_repeated_pass", 0) + (1 if again else 0)
             stats["tables_rewritten"] = stats.get("tables_rewritten", 0) + getattr(typer, "tables_rewritten", 0)
             stats["tables_patched"] = stats.get("tables_patched", 0) + getattr(typer, "tables_patched", 0)
+        if outputs is not None and k == items[-1]:
+            outputs.update(step_outputs(typer, calls, gidx))
         return calls, warn, n_valid, None        # the typer (and the tables of its genes) ends with its lane's turn
 
     items = range(items) if isinstance(items, int) else items
@@ -479,7 +516,8 @@ def measure(rc: RankContext, inputs, pairs: int, method: str, opts) -> dict:
         t0 = time.perf_counter()
         cpu0 = cpu_seconds()
         by_thread0 = {tid: c for _, tid, c in thread_cpu_table()} if traceOn("bench") else None
-        last = run_steps(opts.steps, dev, dindex, gidx, inputs, method, resident=leg_resident, stats=stats)
+        last = run_steps(opts.steps, dev, dindex, gidx, inputs, method, resident=leg_resident, stats=stats,
+                         outputs=outputs if opts.dump else None)
         for d in rc.devices():
             d.sync()
         cpu = cpu_seconds() - cpu0          # this rank's host time for the steps (waits that spin included)
@@ -493,6 +531,7 @@ def measure(rc: RankContext, inputs, pairs: int, method: str, opts) -> dict:
         stats["value_table_new"] = sharedLogTable(dev).known() - stats.pop("value_table_at_start")
         return elapsed, cpu, last, stats
 
+    outputs = {}        # --dump-outputs: the last step of the last timed leg
     kinds = [k for k in ("host", "hbm") if k == opts.inputs or opts.both_legs]
     kinds.sort(key=lambda k: k != opts.inputs)          # the headline's kind first: its first leg meets the new samples
     legs = {k: [] for k in kinds}
@@ -532,7 +571,7 @@ def measure(rc: RankContext, inputs, pairs: int, method: str, opts) -> dict:
         buf.free()
     return {"legs": legs, "prof": prof, "call_log": call_log, "n_valid": n_valid, "serial": serial,
             "n_values": sharedLogTable(dev).known(),      # distinct probabilities met so far = entries of the log10 value table
-            "search_steps": dict(SEARCH_STATS), "cli_stage": cli_stage,
+            "search_steps": dict(SEARCH_STATS), "cli_stage": cli_stage, "outputs": outputs,
             "h2d_bytes": inputs[0][0].nbytes, "record_bytes": inputs[0][0].record_bytes,
             "pairs": pairs, "method": method, "distinct": len(inputs), "opts": opts}
 
@@ -725,6 +764,9 @@ def main():
                          "(0 = no pinning)")
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--profile-host", action="store_true", help="cProfile one extra step to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step of each workload computed (rank 0) as "
+                         "DIR/<workload>_<array>.npy, float64; the inputs are seeded, so two builds compare file for file")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -767,11 +809,14 @@ def main():
         head = k == 0
         opts = SimpleNamespace(steps=args.steps, warmup=args.warmup, legs=args.legs if head else min(args.legs, 3),
                                inputs=args.inputs, both_legs=args.both_legs, serial_steps=args.serial_steps,
-                               cli_samples=args.cli_samples if (head or name == "configs1_pv") else 0, cpu_pairs=args.cpu_pairs)
+                               cli_samples=args.cli_samples if (head or name == "configs1_pv") else 0, cpu_pairs=args.cpu_pairs,
+                               dump=args.dump_outputs is not None and rank == 0)
         t0 = time.time()
         res = measure(rc, by_size[(pairs, distinct)], pairs, method, opts)
         log(f"[bench] rank {rank}: workload {name} ({configName(pairs)}, {method}) measured in {time.time() - t0:.1f}s")
         results.append((name, res))
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, results)
     if rank == 0:
         out = None
         for k, (name, res) in enumerate(results):
@@ -783,6 +828,22 @@ def main():
         print(json.dumps(out), flush=True)
     if rc.comm is not None:
         rc.comm.close()
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(folder: str, results) -> None:
+    """``--dump-outputs``: ``folder/<workload>_<array>.npy`` for every workload measured (``step_outputs``)."""
+    import numpy as np
+    arrays = {f"{name}_{key}": value for name, res in results for key, value in res["outputs"].items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"bench.py: {total} bytes of outputs exceed the {DUMP_LIMIT}-byte limit of --dump-outputs")
+    os.makedirs(folder, exist_ok=True)
+    for key, value in arrays.items():
+        np.save(os.path.join(folder, key + ".npy"), value)
+    log(f"[bench] {len(arrays)} output arrays ({total} bytes) written to {folder}")
 
 
 def workloadTag(pairs: int, method: str) -> str:

@@ -79,6 +79,30 @@ def test_default_run_reports_the_three_workloads(device):
     assert not {"select_cut", "select", "scan", "count_ids"} & set(d["kernels_serial"]["kernels"])
 
 
+def test_dumped_outputs_are_the_same_from_run_to_run(device, tmp_path):
+    """--dump-outputs: the last timed step of each of the three workloads as float64 .npy files, equal between two runs
+    with the same arguments (seeded inputs), well under the 64 MB bound."""
+    import numpy as np
+    args = ["--steps", "3", "--warmup", "1", "--cpu-pairs", "0", "--serial-steps", "0", "--legs", "1", "--one-kind",
+            "--cli-samples", "0", "--pairs-scale", "0.002"]
+    runs = []
+    for k in range(2):
+        d = _run(args + ["--dump-outputs", str(tmp_path / str(k))], timeout=900)
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        runs.append({p.name: np.load(p) for p in sorted((tmp_path / str(k)).glob("*.npy"))})
+    first, second = runs
+    assert sorted(first) == sorted(second)
+    assert sum(a.nbytes for a in first.values()) <= 64 << 20
+    for name in ("configs2_exonfirst", "configs1_pv"):
+        assert {f"{name}_{key}.npy" for key in ("calls", "value", "value_offsets", "allele_id", "fraction",
+                                                "allele_offsets")} <= set(first)
+        assert first[f"{name}_value.npy"].size > 0
+    assert {"em_calls.npy", "em_allele_prob.npy", "em_allele_count.npy"} <= set(first)
+    assert first["em_allele_prob.npy"].sum() > 0
+    for name, a in first.items():
+        assert a.dtype == np.float64 and a.size and np.array_equal(a, second[name], equal_nan=True), name
+
+
 def test_two_ranks_on_one_gpu_through_the_file_backend(device):
     d = _run(["--gpus", "2", "--steps", "4", "--warmup", "2", "--pairs", "20000", "--cpu-pairs", "0", "--serial-steps", "0",
               "--one-kind"], env={"GK_COMM_BACKEND": "file"})

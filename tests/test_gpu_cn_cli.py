@@ -66,9 +66,13 @@ def test_likelihood_curve_close_to_scipy(device):
     assert dev_model.base == cpu_model.base
 
 
-def test_command_line_two_samples(device, tmp_path):
+def test_command_line_two_samples(device, tmp_path, monkeypatch):
     """graphkir CLI on two synthetic samples: same files, same allele calls as the oracle pipeline."""
     from kir_graph_amd import main as cli
+    # the index folder and the CN files are named relative to the working directory, as on a user's command line: the
+    # reference's naming chain puts both paths into every output file's name, which must stay under the 255-byte limit
+    # of a file name wherever the test's temporary folder is
+    monkeypatch.chdir(tmp_path)
     sidx = synth.makeIndex(seed=11, n_genes=3, var_range=(200, 300), allele_range=(12, 20))
     folder = tmp_path / "index"
     folder.mkdir()
@@ -84,11 +88,11 @@ def test_command_line_two_samples(device, tmp_path):
             f.write("@HD\tVN:1.0\tSO:queryname\n" +
                     "".join(f"@SQ\tSN:{g}\tLN:{len(sidx.backbone[g])}\n" for g in sidx.genes) +
                     "\n".join(synth.toSamLines(s)) + "\n")
-        cn_path = tmp_path / f"s{k}.cn.tsv"
-        cn_path.write_text("gene\tcn\n" + "".join(f"{g}\t{c}\n" for g, c in s.gene_cn.items()))
-        sams.append(str(path)); cns.append(str(cn_path)); samples.append(s)
+        cn_path = f"s{k}.cn.tsv"
+        (tmp_path / cn_path).write_text("gene\tcn\n" + "".join(f"{g}\t{c}\n" for g, c in s.gene_cn.items()))
+        sams.append(str(path)); cns.append(cn_path); samples.append(s)
     args = cli.createParser().parse_args(
-        ["--step-skip-extraction", "--index-folder", str(folder), "--output-folder", str(tmp_path / "out"),
+        ["--step-skip-extraction", "--index-folder", "index", "--output-folder", str(tmp_path / "out"),
          "--allele-strategy", "pv", "--cn-provided", *cns, "--alignment", sams[0], "--alignment", sams[1]])
     cli.main(args)
     out = pd.read_csv(tmp_path / "out" / "cohort.allele.tsv", sep="\t")
@@ -122,9 +126,10 @@ def test_command_line_two_samples(device, tmp_path):
         assert len(only) == 2 * sum(r["multiple"] == 1 for r in ref["reads"])
 
 
-def test_command_line_reads_coordinate_sorted_bam(device, tmp_path):
+def test_command_line_reads_coordinate_sorted_bam(device, tmp_path, monkeypatch):
     """A coordinate-sorted BAM goes through the native reader (no samtools) and gives the calls of the SAM text."""
     import sys
+    monkeypatch.chdir(tmp_path)        # relative index folder and CN file: see test_command_line_two_samples
     sys.path.insert(0, os.path.dirname(__file__))
     from bamwriter import samToBam
     from kir_graph_amd import main as cli
@@ -140,15 +145,15 @@ def test_command_line_reads_coordinate_sorted_bam(device, tmp_path):
     samToBam(header + by_coord, str(tmp_path / "s.bam"))
     with gzip.open(tmp_path / "s.sam.gz", "wt") as f:
         f.write("\n".join(lines) + "\n")
-    cn_path = tmp_path / "s.cn.tsv"
-    cn_path.write_text("gene\tcn\n" + "".join(f"{g}\t{c}\n" for g, c in s.gene_cn.items()))
+    cn_path = "s.cn.tsv"
+    (tmp_path / cn_path).write_text("gene\tcn\n" + "".join(f"{g}\t{c}\n" for g, c in s.gene_cn.items()))
     calls = []
     # BAM through the rendered text (JSON wanted), BAM in binary form (no JSON: compact hand-off), SAM text
     for k, (aln, extra) in enumerate((("s.bam", []), ("s.bam", ["--no-variant-json"]), ("s.sam.gz", []))):
         out = tmp_path / f"out{k}"
         args = cli.createParser().parse_args(
-            ["--step-skip-extraction", "--index-folder", str(folder), "--output-folder", str(out),
-             "--allele-strategy", "pv", "--cn-provided", str(cn_path), "--alignment", str(tmp_path / aln)] + extra)
+            ["--step-skip-extraction", "--index-folder", "index", "--output-folder", str(out),
+             "--allele-strategy", "pv", "--cn-provided", cn_path, "--alignment", str(tmp_path / aln)] + extra)
         cli.main(args)
         calls.append(pd.read_csv(out / "cohort.allele.tsv", sep="\t")["alleles"][0])
         produced = [p.name for p in out.iterdir()]

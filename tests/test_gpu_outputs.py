@@ -204,8 +204,12 @@ def test_per_gene_copy_numbers_over_two_ranks_equal_one_process(device):
     shutil.rmtree(d, ignore_errors=True)
 
 
-def _cohort(tmp_path, n_samples=3, n_pairs=6000):
-    """Synthetic index with all 15 genes (KIR3DL3 among them) + samples as SAM text + their truth."""
+def _cohort(tmp_path, monkeypatch, n_samples=3, n_pairs=6000):
+    """Synthetic index with all 15 genes (KIR3DL3 among them) + samples as SAM text + their truth.  The working
+    directory becomes ``tmp_path`` and the index folder is named relative to it, as on a user's command line: the
+    reference's naming chain puts the index path into every output file's name, which must stay under the 255-byte
+    limit of a file name wherever the test's temporary folder is (the command lines below run there too)."""
+    monkeypatch.chdir(tmp_path)
     sidx = synth.makeIndex(seed=21, n_genes=15, var_range=(60, 120), allele_range=(6, 12), len_range=(2500, 4000))
     folder = tmp_path / "index"
     folder.mkdir()
@@ -221,7 +225,7 @@ def _cohort(tmp_path, n_samples=3, n_pairs=6000):
                     "\n".join(synth.toSamLines(s)) + "\n")
         sams.append(str(path))
         samples.append(s)
-    return sidx, str(folder), sams, samples
+    return sidx, "index", sams, samples
 
 
 def _run(folder, out, sams, extra):
@@ -231,11 +235,11 @@ def _run(folder, out, sams, extra):
     cli.main(args)
 
 
-def test_command_line_fits_copy_numbers_itself(device, tmp_path):
+def test_command_line_fits_copy_numbers_itself(device, tmp_path, monkeypatch):
     """No ``--cn-provided``: depth on the device -> per-sample LCND fit -> typing with the fitted copy numbers;
     and ``--cn-cohort``: one pooled fit.  The CN TSVs equal the oracle's fit on the very depth files the run
     wrote; cohort.cn.tsv holds the same cells; the allele table is typed with those copy numbers."""
-    sidx, folder, sams, samples = _cohort(tmp_path)
+    sidx, folder, sams, samples = _cohort(tmp_path, monkeypatch)
     for mode, extra in (("sample", ["--cn-3dl3-not-diploid"]), ("cohort", ["--cn-cohort"])):
         out = tmp_path / f"out_{mode}"
         _run(folder, out, sams, extra)
@@ -267,14 +271,14 @@ def test_command_line_fits_copy_numbers_itself(device, tmp_path):
             assert (out / "cohort.p75.cohort.LCND.json").exists()
 
 
-def test_two_ranks_cn_cohort_equals_one_process(device, tmp_path):
+def test_two_ranks_cn_cohort_equals_one_process(device, tmp_path, monkeypatch):
     """configs[3] in small: ``--cn-cohort`` under two ranks (both on this GPU, so the exchange goes through the
     rendezvous directory; with a GPU per rank it is gk_allgather_f64 on RCCL -- same payload, same order).
     Every rank fits the pooled depths itself: the per-sample CN tables of both ranks, the merged cohort tables
     and the allele calls must equal the single-process run byte for byte."""
     import subprocess
     import sys
-    sidx, folder, sams, samples = _cohort(tmp_path, n_samples=5, n_pairs=4000)
+    sidx, folder, sams, samples = _cohort(tmp_path, monkeypatch, n_samples=5, n_pairs=4000)
     one = tmp_path / "one"
     _run(folder, one, sams, ["--cn-cohort"])
     two = tmp_path / "two"
@@ -286,7 +290,7 @@ def test_two_ranks_cn_cohort_equals_one_process(device, tmp_path):
     for rank in range(2):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK=str(rank), LOCAL_WORLD_SIZE="2",
                    GK_COMM_BACKEND="file", GK_RDZV_DIR=str(tmp_path / "rdzv"), PYTHONPATH=root)
-        procs.append(subprocess.Popen(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+        procs.append(subprocess.Popen(cmd, env=env, cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=600) for p in procs]
     for p, (_, err) in zip(procs, outs):
         assert p.returncode == 0, err[-3000:]
@@ -304,11 +308,11 @@ def test_two_ranks_cn_cohort_equals_one_process(device, tmp_path):
     assert sum(n.endswith(".p75.cohort.LCND.tsv") for n in names) == 5
 
 
-def test_ranks_flag_starts_the_ranks_itself(device, tmp_path):
+def test_ranks_flag_starts_the_ranks_itself(device, tmp_path, monkeypatch):
     """``python -m kir_graph_amd.main --ranks 2`` without a launcher: the same cohort tables as one process."""
     import subprocess
     import sys
-    sidx, folder, sams, samples = _cohort(tmp_path, n_samples=4, n_pairs=3000)
+    sidx, folder, sams, samples = _cohort(tmp_path, monkeypatch, n_samples=4, n_pairs=3000)
     one = tmp_path / "one"
     _run(folder, one, sams, ["--cn-cohort"])
     two = tmp_path / "two"
@@ -317,7 +321,7 @@ def test_ranks_flag_starts_the_ranks_itself(device, tmp_path):
            "--output-folder", str(two), "--allele-strategy", "pv", "--no-variant-json", "--cn-cohort", "--ranks", "2",
            "--log-level", "WARNING"] + [x for s in sams for x in ("--alignment", s)]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    res = subprocess.run(cmd, env=dict(env, PYTHONPATH=root), cwd=root, capture_output=True, text=True,
+    res = subprocess.run(cmd, env=dict(env, PYTHONPATH=root), cwd=tmp_path, capture_output=True, text=True,
                          timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     for name in ("cohort.cn.tsv", "cohort.allele.tsv"):
@@ -326,14 +330,14 @@ def test_ranks_flag_starts_the_ranks_itself(device, tmp_path):
         assert a == b, name
 
 
-def test_configs3_in_small_sixteen_samples_over_five_ranks(device, tmp_path):
+def test_configs3_in_small_sixteen_samples_over_five_ranks(device, tmp_path, monkeypatch):
     """configs[3] reduced (BASELINE.json: 64 samples x 5 M reads, --cn-cohort, 8 GPUs; the full size is
     tests/run_cohort_cfg3.py): 16 samples through ``python -m kir_graph_amd.main --cn-cohort --ranks 5`` on this GPU
     (file backend; the pool allows six processes on a card and this test process is one of them) -- every TSV equals the single-process run byte for byte,
     and the copy numbers equal the oracle's fit on the pooled depths (main.py:572-589, kir_cn.py:61, 167-186)."""
     import subprocess
     import sys
-    sidx, folder, sams, samples = _cohort(tmp_path, n_samples=16, n_pairs=2500)
+    sidx, folder, sams, samples = _cohort(tmp_path, monkeypatch, n_samples=16, n_pairs=2500)
     one = tmp_path / "one"
     _run(folder, one, sams, ["--cn-cohort"])
     many = tmp_path / "many"
@@ -341,7 +345,7 @@ def test_configs3_in_small_sixteen_samples_over_five_ranks(device, tmp_path):
     cmd = [sys.executable, "-m", "kir_graph_amd.main", "--step-skip-extraction", "--index-folder", folder,
            "--output-folder", str(many), "--allele-strategy", "pv", "--no-variant-json", "--cn-cohort", "--ranks", "5",
            "--log-level", "WARNING"] + [x for s in sams for x in ("--alignment", s)]
-    res = subprocess.run(cmd, env=dict(os.environ, GK_COMM_BACKEND="file", PYTHONPATH=root), cwd=root,
+    res = subprocess.run(cmd, env=dict(os.environ, GK_COMM_BACKEND="file", PYTHONPATH=root), cwd=tmp_path,
                          capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     names = sorted(p.name for p in one.iterdir())
