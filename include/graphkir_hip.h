@@ -237,6 +237,27 @@ int gk_compat(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr 
               int32_t vbeg, int32_t vend, gk_dptr d_mask, int32_t words, int32_t n_allele, int32_t keep_empty,
               gk_dptr d_probs, gk_dptr d_miss, gk_dptr d_nvar);
 
+/* ---- novel-variant discovery after typing (novel_discover.py; kernels in csrc/gk_novel.hip).
+ * gk_novel_assign = groupReadByAllele (48-70) on d_probs, gk_compat's column-major double [n_cols][n_rows] table of the
+ *   gene's DISTINCT called alleles (a mask with one bit per column); col_entries[k] = bitmask of the called-list entries
+ *   that name column k (1 <= n_entries <= 16).  d_code uint16 [n_rows] receives each row's group = the entries whose
+ *   column equals the row maximum exactly (np.equal); code_out (may be NULL) a host copy.  count_out / first_out
+ *   [1 << n_cols], indexed by the set of maximal columns: rows in the group and the first of them (undefined where the
+ *   count is 0).
+ * gk_novel_confusion = variantConfusionInRead / statNovelConfusion / extractNovelVariant (73-144) over the rows of the
+ *   singleton groups: d_rows / d_code as given to / returned by gk_novel_assign, d_vflag the error-correction drop flags
+ *   (bit 0 positive lists, bit 1 negative lists), d_carry uint32 [vend - vbeg] the restricted mask (bit entry_col[e]:
+ *   the allele of entry e carries the variant), entry_slot[e] the output slot of entry e (-1: not a singleton).
+ *   totals_out uint64 [n_slots][5] = novel, tp, tn, fp, fn; the (slot, ordinal, count, first-seen key) of every novel /
+ *   fp / fn variant with count >= 1, key = row << 20 | offset of the id in the row's lists, in no particular order.
+ *   *n_out = how many there are; GK_ERR_CAPACITY when that is more than max_out (call again with room). */
+int gk_novel_assign(gk_ctx* ctx, gk_dptr d_probs, int64_t n_rows, int32_t n_cols, const uint32_t* col_entries,
+                    int32_t n_entries, gk_dptr d_code, uint16_t* code_out, uint32_t* count_out, int32_t* first_out);
+int gk_novel_confusion(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_code, gk_dptr d_vflag,
+                       int32_t vbeg, int32_t vend, gk_dptr d_carry, const int32_t* entry_col, const int32_t* entry_slot,
+                       int32_t n_entries, int32_t n_slots, uint64_t* totals_out, int64_t max_out, int32_t* slot_out,
+                       int32_t* ord_out, uint32_t* count_out, uint64_t* key_out, int64_t* n_out);
+
 /* ---- log10 through a value table: log_probs = np.log10(probs) (typing_mulit_allele.py:263).
  * The distinct probability bit patterns are collected on the device, the HOST evaluates
  * numpy.log10 on them (so the bits are the reference's on this machine) and the table is applied
@@ -494,6 +515,25 @@ int gk_json_write_reads(const char* path, const char* sam_text, int64_t n_bytes,
  * position of reference g (header order) in the concatenated position space, gene_off[n_gene] = total;
  * counts_out uint32 [total][6] = A, C, G, T, N, '*'. */
 int gk_bam_pileup(gk_bam* bam, const int64_t* gene_off, int32_t n_gene, uint32_t* counts_out);
+/* base counts at listed sites, counting only reads of a group: the native form of queryPileup + countFilterPileup
+ * (novel_discover.py:237-264, pysam `AlignmentFile.pileup` with its defaults; the rules are listed in
+ * csrc/gk_bamread.cpp).  `path` is a coordinate-sorted BAM; with `{path}.bai` next to it only the BGZF blocks that
+ * overlap the sites are inflated, without it the file is read through.  sites int64 [n_sites][2] = (reference
+ * ordinal in header order, 0-based position); a record counts at site s when the FNV-1a 64 key of its query name
+ * (gk_sam_name_keys) is name_keys[k] with key_group[k] == site_group[s]; each name once per site, the later record
+ * in pileup order winning.  counts_out uint32 [n_sites][6] = A, C, G, T, N, '*' (a name whose records only delete
+ * the site). */
+int gk_bam_pileup_sites(const char* path, const int64_t* sites, int64_t n_sites, const uint64_t* name_keys,
+                        const int32_t* key_group, int64_t n_keys, const int32_t* site_group, uint32_t* counts_out);
+/* FNV-1a 64 of the query name (text up to the first tab) of the given 0-based lines of a SAM text. */
+int gk_sam_name_keys(const char* sam_text, int64_t n_bytes, const int64_t* line_idx, int64_t n_lines, uint64_t* keys_out);
+/* gk_bam_write_lines with a read group per line: the grouped BAM of groupReadToBam (novel_discover.py:216-234).
+ * `rg_text` (n_rg bytes of '@RG' lines) follows the header; line i gets "\tRG:Z:" + tags[line_group[i]] appended
+ * while it is encoded. */
+int gk_bam_write_lines_tagged(const char* path, const char* header_text, int64_t n_header, const char* rg_text,
+                              int64_t n_rg, const char* sam_text, int64_t n_bytes, const int64_t* line_idx,
+                              const int32_t* line_group, int64_t n_lines, const char* const* tags, int32_t n_tags,
+                              int32_t coordinate_sort);
 
 /* ---- read depth: replaces `samtools depth -aa {name}.no_multi.bam` (samtools_utils.py:9-14).
  * Depth of every backbone position from the M runs of the filter-passing pairs of a tabulation made

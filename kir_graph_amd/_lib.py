@@ -143,6 +143,17 @@ _SIGS = {
     "gk_bam_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "gk_bam_header": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "gk_bam_pileup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gk_bam_pileup_sites": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_void_p]),
+    "gk_sam_name_keys": (C.c_int, [C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "gk_bam_write_lines_tagged": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_char_p,
+                                            C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                            C.c_int32]),
+    "gk_novel_assign": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_uint64,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gk_novel_confusion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_uint64, C.c_int32,
+                                     C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "gk_bam_write": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int64, C.c_int32]),
     "gk_bam_write_lines": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_void_p, C.c_int64,
                                      C.c_int32]),

@@ -10,7 +10,7 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 SOURCES = ["gk_runtime.hip", "gk_scan.hip", "gk_tabulate.hip", "gk_typing.hip", "gk_lut.hip",
            "gk_search.hip", "gk_bound.hip", "gk_em.hip", "gk_cn.hip", "gk_depth.hip", "gk_sampack.cpp", "gk_bamread.cpp", "gk_textout.cpp",
-           "gk_comm.cpp", "gk_hostsearch.cpp"]
+           "gk_comm.cpp", "gk_hostsearch.cpp", "gk_novel.hip"]
 
 
 def hipcc() -> str:
@@ -56,6 +56,9 @@ KERNEL_SOURCES = {
     "em_sets_verify": ["gk_em.hip", "gk_common.h"],
     "em_sets_emit": ["gk_em.hip", "gk_common.h"],
     "em_kernel_genes": ["gk_em.hip", "gk_common.h"],
+    "novel_assign": ["gk_novel.hip", "gk_common.h"],
+    "novel_confusion": ["gk_novel.hip", "gk_common.h"],
+    "novel_compact": ["gk_novel.hip", "gk_common.h"],
 }
 
 

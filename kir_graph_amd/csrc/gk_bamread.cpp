@@ -11,6 +11,7 @@
 // written by the test suite's own encoder, not against samtools output ("parity unpinned").
 #include <dlfcn.h>
 #include <sys/stat.h>
+#include <unistd.h>
 #include <zlib.h>
 
 #include <algorithm>
@@ -1317,8 +1318,10 @@ void split_sam_text(std::string_view text, std::string& header, SamHeaderRefs& r
   }
 }
 
+// line_group / tags (optional): line i is encoded with "\tRG:Z:" + tags[line_group[i]] appended
 int write_bam_lines(const char* path, const std::string& header, const SamHeaderRefs& refs,
-                    const std::vector<std::string_view>& lines, int32_t coordinate_sort);
+                    const std::vector<std::string_view>& lines, int32_t coordinate_sort,
+                    const int32_t* line_group = nullptr, const std::vector<std::string>* tags = nullptr);
 
 }  // namespace
 
@@ -1352,10 +1355,64 @@ extern "C" int gk_bam_write_lines(const char* path, const char* header_text, int
   return write_bam_lines(path, header, refs, lines, coordinate_sort);
 }
 
+// The grouped BAM of groupReadToBam (novel_discover.py:216-234): the header of the input BAM, one '@RG' line per group,
+// the pairs of every group with "\tRG:Z:<group>" appended to both lines; sorted and indexed (utils.samtobam).
+extern "C" int gk_bam_write_lines_tagged(const char* path, const char* header_text, int64_t n_header, const char* rg_text,
+                                         int64_t n_rg, const char* sam_text, int64_t n_bytes, const int64_t* line_idx,
+                                         const int32_t* line_group, int64_t n_lines, const char* const* tags,
+                                         int32_t n_tags, int32_t coordinate_sort) {
+  if (!path || (!sam_text && n_bytes) || (!line_idx && n_lines) || (!line_group && n_lines) || (!header_text && n_header) ||
+      (!rg_text && n_rg) || (!tags && n_tags) || n_tags < 0) {
+    gk_set_error("null argument");
+    return GK_ERR_ARG;
+  }
+  std::string header;
+  SamHeaderRefs refs;
+  split_sam_text(std::string_view(header_text, (size_t)n_header), header, refs, nullptr);
+  if (n_rg) header.append(rg_text, (size_t)n_rg);
+  if (!header.empty() && header.back() != '\n') header.push_back('\n');
+  std::vector<std::string> tag_list((size_t)n_tags);
+  for (int32_t k = 0; k < n_tags; ++k) {
+    if (!tags[k]) { gk_set_error("null tag"); return GK_ERR_ARG; }
+    tag_list[(size_t)k] = tags[k];
+  }
+  const std::string_view text(sam_text, (size_t)n_bytes);
+  const std::vector<int64_t> starts = gk_line_starts(text);
+  std::vector<std::string_view> lines((size_t)n_lines);
+  for (int64_t i = 0; i < n_lines; ++i) {
+    if (line_idx[i] < 0 || (size_t)line_idx[i] + 1 >= starts.size()) { gk_set_error("line number out of range"); return GK_ERR_ARG; }
+    if (line_group[i] < 0 || line_group[i] >= n_tags) { gk_set_error("read group out of range"); return GK_ERR_ARG; }
+    lines[(size_t)i] = gk_line_at(text, starts, line_idx[i]);
+  }
+  return write_bam_lines(path, header, refs, lines, coordinate_sort, line_group, &tag_list);
+}
+
+static inline uint64_t fnv1a64(const char* p, size_t n) {
+  uint64_t h = 1469598103934665603ull;
+  for (size_t i = 0; i < n; ++i) { h ^= (uint8_t)p[i]; h *= 1099511628211ull; }
+  return h;
+}
+
+// FNV-1a 64 of the query names of the given lines: the keys gk_bam_pileup_sites selects reads by
+extern "C" int gk_sam_name_keys(const char* sam_text, int64_t n_bytes, const int64_t* line_idx, int64_t n_lines,
+                                uint64_t* keys_out) {
+  if ((!sam_text && n_bytes) || (n_lines && (!line_idx || !keys_out))) { gk_set_error("null argument"); return GK_ERR_ARG; }
+  const std::string_view text(sam_text ? sam_text : "", (size_t)n_bytes);
+  const std::vector<int64_t> starts = gk_line_starts(text);
+  for (int64_t i = 0; i < n_lines; ++i) {
+    if (line_idx[i] < 0 || (size_t)line_idx[i] + 1 >= starts.size()) { gk_set_error("line number out of range"); return GK_ERR_ARG; }
+    const std::string_view line = gk_line_at(text, starts, line_idx[i]);
+    const size_t t = line.find('\t');
+    keys_out[i] = fnv1a64(line.data(), t == std::string_view::npos ? line.size() : t);
+  }
+  return GK_OK;
+}
+
 namespace {
 
 int write_bam_lines(const char* path, const std::string& header, const SamHeaderRefs& refs,
-                    const std::vector<std::string_view>& lines, int32_t coordinate_sort) {
+                    const std::vector<std::string_view>& lines, int32_t coordinate_sort, const int32_t* line_group,
+                    const std::vector<std::string>* tags) {
   struct Enc { std::string rec; int32_t ref_id, pos0; };
   std::vector<Enc> enc(lines.size());
   std::vector<char> bad((size_t)std::max(ingest_threads(), 1), 0);
@@ -1363,8 +1420,17 @@ int write_bam_lines(const char* path, const std::string& header, const SamHeader
     const size_t n = lines.size();
     const int n_thr = (int)std::min<size_t>((size_t)ingest_threads(), std::max<size_t>(n / 1024, 1));
     auto work = [&](int t, size_t a, size_t b) {
-      for (size_t i = a; i < b; ++i)
-        if (!encode_record(lines[i], refs.names, enc[i].rec, enc[i].ref_id, enc[i].pos0)) { bad[(size_t)t] = 1; return; }
+      std::string tagged;
+      for (size_t i = a; i < b; ++i) {
+        std::string_view line = lines[i];
+        if (line_group) {       // the read group tag goes on while the line is encoded (no text of the whole file)
+          tagged.assign(line.data(), line.size());
+          tagged += "\tRG:Z:";
+          tagged += (*tags)[(size_t)line_group[i]];
+          line = tagged;
+        }
+        if (!encode_record(line, refs.names, enc[i].rec, enc[i].ref_id, enc[i].pos0)) { bad[(size_t)t] = 1; return; }
+      }
     };
     if (n_thr <= 1) work(0, 0, n);
     else {
@@ -1594,4 +1660,339 @@ extern "C" int gk_bam_pileup(gk_bam* b, const int64_t* gene_off, int32_t n_gene,
       if (x.qual >= 13 && x.pos >= 0 && x.pos < len) counts_out[(off + x.pos) * 6 + x.code] += 1;
   }
   return GK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Base counts at a few sites for the reads of a group: the native form of queryPileup + countFilterPileup
+// (novel_discover.py:237-264), which walk pysam's `AlignmentFile.pileup(ref, pos, pos + 1)` with its defaults.
+// The model of those defaults (pysam is not in this image, so parity is unpinned; tests/test_novel_host.py restates
+// the rules in Python and checks this code against them):
+//   stepper "all"        records flagged UNMAP / SECONDARY / QCFAIL / DUP are skipped;
+//   ignore_orphans       so are paired records that are not in a proper pair;
+//   max_depth 8000       only the first 8000 remaining records covering the site, in file order, take part;
+//   ignore_overlaps      where both mates of a pair cover the site, the earlier one in file order ("first") and the
+//                        later one are adjusted as htslib's tweak_overlap_quality does: equal bases -> first keeps
+//                        min(200, q1 + q2), the later 0; different bases -> the better one (first on a tie) keeps 0.8 of
+//                        its quality, the other 0;
+//   min_base_quality 13  a base of lower (adjusted) quality is not in the column;
+//   queryPileup          deletions and reference skips give no base; a name keeps the base of its LAST record in the
+//                        column (dict assignment);
+//   countFilterPileup    only names of the site's group count, once each.
+// A name of the group whose records only delete the site is counted as '*' (queryPileup leaves it out: callers that
+// restate the reference ignore that column).
+// With the `.bai` that gk_bam_write writes next to the file, only the BGZF blocks from the linear-index entry of each
+// site's 16 kb window onwards are read and inflated, up to the first record that starts past the site; without an
+// index every block is read and inflated once and each record visits the sites it covers.
+namespace {
+
+// Blocks are read from the file one at a time (pread of the block's bytes only), so a seek costs the blocks it touches
+// and never the whole file.
+struct BgzfFile {
+  FILE* fp = nullptr;
+  uint64_t size = 0;                     // bytes of the file
+  std::vector<uint8_t> comp;             // the compressed block at hand
+  uint64_t cur = UINT64_MAX, next = 0;   // file offset of the inflated block, of the one after it
+  std::vector<uint8_t> buf;
+  size_t at = 0;
+  z_stream zs{};
+  bool zs_ok = false;
+
+  ~BgzfFile() {
+    if (zs_ok) inflateEnd(&zs);
+    if (fp) fclose(fp);
+  }
+  bool pread_at(uint64_t off, size_t n, uint8_t* dst) {
+    return pread(fileno(fp), dst, n, (off_t)off) == (ssize_t)n;
+  }
+  bool load(uint64_t off) {
+    if (off == cur) { at = 0; return true; }
+    if (off + 18 > size) return false;
+    uint8_t hd[18];
+    if (!pread_at(off, 18, hd)) return false;
+    if (hd[0] != 31 || hd[1] != 139 || hd[2] != 8 || !(hd[3] & 4)) return false;
+    const uint32_t xlen = rd16(hd + 10);
+    uint32_t bsize = 0;
+    comp.resize(12u + xlen);
+    if (!pread_at(off, comp.size(), comp.data())) return false;
+    for (uint32_t x = 0; x + 4 <= xlen;) {
+      const uint8_t* f = comp.data() + 12 + x;
+      const uint32_t slen = rd16(f + 2);
+      if (f[0] == 66 && f[1] == 67 && slen == 2 && x + 6 <= xlen) bsize = rd16(f + 4);
+      x += 4 + slen;
+    }
+    const uint64_t total = (uint64_t)bsize + 1;
+    if (!bsize || off + total > size || total < 12u + xlen + 8u) return false;
+    comp.resize(total);
+    if (!pread_at(off, total, comp.data())) return false;
+    const uint8_t* h = comp.data();
+    const uint32_t isize = rd32(h + total - 4);
+    buf.resize(isize);
+    if (!zs_ok) {
+      if (inflateInit2(&zs, -15) != Z_OK) return false;
+      zs_ok = true;
+    } else if (inflateReset(&zs) != Z_OK) {
+      return false;
+    }
+    zs.next_in = const_cast<uint8_t*>(h + 12 + xlen);
+    zs.avail_in = (uInt)(total - 12 - xlen - 8);
+    zs.next_out = buf.data();
+    zs.avail_out = (uInt)isize;
+    const int rc = inflate(&zs, Z_FINISH);
+    if (rc != Z_STREAM_END || zs.avail_out != 0) return false;
+    cur = off;
+    next = off + total;
+    at = 0;
+    return true;
+  }
+  bool seek(uint64_t voff) {
+    if (!load(voff >> 16)) return false;
+    at = (size_t)(voff & 0xFFFF);
+    return at <= buf.size();
+  }
+  // n bytes of the stream; false at its end (or on a damaged block)
+  bool read(void* dst, size_t n) {
+    uint8_t* d = (uint8_t*)dst;
+    while (n) {
+      if (at == buf.size()) {
+        if (next >= size || !load(next)) return false;
+        continue;
+      }
+      const size_t k = std::min(n, buf.size() - at);
+      memcpy(d, buf.data() + at, k);
+      d += k; at += k; n -= k;
+    }
+    return true;
+  }
+};
+
+struct SiteEntry { uint64_t key; uint8_t code, qual; bool is_del; };
+
+// the entry of one record at reference position `pos` (false when the record does not cover it or skips it)
+bool record_at(const std::vector<uint8_t>& r, int64_t pos, uint8_t& code, uint8_t& qual, bool& is_del) {
+  const uint8_t* p = r.data();
+  const uint32_t l_name = p[8], n_cig = rd16(p + 12), l_seq = rd32(p + 16);
+  const size_t need = 32ull + l_name + 4ull * n_cig + (l_seq + 1) / 2 + l_seq;
+  if (need > r.size()) return false;
+  const uint8_t* cig = p + 32 + l_name;
+  const uint8_t* seq = cig + 4ull * n_cig;
+  const uint8_t* qs = seq + (l_seq + 1) / 2;
+  int64_t ref = rds32(p + 4);
+  uint64_t ri = 0;
+  for (uint32_t c = 0; c < n_cig; ++c) {
+    const uint32_t v = rd32(cig + 4ull * c), op = v & 15u, len = v >> 4;
+    if (op == 0 || op == 7 || op == 8) {
+      if (pos < ref + len) {
+        const uint64_t q = ri + (uint64_t)(pos - ref);
+        if (q >= l_seq) return false;
+        static const uint8_t kCode[16] = {4, 0, 1, 4, 2, 4, 4, 4, 3, 4, 4, 4, 4, 4, 4, 4};
+        code = kCode[(seq[q >> 1] >> ((~q & 1u) << 2)) & 15u];
+        qual = qs[q];
+        is_del = false;
+        return true;
+      }
+      ref += len; ri += len;
+    } else if (op == 2 || op == 3) {
+      if (pos < ref + len) {
+        if (op == 3) return false;             // a reference skip is never in a column's reads that give a base
+        code = 5; qual = 0; is_del = true;
+        return true;
+      }
+      ref += len;
+    } else if (op == 1 || op == 4) {
+      ri += len;
+    }
+    if (ref > pos) return false;
+  }
+  return false;
+}
+
+int64_t record_end(const std::vector<uint8_t>& r) {
+  const uint8_t* p = r.data();
+  const uint32_t l_name = p[8], n_cig = rd16(p + 12);
+  if (32ull + l_name + 4ull * n_cig > r.size()) return rds32(p + 4);
+  int64_t span = 0;
+  for (uint32_t c = 0; c < n_cig; ++c) {
+    const uint32_t v = rd32(p + 32 + l_name + 4ull * c), op = v & 15u;
+    if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += v >> 4;
+  }
+  return rds32(p + 4) + (span > 0 ? span : 1);
+}
+
+bool usable_flag(uint32_t flag) {
+  if (flag & (4u | 256u | 512u | 1024u)) return false;
+  return !((flag & 1u) && !(flag & 2u));
+}
+
+// one column: the records (file order) of the group's names -> counts
+void count_column(std::vector<SiteEntry>& col, uint32_t* counts) {
+  // overlapping mates: the first and the second record of a name in the column
+  std::unordered_map<uint64_t, size_t> first;
+  for (size_t i = 0; i < col.size(); ++i) {
+    auto it = first.find(col[i].key);
+    if (it == first.end()) { first.emplace(col[i].key, i); continue; }
+    SiteEntry& a = col[it->second];
+    SiteEntry& b = col[i];
+    if (!a.is_del && !b.is_del) {
+      if (a.code == b.code) {
+        a.qual = (uint8_t)std::min<int>(200, (int)a.qual + (int)b.qual);
+        b.qual = 0;
+      } else if (a.qual >= b.qual) {
+        a.qual = (uint8_t)(0.8 * a.qual);
+        b.qual = 0;
+      } else {
+        b.qual = (uint8_t)(0.8 * b.qual);
+        a.qual = 0;
+      }
+    }
+    first.erase(it);
+  }
+  std::unordered_map<uint64_t, int> base;     // name -> code of its last base (5: deletions only)
+  for (const SiteEntry& e : col) {
+    if (e.is_del) { base.emplace(e.key, 5); continue; }
+    if (e.qual < 13) continue;
+    base[e.key] = e.code;
+  }
+  for (const auto& kv : base) counts[kv.second] += 1;
+}
+
+bool read_record(BgzfFile& f, std::vector<uint8_t>& rec) {
+  uint8_t len4[4];
+  if (!f.read(len4, 4)) return false;
+  const uint32_t n = rd32(len4);
+  if (n < 32 || n > (1u << 28)) return false;
+  rec.resize(n);
+  return f.read(rec.data(), n);
+}
+
+}  // namespace
+
+extern "C" int gk_bam_pileup_sites(const char* path, const int64_t* sites, int64_t n_sites, const uint64_t* name_keys,
+                                   const int32_t* key_group, int64_t n_keys, const int32_t* site_group,
+                                   uint32_t* counts_out) {
+  if (!path || n_sites < 0 || n_keys < 0 || (n_sites && (!sites || !site_group || !counts_out)) ||
+      (n_keys && (!name_keys || !key_group))) {
+    gk_set_error("bad site pileup arguments");
+    return GK_ERR_ARG;
+  }
+  if (n_sites == 0) return GK_OK;
+  memset(counts_out, 0, sizeof(uint32_t) * 6 * (size_t)n_sites);
+  return guarded("gk_bam_pileup_sites", [&]() -> int {
+    BgzfFile f;
+    {
+      f.fp = fopen(path, "rb");
+      if (!f.fp) { gk_set_error("cannot open %s", path); return GK_ERR_ARG; }
+      struct stat st;
+      if (fstat(fileno(f.fp), &st) != 0) { gk_set_error("cannot stat %s", path); return GK_ERR_ARG; }
+      f.size = (uint64_t)st.st_size;
+    }
+    // header: magic, text, references
+    uint8_t b4[4];
+    if (!f.seek(0) || !f.read(b4, 4) || memcmp(b4, "BAM\1", 4) != 0) { gk_set_error("%s is not a BAM file", path); return GK_ERR_ARG; }
+    if (!f.read(b4, 4)) { gk_set_error("truncated BAM header"); return GK_ERR_ARG; }
+    std::vector<uint8_t> skip(rd32(b4));
+    if (!f.read(skip.data(), skip.size()) || !f.read(b4, 4)) { gk_set_error("truncated BAM header"); return GK_ERR_ARG; }
+    const int32_t n_ref = rds32(b4);
+    for (int32_t k = 0; k < n_ref; ++k) {
+      if (!f.read(b4, 4)) { gk_set_error("truncated BAM header"); return GK_ERR_ARG; }
+      skip.resize((size_t)rd32(b4) + 4);
+      if (!f.read(skip.data(), skip.size())) { gk_set_error("truncated BAM header"); return GK_ERR_ARG; }
+    }
+    const uint64_t first_rec = f.cur << 16 | f.at;
+    std::unordered_map<uint64_t, int32_t> group_of;
+    group_of.reserve((size_t)n_keys * 2);
+    for (int64_t k = 0; k < n_keys; ++k) group_of[name_keys[k]] = key_group[k];
+    // sites in (reference, position) order
+    std::vector<int64_t> order((size_t)n_sites);
+    for (int64_t s = 0; s < n_sites; ++s) order[(size_t)s] = s;
+    std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) {
+      return sites[2 * x] != sites[2 * y] ? sites[2 * x] < sites[2 * y] : sites[2 * x + 1] < sites[2 * y + 1];
+    });
+    std::vector<std::vector<SiteEntry>> cols((size_t)n_sites);
+    std::vector<int32_t> depth((size_t)n_sites, 0);
+    constexpr int32_t kMaxDepth = 8000;
+    std::vector<uint8_t> rec;
+    auto visit = [&](int64_t s) {      // rec covers the reference of site s; add it to the column when it covers the site
+      if (depth[(size_t)s] >= kMaxDepth) return;
+      const uint8_t* p = rec.data();
+      uint8_t code = 0, qual = 0;
+      bool is_del = false;
+      if (!record_at(rec, sites[2 * s + 1], code, qual, is_del)) return;
+      ++depth[(size_t)s];
+      const uint64_t key = fnv1a64((const char*)p + 32, strnlen((const char*)p + 32, p[8]));
+      auto it = group_of.find(key);
+      if (it == group_of.end() || it->second != site_group[s]) return;
+      cols[(size_t)s].push_back({key, code, qual, is_del});
+    };
+    // the linear index of every reference, when the .bai is there
+    std::vector<std::vector<uint64_t>> linear;
+    bool indexed = false;
+    {
+      const std::string bai = std::string(path) + ".bai";
+      FILE* fi = fopen(bai.c_str(), "rb");
+      if (fi) {
+        std::vector<uint8_t> x;
+        struct stat st;
+        if (fstat(fileno(fi), &st) == 0) {
+          x.resize((size_t)st.st_size);
+          if (fread(x.data(), 1, x.size(), fi) != x.size()) x.clear();
+        }
+        fclose(fi);
+        size_t at = 0;
+        auto need = [&](size_t n) { return at + n <= x.size(); };
+        bool ok = need(8) && memcmp(x.data(), "BAI\1", 4) == 0 && rds32(x.data() + 4) == n_ref;
+        at = 8;
+        for (int32_t r = 0; ok && r < n_ref; ++r) {
+          if (!need(4)) { ok = false; break; }
+          const uint32_t n_bin = rd32(x.data() + at); at += 4;
+          for (uint32_t b = 0; ok && b < n_bin; ++b) {
+            if (!need(8)) { ok = false; break; }
+            const uint32_t n_chunk = rd32(x.data() + at + 4);
+            at += 8;
+            if (!need(16ull * n_chunk)) { ok = false; break; }
+            at += 16ull * n_chunk;
+          }
+          if (!ok || !need(4)) { ok = false; break; }
+          const uint32_t n_intv = rd32(x.data() + at); at += 4;
+          if (!need(8ull * n_intv)) { ok = false; break; }
+          std::vector<uint64_t> lin(n_intv);
+          for (uint32_t w = 0; w < n_intv; ++w) lin[w] = (uint64_t)rd32(x.data() + at + 8ull * w) | (uint64_t)rd32(x.data() + at + 8ull * w + 4) << 32;
+          at += 8ull * n_intv;
+          linear.push_back(std::move(lin));
+        }
+        indexed = ok;
+      }
+    }
+    if (indexed) {
+      for (int64_t s : order) {
+        const int64_t ref = sites[2 * s], pos = sites[2 * s + 1];
+        if (ref < 0 || ref >= n_ref || pos < 0) continue;
+        const std::vector<uint64_t>& lin = linear[(size_t)ref];
+        const size_t w = (size_t)(pos >> 14);
+        if (w >= lin.size() || lin[w] == 0) continue;          // no record overlaps the window
+        if (!f.seek(lin[w])) { gk_set_error("bad virtual offset in %s.bai", path); return GK_ERR_ARG; }
+        while (read_record(f, rec)) {
+          const uint8_t* p = rec.data();
+          const int32_t r_ref = rds32(p), r_pos = rds32(p + 4);
+          if (r_ref != ref || r_pos > pos) break;               // coordinate sorted: nothing later covers the site
+          if (!usable_flag(rd16(p + 14)) || record_end(rec) <= pos) continue;
+          visit(s);
+        }
+      }
+    } else {
+      if (!f.seek(first_rec)) { gk_set_error("truncated BAM file"); return GK_ERR_ARG; }
+      while (read_record(f, rec)) {
+        const uint8_t* p = rec.data();
+        const int32_t r_ref = rds32(p), r_pos = rds32(p + 4);
+        if (r_ref < 0 || !usable_flag(rd16(p + 14))) continue;
+        const int64_t r_end = record_end(rec);
+        // the sites on this reference in [r_pos, r_end)
+        auto lo = std::lower_bound(order.begin(), order.end(), (int64_t)r_pos, [&](int64_t s, int64_t v) {
+          return sites[2 * s] != r_ref ? sites[2 * s] < r_ref : sites[2 * s + 1] < v;
+        });
+        for (auto it = lo; it != order.end() && sites[2 * *it] == r_ref && sites[2 * *it + 1] < r_end; ++it) visit(*it);
+      }
+    }
+    for (int64_t s = 0; s < n_sites; ++s) count_column(cols[(size_t)s], counts_out + 6 * s);
+    return GK_OK;
+  });
 }

@@ -8,7 +8,7 @@ readMapping 124-168, alleleTyping 171-220, getCommonName 223-250).  What differs
   is handed to typing in memory (the ``.variant.json`` is still written unless
   ``--no-variant-json``);
 * additive flags: ``--alignment`` (use existing name-collated SAM/BAM instead of running hisat2),
-  ``--no-variant-json``; ``--allele-strategy`` also accepts ``pv`` (= full) and maps ``report`` to
+  ``--no-variant-json``, ``--novel-discovery`` (novel_discover.py after typing: ``{result}.novel.*``); ``--allele-strategy`` also accepts ``pv`` (= full) and maps ``report`` to
   the EM strategy (the reference forwards ``report`` to a factory that rejects it, main.py:192);
 * launched with RANK / WORLD_SIZE / LOCAL_RANK set (``torchrun`` or any launcher) the samples are sharded over
   the ranks (one GPU each, largest inputs first); ``--cn-cohort`` then pools the gene depths with one
@@ -66,14 +66,15 @@ def hisatMap(index: str, f1: str, f2: str, output_file: str, threads: int = 1) -
 
 
 def mapSamples(names, reads, index, index_ref, exon_region_only=False, alignments=None, write_json=True,
-               keep_records=False):
+               keep_records=False, keep_text=False):
     """Graph mapping (external) -> tabulation (GPU) -> depth (GPU), one sample at a time (main.py:124-168).
 
     Yields ``(alignment file, "{name}.variant", SampleData, depth file)`` per sample, in order.  When a sample
     is yielded its by-products are on disk and its depth is computed, so what only they needed -- the SAM
     text of the pairs and the packed records in HBM -- has been released: the consumer holds the CSR of the
     tabulation only (and closes it after typing), whatever the size of the cohort.  ``keep_records``: the packed
-    records stay in HBM with the sample (``--cn-cohort`` parks a sample as its compact records, ``ParkedRecords``)."""
+    records stay in HBM with the sample (``--cn-cohort`` parks a sample as its compact records, ``ParkedRecords``).
+    ``keep_text``: the SAM lines of the pairs stay with the sample (``--novel-discovery`` writes them grouped)."""
     gk = GkIndex.load(index_ref)
     gene_len = readLocusLengths(index_ref)
     dev = defaultDevice()
@@ -110,7 +111,7 @@ def mapSamples(names, reads, index, index_ref, exon_region_only=False, alignment
     writes = []
     try:
         yield from _mapLoop(names, prepare, ahead, gk, gene_len, (copier, ingest), dindex, index_ref, exon_region_only,
-                            write_json, writer, writes, keep_records)
+                            write_json, writer, writes, keep_records, keep_text)
     finally:
         for w in writes:
             w.result()          # every hand-off file is complete (and any write error surfaces) before we return
@@ -118,7 +119,7 @@ def mapSamples(names, reads, index, index_ref, exon_region_only=False, alignment
 
 
 def _mapLoop(names, prepare, ahead, gk, gene_len, staging, dindex, index_ref, exon_region_only, write_json, writer, writes,
-             keep_records=False):
+             keep_records=False, keep_text=False):
     copier, dev = staging
     for name, source, pack in cohort.prefetched(range(len(names)), prepare, depth=ahead, workers=ahead):
         name += ".variant"
@@ -158,14 +159,15 @@ def _mapLoop(names, prepare, ahead, gk, gene_len, staging, dindex, index_ref, ex
             logger.info(f"[Graph] Filter exon read to {depth_name}.exon.tsv")
             filterDepth(depth_name + ".tsv", depth_name + ".exon.tsv", readExons(index_ref))
             depth_name += ".exon"
-        releaseInputs(data, keep_records)
+        releaseInputs(data, keep_records, keep_text)
         yield source, name, data, depth_name + ".tsv"
 
 
-def releaseInputs(data: SampleData, keep_records: bool = False) -> None:
-    """Drop what only the by-products and the depth needed: the SAM text of the pairs (host) and the packed
-    records (HBM, 256 B per pair; unless ``keep_records``).  The tabulation's lists stay for typing."""
-    data.pairs_text = None
+def releaseInputs(data: SampleData, keep_records: bool = False, keep_text: bool = False) -> None:
+    """Drop what only the by-products and the depth needed: the SAM text of the pairs (host; unless ``keep_text``) and
+    the packed records (HBM, 256 B per pair; unless ``keep_records``).  The tabulation's lists stay for typing."""
+    if not keep_text:
+        data.pairs_text = None
     data._reads = None
     mates = getattr(data.tab, "mates", None)
     if mates is not None and not keep_records:
@@ -234,21 +236,42 @@ def writeTyping(name: str, typer, called_alleles: list[str], warning_genes: list
     return name + ".tsv"
 
 
-def sampleTyper(method: str, release: bool = True) -> "cohort.SampleTyper":
+def discoverAfterTyping(typer, called_alleles: list[str], name: str, result: str, index_ref: str) -> None:
+    """Novel-variant discovery of one typed sample, on its tabulation in HBM (novel_discover.discoverSample):
+    ``{result}.novel.variant.tsv / .tsv / .fa / .bam / .txt``, the reads piled up from ``{name}.no_multi.bam``."""
+    from .novel_discover import discoverSample
+    data = typer._data
+    tab = typer._context()[0]
+    output = result + ".novel"
+    logger.info(f"[Novel] Discover novel variants ({output})")
+    with open(output + ".txt", "w") as descr:
+        discoverSample(data, list(called_alleles), index_ref, name + ".no_multi.bam", output, novel_descr=descr, tab=tab)
+    data.pairs_text = None
+
+
+def sampleTyper(method: str, release: bool = True, novel_index: str | None = None) -> "cohort.SampleTyper":
     """The typing stage of this process (``cohort.SampleTyper``: the sample lanes, search slots, urgent preamble and
     blocking waits that ``bench.py`` measures), finishing every sample the reference's way: its two files written, its
-    tabulation released.  Submit ``(SampleData or hand-off file, copy numbers, (name, cn_file))``."""
+    tabulation released.  Submit ``(SampleData or hand-off file, copy numbers, (name, cn_file))``.
+    ``novel_index`` (``--novel-discovery``): the index prefix; every typed sample then goes through novel_discover.py
+    (``{result}.novel.*``, typingNovelWrap of the reference's research/kg_main.py) before its tabulation is released."""
     def finish(typer, called_alleles, warning_genes, item):
         name, cn_file, source = item
-        if release or not isinstance(source, SampleData):      # done with this sample: free its HBM
-            tab = typer._data.tab
-            mates = getattr(tab, "mates", None)
-            if mates is not None:
-                mates.free()
-                tab.mates = None
-            tab.close()
-        logger.info(f"[Allele] {called_alleles} ({name})")
-        return writeTyping(name + typingSuffix(name, cn_file, method), typer, called_alleles, warning_genes)
+        result = name + typingSuffix(name, cn_file, method)
+        try:
+            if novel_index is not None:
+                discoverAfterTyping(typer, called_alleles, name, result, novel_index)
+        finally:       # a failed discovery still leaves the sample's typing files written and its HBM released
+            if release or not isinstance(source, SampleData):      # done with this sample: free its HBM
+                tab = typer._data.tab
+                mates = getattr(tab, "mates", None)
+                if mates is not None:
+                    mates.free()
+                    tab.mates = None
+                tab.close()
+            logger.info(f"[Allele] {called_alleles} ({name})")
+            written = writeTyping(result, typer, called_alleles, warning_genes)
+        return written
 
     return cohort.SampleTyper(method, finish=finish)
 
@@ -272,8 +295,18 @@ def alleleTyping(processed_bam, cn_files: list[str], method: str = "full", relea
     return allele_files
 
 
+class _Parser(argparse.ArgumentParser):
+    """Rejects flag combinations that cannot work, at argument time."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        if getattr(ns, "novel_discovery", False) and getattr(ns, "no_variant_json", False):
+            self.error("--novel-discovery needs the {name}.variant.no_multi.bam that --no-variant-json does not write")
+        return ns, rest
+
+
 def createParser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(description="Run Graph-KIR (MI355X typing path)",
+    p = _Parser(description="Run Graph-KIR (MI355X typing path)",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("--thread", default=1, help="Number of threads")
     p.add_argument("--engine", default="local", choices=["podman", "docker", "singularity", "local"],
@@ -309,6 +342,10 @@ def createParser() -> argparse.ArgumentParser:
     p.add_argument("--alignment", action="append",
                    help="Existing name-collated alignments (SAM / SAM.gz / BAM), one per sample: skips hisat2")
     p.add_argument("--no-variant-json", action="store_true", help="Do not write {name}.variant.json")
+    p.add_argument("--novel-discovery", action="store_true",
+                   help="After typing, look for novel variants of the called alleles in their reads: writes "
+                        "{result}.novel.variant.tsv / .tsv / .fa / .bam / .txt per sample (needs the .no_multi.bam, so "
+                        "not with --no-variant-json)")
     p.add_argument("--ranks", type=int, default=1,
                    help="Start this many rank processes (samples are sharded over them; ranks map to GPUs round robin, "
                         "so 3 x the GPU count keeps every GPU busy).  Not needed under torchrun / any launcher that "
@@ -398,7 +435,8 @@ def _runCohort(args, names, reads, cn_files, index, index_ref, cohort_name, comm
     kwargs = {"base_dev": float(args.cn_dist_dev), "start_base": 2}
     method = {"pv": "full", "report": "em"}.get(args.allele_strategy, args.allele_strategy)
     pooled_fit = args.cn_cohort and not all(cn_files)
-    lanes = sampleTyper(method)
+    novel = getattr(args, "novel_discovery", False)
+    lanes = sampleTyper(method, novel_index=index_ref if novel else None)
     try:
         allele_files, my_cn = _typeShare(args, lanes, pick(names), pick(reads), my_cn, pick, index, index_ref, cohort_name,
                                          comm, kwargs, pooled_fit)
@@ -417,7 +455,8 @@ def _typeShare(args, lanes, names, reads, my_cn, pick, index, index_ref, cohort_
     budget = int(float(os.environ.get("GK_RETAIN_GB", "64")) * 2**30)   # tabulations kept in HBM until the pooled fit
     samples = mapSamples(names, reads, index, index_ref, exon_region_only=args.cn_exon,
                          alignments=pick(args.alignment) if args.alignment else None,
-                         write_json=not args.no_variant_json, keep_records=pooled_fit and not args.step_skip_typing)
+                         write_json=not args.no_variant_json, keep_records=pooled_fit and not args.step_skip_typing,
+                         keep_text=getattr(args, "novel_discovery", False) and not args.step_skip_typing)
     for i, (_, name, data, depth_file) in enumerate(samples):
         depth_files.append(depth_file)
         if pooled_fit:
@@ -429,7 +468,8 @@ def _typeShare(args, lanes, names, reads, my_cn, pick, index, index_ref, cohort_
                 waiting.append((name, None))
                 continue
             size = int(0.12 * 256 * data.tab.n_pairs) + (1 << 20)      # what the compact records will take, roughly
-            if retained + size > budget or data.tab.mates is None:
+            # a sample whose reads novel discovery writes again waits as its .variant.json (the lines are in it)
+            if retained + size > budget or data.tab.mates is None or getattr(args, "novel_discovery", False):
                 if args.no_variant_json:
                     parked = name + ".npz"          # already written by mapSamples, unless hand-off files are lazy
                     if os.environ.get("GK_HANDOFF", "always") == "lazy":

@@ -60,6 +60,15 @@ class SynthIndex:
                 ex = " ".join(f"{s + 1}-{e + 1}" for s, e in self.exons[g])
                 f.write(f"{g}\t{g}\t0\t{n}\t{n}\t{ex}\t+\n")
 
+    def writeBackbone(self, prefix: str) -> None:
+        """Write ``{prefix}_backbone.fa``: the backbone sequences, as the HISAT2 index build leaves them."""
+        with open(prefix + "_backbone.fa", "w") as f:
+            for g in self.genes:
+                seq = self.backbone[g].tobytes().decode()
+                f.write(f">{g}\n")
+                for i in range(0, len(seq), 60):
+                    f.write(seq[i:i + 60] + "\n")
+
 
 def makeIndex(seed: int = 2022, n_genes: int = 15, len_range=(4200, 17000),
               var_range=(1000, 4000), allele_range=(30, 250),
