@@ -9,24 +9,32 @@ through the log10 value table and the allele selection of the strategy -- the gr
 (gk_sample_em).  The steps run through the package's own sample pipeline (kir_graph_amd.cohort: stagedSamples ->
 typeSamples), the one `python -m kir_graph_amd.main` types a cohort with.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what its headline figure needs and no more: it makes the
+inputs, warms up, times ONE leg of K steps, writes --dump-outputs if asked, and prints the line (~17 s on one MI355X besides
+the steps).  `--full` adds everything else described below: the second kind of leg, three legs of each kind, the two other
+workloads, the serial pass (kernels_serial, roofline), the command line's typing stage and the CPU baselines (~3 min).
+An option given explicitly (--legs, --serial-steps, --cpu-pairs, --cli-samples, --one-kind, --no-secondary) holds either way.
+
 Workloads.  Without --pairs / --method the line's headline (`value`) is BASELINE.json configs[2] -- 20 M reads = 10 M
-pairs per sample, --allele-strategy exonfirst (what the reference's own pipeline runs, kir/graphkir.py:76-87) -- and, on one
-GPU, two more workloads are measured the same way and reported as objects of the same line: `em` (configs[2],
+pairs per sample, --allele-strategy exonfirst (what the reference's own pipeline runs, kir/graphkir.py:76-87) -- and, with
+--full on one GPU, two more workloads are measured the same way and reported as objects of the same line: `em` (configs[2],
 --allele-strategy em: EM to convergence) and `configs1_pv` (configs[1]: 2 M reads, --allele-strategy pv -- the headline of
 rounds 1 - 4).  Each carries its own legs, `kernels_serial`, `roofline` and `cpu_baseline`.  With --pairs and / or --method:
 that one workload.  All use the synthetic example_index-shaped index (~2.4 k alleles in 15 genes), top_n 600, variant
-correction on.
+correction on.  The samples are made by bench.synth_sample / pack_sample: synth.makeSample + packed.packSample, bit for
+bit, in a fraction of their time.
 
 Two kinds of timed leg over the same K steps, each bracketed by a barrier + device synchronise on both sides, each kind
-timed `--legs` times (default 3) with the MEDIAN leg reported:
+timed `--legs` times (--full: 3; a plain run times the headline kind once) with the MEDIAN leg reported:
   host  (`value`)         a sample's records start in PINNED HOST MEMORY, in the compact form they cross PCIe in (~30 bytes
                           per mate: packed.CompactMates): the host-to-device copy and the expansion into 128-byte
                           records are inside the region (SURVEY.md section 8(d)), staged two samples ahead of the typing;
   hbm   (`hbm_resident`)  the records of the distinct samples are resident in HBM before the clock starts.
 `--inputs hbm` swaps the two (`value` from resident records, `pcie_inclusive` beside it).
 Consecutive steps take DIFFERENT samples: `--distinct N` distinct ones per rank in rotation (2 at configs[2] size -- a
-sample takes ~30 s to make -- 8 below), seeds 1031 + 7 rank + i.  With N >= steps + warmup the first leg types only samples
-nobody has typed before -- `legs[0]` then says what a NEW sample costs (value_table_new_per_sample, samples_repeated_pass).
+sample takes ~7 s and ~12 GB of host memory to make -- 8 below), seeds 1031 + 7 rank + i.  With N >= steps + warmup the
+first leg types only samples nobody has typed before -- `legs[0]` then says what a NEW sample costs
+(value_table_new_per_sample, samples_repeated_pass).
 
 ``--gpus N``: N ranks, one per GPU, every rank types its own samples (cohort sharding: weak scaling, no
 data-path collective); value = reads of all ranks / max-over-ranks time.  Started without a launcher
@@ -34,7 +42,8 @@ data-path collective); value = reads of all ranks / max-over-ranks time.  Starte
 anything here touches the GPU -- and relays rank 0's line; under `torchrun` (RANK / WORLD_SIZE set) it
 is one of the ranks.  Ranks meet through kir_graph_amd/comm.py (RCCL: barrier + max of the times).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects (--full; a plain run has `host` and
+`legs`):
   roofline        the dominant kernel of the step, from a SERIAL pass (one sample at a time on one stream, no prefetch)
                   run right after the timed legs: HIP-event time per launch, algorithmic bytes / operations per launch
                   (kir_graph_amd/roofmodel.py); `roofline.step` = the algorithmic bytes of ALL
@@ -52,7 +61,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
 
 ``--dump-outputs DIR`` also writes what the last timed step of each workload computed (the calls, and per gene the
 search's last step or the EM's abundances) as float64 arrays ``DIR/<workload>_<array>.npy``: the inputs are seeded, so the
-files of two builds run with the same arguments compare one for one.
+files of two builds run with the same arguments compare one for one.  Without --full the `em` and `configs1_pv` workloads
+then run for their outputs alone (warm-up and one leg each; not in the line).
 """
 from __future__ import annotations
 
@@ -154,18 +164,288 @@ def build_index(index_seed: int = 2022):
     return sidx, gidx, by_gene
 
 
-def build_sample(sidx, gidx, by_gene, seed: int, n_pairs: int):
-    from kir_graph_amd import synth, packed
-    sample = synth.makeSample(sidx, seed=seed, n_pairs=n_pairs, variants_by_gene=by_gene)
-    rec, table = packed.packSample(sample, gidx)
+def build_sample(sidx, gidx, by_gene, seed: int, n_pairs: int, threads: int = 1):
+    """(sample, records, string table): ``synth.makeSample`` + ``packed.packSample``, the records packed on ``threads``
+    threads (``pack_sample``); what the package's two functions make, faster."""
+    sample = synth_sample(sidx, seed=seed, n_pairs=n_pairs, variants_by_gene=by_gene)
+    rec, table = pack_sample(sample, gidx, threads)
     return sample, rec, table
+
+
+def synth_sample(index, seed: int = 1031, n_pairs: int = 2000,
+                 err_rate: float = 0.001, gene_cn: dict[str, int] | None = None,
+                 frac_multi: float = 0.03, frac_improper: float = 0.01,
+                 frac_clip: float = 0.01, read_len: int = 150,
+                 frag_mean: float = 400.0, frag_sd: float = 10.0,
+                 variants_by_gene: dict | None = None):
+    """``synth.makeSample`` -- the same draws, the same arrays bit for bit (tests/test_bench_inputs.py) -- in a
+    quarter of its time: the events are ordered by ONE stable argsort of a packed (mate, position, kind, error) key
+    instead of ``np.lexsort``, the graph-SNP lookup of NM touches the error events only, the backbone bases are one
+    gather.  Those three were 3 / 4 of the ~30 s a configs[2] sample took to make; the package's function stays the
+    definition.  Everything else is its text."""
+    import numpy as np
+    from kir_graph_amd.synth import BASES, EV_DEL, EV_INS, EV_SINGLE, SynthSample
+    rng = np.random.default_rng(seed)
+    genes = index.genes
+    if gene_cn is None:
+        gene_cn = {}
+        for g in genes:
+            gene_cn[g] = 2 if "3DL3" in g else int(rng.choice([0, 1, 2, 2, 2, 3]))
+    truth: dict[str, list[str]] = {}
+    haps: list[tuple[int, str]] = []
+    for gi, g in enumerate(genes):
+        cn = gene_cn.get(g, 0)
+        names = index.alleles[g]
+        picks = []
+        for c in range(cn):
+            if c and rng.random() < 0.2:
+                picks.append(picks[0])
+            else:
+                picks.append(names[int(rng.integers(0, len(names)))])
+        truth[g] = picks
+        haps.extend((gi, a) for a in picks)
+    if not haps:
+        raise ValueError("sample has no gene copies")
+    if variants_by_gene is None:
+        variants_by_gene = {}
+        for v in index.variants:
+            variants_by_gene.setdefault(v.ref, []).append(v)
+
+    weights = np.array([len(index.backbone[genes[gi]]) for gi, _ in haps], dtype=np.float64)
+    hap_of_pair = rng.choice(len(haps), size=n_pairs, p=weights / weights.sum())
+
+    ins_strings: list[str] = []
+    ins_lookup: dict[str, int] = {}
+
+    pos0 = np.zeros(2 * n_pairs, dtype=np.int32)
+    span = np.zeros(2 * n_pairs, dtype=np.int32)
+    ev_m: list[np.ndarray] = []
+    ev_p: list[np.ndarray] = []
+    ev_k: list[np.ndarray] = []
+    ev_v: list[np.ndarray] = []
+    pair_gene = np.zeros(n_pairs, dtype=np.int32)
+
+    for h, (gi, allele) in enumerate(haps):
+        pidx = np.nonzero(hap_of_pair == h)[0]
+        if not len(pidx):
+            continue
+        g = genes[gi]
+        pair_gene[pidx] = gi
+        bb = index.backbone[g]
+        L = len(bb)
+        hv = [v for v in variants_by_gene.get(g, []) if allele in v.allele]
+        hpos = np.array([v.pos for v in hv], dtype=np.int64)
+        hkind = np.array([{"single": EV_SINGLE, "insertion": EV_INS, "deletion": EV_DEL}[v.typ]
+                          for v in hv], dtype=np.uint8)
+        hval = np.zeros(len(hv), dtype=np.int32)
+        for i, v in enumerate(hv):
+            if v.typ == "single":
+                hval[i] = ord(str(v.val))
+            elif v.typ == "deletion":
+                hval[i] = int(v.val)
+            else:
+                s = str(v.val)
+                if s not in ins_lookup:
+                    ins_lookup[s] = len(ins_strings)
+                    ins_strings.append(s)
+                hval[i] = ins_lookup[s]
+        # allele coordinate -> reference position (-1 for inserted bases)
+        keep = np.ones(L, dtype=bool)
+        for v in hv:
+            if v.typ == "deletion":
+                keep[v.pos:v.pos + int(v.val)] = False
+        ref_of = np.nonzero(keep)[0].astype(np.int64)
+        ins_v = [v for v in hv if v.typ == "insertion"]
+        if ins_v:
+            at = np.searchsorted(ref_of, [v.pos for v in ins_v])
+            at = np.repeat(at, [len(str(v.val)) for v in ins_v])
+            ref_of = np.insert(ref_of, at, -1)
+        La = len(ref_of)
+        allele_base = bb.copy()
+        for v in hv:
+            if v.typ == "single":
+                allele_base[v.pos] = ord(str(v.val))
+
+        n = len(pidx)
+        frag = np.clip(np.rint(rng.normal(frag_mean, frag_sd, n)).astype(np.int64),
+                       2 * read_len // 2 + 10, La - 2)
+        frag = np.maximum(frag, read_len)
+        u = (rng.random(n) * (La - frag)).astype(np.int64)
+        starts = np.stack([u, u + frag - read_len], axis=1)  # [n, 2] allele coords
+        # both ends of each mate must be reference-aligned bases
+        for _ in range(8):
+            bad = (ref_of[starts] < 0) | (ref_of[starts + read_len - 1] < 0)
+            if not bad.any():
+                break
+            starts = np.where(bad, np.minimum(starts + 1, La - read_len), starts)
+        bad = (ref_of[starts] < 0) | (ref_of[starts + read_len - 1] < 0)
+        starts = np.where(bad, 0, starts)  # allele coordinate 0 is always aligned enough
+        m_ids = (2 * pidx[:, None] + np.arange(2)[None, :]).reshape(-1)
+        st = starts.reshape(-1)
+        p0 = ref_of[st]
+        pe = ref_of[st + read_len - 1] + 1
+        bad0 = (p0 < 0) | (pe <= 0)
+        if bad0.any():  # pathological allele start inside an insertion: fall back to a clean window
+            st = np.where(bad0, np.argmax(ref_of >= 0), st)
+            p0 = ref_of[st]
+            pe = ref_of[st + read_len - 1] + 1
+        pos0[m_ids] = p0
+        span[m_ids] = pe - p0
+
+        # allele-carried variants inside each mate
+        lo = np.searchsorted(hpos, p0, side="left")
+        hi = np.searchsorted(hpos, pe, side="left")
+        cnt = hi - lo
+        tot = int(cnt.sum())
+        if tot:
+            rep = np.repeat(np.arange(len(m_ids)), cnt)
+            offs = np.arange(tot) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+            vi = np.repeat(lo, cnt) + offs
+            k = hkind[vi]
+            p = hpos[vi]
+            ok = (k == EV_SINGLE) | (p > p0[rep])
+            ev_m.append(m_ids[rep][ok]); ev_p.append(p[ok].astype(np.int32))
+            ev_k.append(k[ok]); ev_v.append(hval[vi][ok])
+        # substitution errors on aligned bases
+        n_err = rng.binomial(read_len, err_rate, len(m_ids))
+        te = int(n_err.sum())
+        if te:
+            rep = np.repeat(np.arange(len(m_ids)), n_err)
+            off = rng.integers(0, read_len, te)
+            rp = ref_of[st[rep] + off]
+            ok = rp >= 0
+            rep, rp = rep[ok], rp[ok]
+            cur = allele_base[rp]
+            shift = rng.integers(1, 4, len(rp))
+            code = (np.searchsorted(BASES, cur) + shift) % 4
+            eb = BASES[code]
+            # priority 1 events: override allele base; dropped later if equal to backbone
+            ev_m.append(m_ids[rep]); ev_p.append(rp.astype(np.int32))
+            ev_k.append(np.full(len(rp), 8 + EV_SINGLE, dtype=np.uint8)); ev_v.append(eb.astype(np.int32))
+
+    if ev_m:
+        m = np.concatenate(ev_m); p = np.concatenate(ev_p)
+        k = np.concatenate(ev_k); v = np.concatenate(ev_v)
+    else:
+        m = np.zeros(0, np.int64); p = np.zeros(0, np.int32)
+        k = np.zeros(0, np.uint8); v = np.zeros(0, np.int32)
+    # order: mate, position, (ins < single < del like the walk), errors after allele singles -- the four packed into
+    # one int64 (positions < 2^15: the backbones are at most 17 kb) and sorted stably, which is what np.lexsort does
+    is_err = (k >= 8)
+    kk = (k & 7).astype(np.int64)
+    rank = np.where(kk == EV_INS, 0, np.where(kk == EV_SINGLE, 1, 2))
+    if len(p) and int(p.max()) >= 1 << 15:
+        raise ValueError("synth_sample: a position does not fit the packed sort key")
+    order = np.argsort((m.astype(np.int64) << 18) | (p.astype(np.int64) << 3) | (rank << 1) | is_err, kind="stable")
+    m, p, k, v, kk, is_err = m[order], p[order], k[order], v[order], kk[order], is_err[order]
+    # collapse same (mate, pos) singles: the last one (error) wins
+    single = kk == EV_SINGLE
+    nxt_same = np.zeros(len(m), dtype=bool)
+    if len(m) > 1:
+        nxt_same[:-1] = single[:-1] & single[1:] & (m[:-1] == m[1:]) & (p[:-1] == p[1:])
+    keep = ~nxt_same
+    # singles equal to the backbone are no mismatch at all
+    gname_of_m = pair_gene[m // 2]
+    bb_len = np.array([len(index.backbone[g]) for g in genes], dtype=np.int64)
+    bb_all = np.concatenate([index.backbone[g] for g in genes])
+    bb_at = (np.cumsum(bb_len) - bb_len)[gname_of_m] + np.minimum(p, bb_len[gname_of_m] - 1)
+    refbase = bb_all[bb_at].astype(np.int32)
+    keep &= ~(single & (v == refbase))
+    m, p, kk, v, is_err = m[keep], p[keep], kk[keep], v[keep], is_err[keep]
+
+    n_m = 2 * n_pairs
+    ev_cnt = np.bincount(m, minlength=n_m)
+    ev_off = np.zeros(n_m + 1, dtype=np.int64)
+    np.cumsum(ev_cnt, out=ev_off[1:])
+    # NM: HISAT2 counts only edits that are NOT variants of the graph (the reference's own example,
+    # hisat2.py:294, is a read with two graph deletions that must pass the NM <= 4 filter), so
+    # allele-carried variants cost nothing and substitution errors cost 1 unless they hit a graph SNP.
+    known = np.array(sorted((gi << 40) | (vv.pos << 8) | ord(str(vv.val))
+                            for gi, g in enumerate(genes) for vv in variants_by_gene.get(g, [])
+                            if vv.typ == "single"), dtype=np.int64)
+    err = np.nonzero(is_err)[0]           # only errors can be novel: the lookup on them alone
+    ekey = (pair_gene[m[err] // 2].astype(np.int64) << 40) | (p[err].astype(np.int64) << 8) | v[err].astype(np.int64)
+    novel = np.zeros(len(m), dtype=bool)
+    novel[err] = ~np.isin(ekey, known)
+    nm = np.bincount(m[novel], minlength=n_m).astype(np.int32)
+
+    # flags / NH / secondary / clipping
+    strand = rng.random(n_pairs) < 0.5
+    flag = np.zeros(n_m, dtype=np.uint16)
+    flag[0::2] = np.where(strand, 99, 83)
+    flag[1::2] = np.where(strand, 147, 163)
+    improper = rng.random(n_pairs) < frac_improper
+    flag[0::2] = np.where(improper, flag[0::2] & ~np.uint16(2), flag[0::2])
+    flag[1::2] = np.where(improper, flag[1::2] & ~np.uint16(2), flag[1::2])
+    # mates that would not fit the packed device record are reported as not properly paired (both
+    # the SAM and the packed route then drop the pair in filterRead)
+    n_single = np.bincount(m[kk == EV_SINGLE], minlength=n_m)
+    n_indel = np.bincount(m[kk != EV_SINGLE], minlength=n_m)
+    n_ins = np.bincount(m[kk == EV_INS], minlength=n_m)
+    too_big = (n_single > 16) | (n_ins > 6) | (2 * n_indel + 1 > 14) | (ev_cnt > 22)
+    big_pair = too_big[0::2] | too_big[1::2]
+    flag[0::2] = np.where(big_pair, flag[0::2] & ~np.uint16(2), flag[0::2])
+    flag[1::2] = np.where(big_pair, flag[1::2] & ~np.uint16(2), flag[1::2])
+    pair_nh = np.where(rng.random(n_pairs) < frac_multi, 2, 1).astype(np.uint8)
+    clip = np.zeros((n_m, 2), dtype=np.int32)
+    clipped = np.nonzero(rng.random(n_m) < frac_clip)[0]
+    for mm in clipped:  # only event-free mates are clipped (keeps MD/CIGAR trivially valid)
+        if ev_cnt[mm] == 0:
+            c = int(rng.integers(1, 12))
+            side = int(rng.integers(0, 2))
+            clip[mm, side] = c
+            if side == 0:
+                pos0[mm] += c
+            span[mm] -= c
+
+    return SynthSample(index=index, gene_cn=gene_cn, truth=truth, pair_gene=pair_gene,
+                       pair_nh=pair_nh, pair_secondary=np.zeros(n_pairs, dtype=bool),
+                       pair_qname=np.arange(n_pairs, dtype=np.int64),
+                       pos0=pos0, span=span, flag=flag, nm=nm, clip=clip, ev_off=ev_off,
+                       ev_pos=p.astype(np.int32), ev_kind=kk.astype(np.uint8),
+                       ev_val=v.astype(np.int32), ins_strings=ins_strings, read_len=read_len)
+
+
+def pack_sample(sample, gidx, threads: int = 1):
+    """``packed.packSample`` on ``threads`` slices of the sample's pairs at a time: a record depends on its own pair's
+    mates and events only, so the slices pack into their part of the same records, and the string table is interned
+    once, in the sample's order, before the slices start -- the same records and table as one call."""
+    import dataclasses
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    from kir_graph_amd import packed
+    n = sample.n_pairs
+    k = max(1, min(threads, n // 50_000))
+    if k == 1:
+        return packed.packSample(sample, gidx)
+    table = packed.InsTable(gidx)
+    for s in sample.ins_strings:
+        table.intern(s)
+    cut = np.linspace(0, n, k + 1).astype(np.int64)
+    rec = np.empty(2 * n, dtype=packed.MATE_DTYPE)
+
+    def one(i):
+        a, b = int(cut[i]), int(cut[i + 1])
+        e0, e1 = int(sample.ev_off[2 * a]), int(sample.ev_off[2 * b])
+        part = dataclasses.replace(
+            sample, pair_gene=sample.pair_gene[a:b], pair_nh=sample.pair_nh[a:b],
+            pair_secondary=sample.pair_secondary[a:b], pair_qname=sample.pair_qname[a:b],
+            pos0=sample.pos0[2 * a:2 * b], span=sample.span[2 * a:2 * b], flag=sample.flag[2 * a:2 * b],
+            nm=sample.nm[2 * a:2 * b], clip=sample.clip[2 * a:2 * b], ev_off=sample.ev_off[2 * a:2 * b + 1] - e0,
+            ev_pos=sample.ev_pos[e0:e1], ev_kind=sample.ev_kind[e0:e1], ev_val=sample.ev_val[e0:e1])
+        rec[2 * a:2 * b] = packed.packSample(part, gidx, table)[0]
+
+    with ThreadPoolExecutor(max_workers=k) as pool:
+        list(pool.map(one, range(k)))
+    return rec, table
 
 
 def build_inputs(seed: int, n_pairs: int, index_seed: int = 2022):
     """(index, packed index, sample, records, string table) of one synthetic sample (tests use this)."""
     t = time.time()
     sidx, gidx, by_gene = build_index(index_seed)
-    sample, rec, table = build_sample(sidx, gidx, by_gene, seed, n_pairs)
+    from kir_graph_amd.cohort import hostCoresPerRank
+    sample, rec, table = build_sample(sidx, gidx, by_gene, seed, n_pairs, threads=hostCoresPerRank())
     log(f"[bench] inputs: {len(gidx.variants)} variants, {sum(len(t.alleles) for t in gidx.tables)} alleles, "
         f"{n_pairs} pairs in {time.time() - t:.1f}s")
     return sidx, gidx, sample, rec, table
@@ -393,20 +673,23 @@ def configName(pairs: int) -> str:
     return "configs[1]" if pairs == 1_000_000 else "configs[2]" if pairs == 10_000_000 else "custom"
 
 
-def make_inputs(sidx, gidx, by_gene, rank: int, pairs: int, distinct: int, threads: int = 1):
+def make_inputs(sidx, gidx, by_gene, rank: int, pairs: int, distinct: int, threads: int = 1, cores: int = 1):
     """``distinct`` synthetic samples of ``pairs`` pairs as (pinned compact records, string table, copy numbers), seeds
     1031 + 7 rank + i.  ``threads`` > 1: that many samples are made at a time (numpy releases the interpreter lock in
-    its large operations; a 10 M-pair sample takes ~30 s and ~12 GB of host memory while it is made)."""
+    its large operations; a 10 M-pair sample takes ~12 GB of host memory while it is made), each packed on its share of
+    the rank's ``cores``."""
     from concurrent.futures import ThreadPoolExecutor
+    at_once = max(1, min(threads, distinct))
 
     def one(i):
-        sample, rec, table = build_sample(sidx, gidx, by_gene, 1031 + 7 * rank + i, pairs)
+        sample, rec, table = build_sample(sidx, gidx, by_gene, 1031 + 7 * rank + i, pairs,
+                                          threads=max(1, cores // at_once))
         pinned = PinnedRecords(rec)
         return pinned, table, sample.gene_cn
 
     t0 = time.time()
-    if threads > 1 and distinct > 1:
-        with ThreadPoolExecutor(max_workers=min(threads, distinct)) as pool:
+    if at_once > 1:
+        with ThreadPoolExecutor(max_workers=at_once) as pool:
             inputs = list(pool.map(one, range(distinct)))
     else:
         inputs = [one(i) for i in range(distinct)]
@@ -637,10 +920,12 @@ def report(rc: RankContext, res: dict, name: str, pinned, cores_before, head: bo
                                  "kernels": table}
         out["roofline"] = roofmodel.dominant(s_prof, serial["call_log"])
         out["roofline"]["step"] = roofmodel.stepRoofline(serial["call_log"], steps, ms_per_step)
-    else:
+    elif prof:
         out["roofline"] = roofmodel.dominant(prof, call_log)
         out["roofline"]["note_basis"] = "launch times taken inside the timed region (other samples share the GPU)"
-    out["roofline"]["traffic"], out["roofline"]["traffic_source"] = measured_traffic(out["roofline"].get("kernel"), pairs, method)
+    if "roofline" in out:      # neither a serial pass nor --verbose: no launch was timed, nothing to price
+        out["roofline"]["traffic"], out["roofline"]["traffic_source"] = measured_traffic(out["roofline"].get("kernel"),
+                                                                                         pairs, method)
     if prof:     # --verbose: launch times inside the timed region (kernels of the samples in flight overlap there)
         out["kernel_ms_per_step"] = {k: v[1] / opts.steps for k, v in prof.items()}
     out["search_steps"] = res.get("search_steps")    # steps bounded by integers / redone with f64 only (so far in this process)
@@ -736,27 +1021,38 @@ def main():
     ap.add_argument("--pairs", type=int, default=None,
                     help="read pairs per sample: 10000000 = configs[2], 1000000 = configs[1].  Given (or --method given): "
                          "that ONE workload.  Neither given: configs[2] with --allele-strategy exonfirst as the line's "
-                         "headline, and -- on one GPU -- `em` (configs[2]) and `configs1_pv` (configs[1]) as objects beside it")
+                         "headline, and -- with --full on one GPU -- `em` (configs[2]) and `configs1_pv` (configs[1]) as "
+                         "objects beside it")
     ap.add_argument("--method", default=None, help="--allele-strategy of the typing: pv, exonfirst, em")
     ap.add_argument("--distinct", type=int, default=None,
                     help="distinct samples a rank rotates through (default: 2 at configs[2] size, 8 below; a cohort types "
                          "every sample once: with N >= steps + warmup the first leg only meets samples nobody has typed before)")
-    ap.add_argument("--legs", type=int, default=3, help="timed legs per kind of input; the median leg is reported")
-    ap.add_argument("--cpu-pairs", type=int, default=20000, help="pairs for the CPU baseline sample (0 = skip)")
-    ap.add_argument("--serial-steps", type=int, default=2,
-                    help="steps of the one-process serial pass after the timed region (roofline basis; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: three timed legs per kind (median), both kinds of input, "
+                         "the `em` / `configs1_pv` workloads, the serial pass (kernels_serial, roofline), the command "
+                         "line's typing stage and the CPU baselines.  Without it: the headline workload, its warm-up, ONE "
+                         "timed leg of --steps steps and the line.  An option given explicitly holds either way")
+    ap.add_argument("--legs", type=int, default=None,
+                    help="timed legs per kind of input; the median leg is reported (default: 3 with --full, else 1)")
+    ap.add_argument("--cpu-pairs", type=int, default=None,
+                    help="pairs for the CPU baseline sample (0 = skip; default: 20000 with --full, else 0)")
+    ap.add_argument("--serial-steps", type=int, default=None,
+                    help="steps of the one-process serial pass after the timed region (roofline basis; 0 = skip; "
+                         "default: 2 with --full, else 0)")
     ap.add_argument("--inputs", choices=("host", "hbm"), default="host",
                     help="where a sample's records are when its step starts -- what `value` is measured on: pinned host "
                          "memory (the copy inside the step: SURVEY.md section 8(d), the metric), or resident in "
                          "HBM (a step = tabulation + typing + calls).  The other kind is timed too and reported beside it")
-    ap.add_argument("--one-kind", "--no-pcie-leg", dest="both_legs", action="store_false",
-                    help="time only the kind of leg --inputs names (no second object in the JSON line)")
-    ap.add_argument("--cli-samples", type=int, default=12,
+    ap.add_argument("--one-kind", "--no-pcie-leg", dest="both_legs", action="store_false", default=None,
+                    help="time only the kind of leg --inputs names (no second object in the JSON line; the default "
+                         "without --full)")
+    ap.add_argument("--cli-samples", type=int, default=None,
                     help="samples for the command line's typing stage (main.alleleTyping), timed after the legs as "
-                         "`cli_typing_stage` (rank 0 of the one-GPU run only; 0 = skip)")
+                         "`cli_typing_stage` (rank 0 of the one-GPU run only; 0 = skip; default: 12 with --full, else 0)")
     ap.add_argument("--pairs-scale", type=float, default=1.0, help=argparse.SUPPRESS)      # tests: the default workloads, smaller
-    ap.add_argument("--no-secondary", dest="secondary", action="store_false",
-                    help="the headline workload only (no `em` / `configs1_pv` objects)")
+    ap.add_argument("--no-secondary", dest="secondary", action="store_false", default=None,
+                    help="the headline workload only (no `em` / `configs1_pv` objects; the default without --full and "
+                         "--dump-outputs)")
     ap.add_argument("--synth-threads", type=int, default=0,
                     help="samples synthesised at a time (0: by the host cores and ranks of the node)")
     ap.add_argument("--cores-per-gpu", type=int, default=0,
@@ -766,8 +1062,16 @@ def main():
     ap.add_argument("--profile-host", action="store_true", help="cProfile one extra step to stderr")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step of each workload computed (rank 0) as "
-                         "DIR/<workload>_<array>.npy, float64; the inputs are seeded, so two builds compare file for file")
+                         "DIR/<workload>_<array>.npy, float64; the inputs are seeded, so two builds compare file for file.  "
+                         "Without --full the `em` / `configs1_pv` workloads then run for their outputs only (warm-up and "
+                         "one leg each, not reported)")
     args = ap.parse_args()
+    for key, full, lean in (("legs", 3, 1), ("cpu_pairs", 20000, 0), ("serial_steps", 2, 0), ("cli_samples", 12, 0),
+                            ("both_legs", True, False)):
+        if getattr(args, key) is None:
+            setattr(args, key, full if args.full else lean)
+    if args.secondary is None:
+        args.secondary = args.full or args.dump_outputs is not None
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args, sys.argv[1:])
@@ -793,19 +1097,23 @@ def main():
     if args.pairs is None and args.method is None:
         scale = args.pairs_scale      # tests: the three workloads at a fraction of their size
         names = ["configs2_exonfirst"] + (["em", "configs1_pv"] if args.secondary and world == 1 else [])
+        # without --full the other two run only for --dump-outputs: their objects stay out of the line
+        reported = names if args.full else names[:1]
         plan = [(name, max(1000, int(WORKLOADS[name][1] * scale)), WORKLOADS[name][2], WORKLOADS[name][3]) for name in names]
     else:
         pairs = 1_000_000 if args.pairs is None else args.pairs
         plan = [("custom", pairs, args.method or "pv", 2 if pairs >= 5_000_000 else N_DISTINCT)]
+        reported = ["custom"]
     rc = RankContext(args, rank, local_rank)
-    threads = args.synth_threads or max(1, min(4, cohort.hostCoresPerRank() // 3))
+    cores = cohort.hostCoresPerRank()
+    threads = args.synth_threads or max(1, min(4, cores // 3))
     results, by_size = [], {}
     from types import SimpleNamespace
     for k, (name, pairs, method, distinct) in enumerate(plan):
         distinct = max(1, min(args.distinct or distinct, args.steps + args.warmup))
         if (pairs, distinct) not in by_size:
             by_size.clear()                     # the samples of the workload before go (their pinned memory with them)
-            by_size[(pairs, distinct)] = make_inputs(rc.sidx, rc.gidx, rc.by_gene, rank, pairs, distinct, threads)
+            by_size[(pairs, distinct)] = make_inputs(rc.sidx, rc.gidx, rc.by_gene, rank, pairs, distinct, threads, cores)
         head = k == 0
         opts = SimpleNamespace(steps=args.steps, warmup=args.warmup, legs=args.legs if head else min(args.legs, 3),
                                inputs=args.inputs, both_legs=args.both_legs, serial_steps=args.serial_steps,
@@ -819,7 +1127,7 @@ def main():
         dump_outputs(args.dump_outputs, results)
     if rank == 0:
         out = None
-        for k, (name, res) in enumerate(results):
+        for k, (name, res) in enumerate(r for r in results if r[0] in reported):
             obj = report(rc, res, name, pinned, cores_before, head=(k == 0))
             if k == 0:
                 out = obj

@@ -1,7 +1,7 @@
 """bench.py run the way the driver runs it (a child process, small sample): the one JSON line and its contract -- the
-metric of BASELINE.json, whole-job throughput from records in pinned host memory, the legs from records
-resident in HBM beside it, the median of the timed legs, the roofline of the dominant kernel measured in the same run, the
-host budget, what the value table did -- and the multi-rank form on one GPU."""
+metric of BASELINE.json, whole-job throughput from records in pinned host memory; with --full the legs
+from records resident in HBM beside it, the median of the timed legs, the roofline of the dominant kernel measured in the
+same run, the host budget, what the value table did -- and the multi-rank form on one GPU."""
 import json
 import os
 import subprocess
@@ -23,7 +23,8 @@ def _run(args, env=None, timeout=600):
 
 
 def test_one_gpu_line_keeps_the_contract(device):
-    d = _run(["--gpus", "1", "--steps", "6", "--warmup", "2", "--pairs", "20000", "--cpu-pairs", "0", "--serial-steps", "1"])
+    d = _run(["--gpus", "1", "--steps", "6", "--warmup", "2", "--pairs", "20000", "--cpu-pairs", "0", "--serial-steps", "1",
+              "--full"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "host", "hbm_resident", "legs",
                 "value_table_new_per_sample", "samples_repeated_pass", "search_steps"):
@@ -63,7 +64,7 @@ def test_default_run_reports_the_three_workloads(device):
     own legs, serial kernel table, roofline and CPU baseline (here at 1 / 500 of the sizes: the structure, not the
     numbers; the names of the kernels are their own, so the EM kernels and the set sums show under them)."""
     d = _run(["--steps", "3", "--warmup", "1", "--cpu-pairs", "5000", "--serial-steps", "1", "--legs", "1", "--cli-samples", "0",
-              "--pairs-scale", "0.002"], timeout=900)
+              "--pairs-scale", "0.002", "--full"], timeout=900)
     assert d["config"]["allele_strategy"] == "exonfirst" and d["config"]["pairs_per_sample"] == 20000
     assert d["n_gpus"] == 1 and d["value"] > 0 and "cpu_baseline" in d and d["cpu_baseline"]["kind"] == "port"
     for name, method, pairs in (("em", "em", 20000), ("configs1_pv", "pv", 2000)):
@@ -77,6 +78,22 @@ def test_default_run_reports_the_three_workloads(device):
     assert "compat_kernel" in d["kernels_serial"]["kernels"] and "compat_kernel" not in em_kernels
     # kernels are timed under their own names: no collective labels left
     assert not {"select_cut", "select", "scan", "count_ids"} & set(d["kernels_serial"]["kernels"])
+
+
+def test_plain_run_is_the_headline_alone(device):
+    """Without --full: the headline workload, its warm-up and ONE timed leg of --steps steps -- no second kind of leg, no
+    other workload, serial pass, typing stage of the command line or CPU baseline -- and the contract's keys as ever."""
+    d = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs-scale", "0.002"])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config", "host", "legs"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["config"]["allele_strategy"] == "exonfirst" and d["config"]["pairs_per_sample"] == 20000
+    assert len(d["legs"]) == 1 and d["legs"][0]["ms_per_step"] == pytest.approx(d["ms_per_step"])
+    assert abs(d["value"] - 2 * 20000 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-9
+    for key in ("em", "configs1_pv", "hbm_resident", "pcie_inclusive", "kernels_serial", "roofline", "cli_typing_stage",
+                "cpu_baseline"):
+        assert key not in d, key
 
 
 def test_dumped_outputs_are_the_same_from_run_to_run(device, tmp_path):

@@ -9,8 +9,8 @@
 #   2. --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes: HBM bytes per launch (tools/pmc_traffic.py; FETCH_SIZE
 #      counts half of coalesced reads on gfx950 -- the guide's correction);
 #   3. two passes of SQ counters (issue / wait / LDS), summarised per kernel (tools/pmc_summary.py).
-# Then the driver's own command, AFTER the traffic files of this code are in place (bench.py only reports a traffic
-# figure whose recorded source digest is the running code's).
+# Then the full benchmark (bench.py --full: roofline, traffic, CPU baselines), AFTER the traffic files of this code are
+# in place (bench.py only reports a traffic figure whose recorded source digest is the running code's).
 set -e
 R=$GRAFT_REPO_ROOT
 TAG=${1:-r05}
@@ -55,7 +55,7 @@ done
 unset GK_PREFETCH GK_SAMPLE_LANES      # the serial mode was for the profiler only
 if [ "$RUN_BENCH" = "1" ]; then
   cd $R
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
   echo "[collect] bench done"
   tail -c 1500 $O/bench.json
 fi
