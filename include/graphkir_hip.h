@@ -320,6 +320,13 @@ int gk_compat_log_miss(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows,
                        int32_t vbeg, int32_t vend, gk_dptr d_mask, int32_t words, int32_t n_allele,
                        int32_t keep_empty, gk_lut* lut, gk_dptr d_log, gk_dptr d_miss8, int64_t ldm, gk_dptr d_flags);
 int gk_miss_colsum(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int32_t n_cols, gk_dptr d_msum);
+/* gk_compat_log_miss for a list of the gene's alleles (typing_mulit_allele.py:506-520, 740-746: the candidate columns of
+ * exon-first): table_cols = n_table_cols allele ordinals (host), ascending and unique; d_log is [n_table_cols][n_rows],
+ * d_miss8 [n_table_cols][ldm], column c = allele table_cols[c], bit-identical to that column of the whole table. */
+int gk_compat_log_miss_cols(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag,
+                            int32_t vbeg, int32_t vend, gk_dptr d_mask, int32_t words, int32_t n_allele,
+                            int32_t keep_empty, gk_lut* lut, const int32_t* table_cols, int32_t n_table_cols,
+                            gk_dptr d_log, gk_dptr d_miss8, int64_t ldm, gk_dptr d_flags);
 /* Bits 2 and 3 of *d_flags after gk_compat_log_miss: bit 2 = some product had no log10 in the value table yet; its entry
  * of d_log holds the PRODUCT itself (strictly positive, which no log10 of a probability is) until gk_compat_patch, after
  * the table has been resolved (gk_lut_resolve*), puts the log10 and the mismatch byte there -- one pass over this gene's
@@ -392,6 +399,14 @@ typedef struct gk_gene_job {
   int32_t table_of, n_step_cols;
   const int32_t* step_cols;
   const int32_t* step_cols_off;
+  /* n_table_cols > 0 (a job that writes its own table, pipelined form): the tables hold the listed alleles only --
+   * table_cols = host array of allele ordinals, ascending and unique; d_L is [n_table_cols][n_rows], d_miss8
+   * [n_table_cols][ldm], d_msum [n_table_cols], column c = allele table_cols[c] -- with the same bits in those columns
+   * as the whole table has (an entry depends on its read and its allele only).  The searches on the table (this job's
+   * own steps, the jobs with table_of) still name alleles by ORDINAL in step_cols and get ordinals back; an ordinal
+   * that is not listed is GK_ERR_ARG.  0: every allele. */
+  const int32_t* table_cols;
+  int32_t n_table_cols;
 } gk_gene_job;
 int gk_sample_search(gk_ctx* ctx, gk_ctx** more_ctx, int32_t n_more, gk_tab* tab, gk_dptr d_vflag, gk_lut* lut,
                      gk_gene_job* jobs, int32_t n_jobs, gk_argsort_fn argsort, gk_log10_fn log10_fn, gk_search** out);
@@ -404,6 +419,8 @@ int gk_search_copy(gk_search* s, int32_t step, double* value, double* sum_indv, 
  * [cells] hold the rows of the steps back to back in (search, step) order (gk_search_copy's columns) */
 int gk_search_export(gk_search* const* s, int32_t n, int64_t* totals, int64_t* meta, double* value, double* sum_indv,
                      double* frac, int32_t* ids);
+/* out [n_allele] = column sums of the search's table; for a table of listed alleles (table_cols) the listed entries are
+ * filled and every other entry is NaN */
 int gk_search_colsum(gk_search* s, double* out);
 /* launch geometries of the run, 7 int64 per device call: kind (0 gk_maxsum, 1 gk_bound_step, 2 gk_setsum /
  * gk_fraction) and the arguments of the roofline model (kir_graph_amd/roofmodel.py) */

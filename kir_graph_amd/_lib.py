@@ -58,6 +58,7 @@ class GeneJob(C.Structure):
         ("n_steps", C.c_int32), ("top_n", C.c_int32), ("bound_ok", C.c_int32), ("passes", C.c_int32),
         ("indexed", C.c_int32), ("patches", C.c_int32),
         ("table_of", C.c_int32), ("n_step_cols", C.c_int32), ("step_cols", C.c_void_p), ("step_cols_off", C.c_void_p),
+        ("table_cols", C.c_void_p), ("n_table_cols", C.c_int32),
     ]
 
 
@@ -191,6 +192,9 @@ _SIGS = {
                              C.c_int32, C.c_uint64]),
     "gk_em_distinct": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int32)]),
+    "gk_compat_log_miss_cols": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_int32, C.c_int32,
+                                          C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.c_uint64, C.c_uint64, C.c_int64, C.c_uint64]),
     "gk_compat_log_miss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_int32, C.c_int32,
                                      C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64,
                                      C.c_int64, C.c_uint64]),

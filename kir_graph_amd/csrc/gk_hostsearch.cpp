@@ -180,6 +180,10 @@ double unevenness(const double* f, int c) {
 
 struct gk_search {
   int n_allele = 0;
+  // a search on a table of LISTED alleles (gk_gene_job.table_cols) runs on column numbers: colsum is per column, and the
+  // ids of its steps are translated to allele ordinals once, when the search leaves the library (to_alleles)
+  std::vector<int32_t> table_cols;
+  int n_full = 0;               // alleles of the gene (with table_cols)
   std::vector<double> colsum;
   std::vector<Step> steps;
   // launch geometries for the roofline accounting (kir_graph_amd/roofmodel.py): 7 numbers per device call --
@@ -196,6 +200,12 @@ struct gk_search {
     const int64_t row[7] = {kind, a, b, c, d, e, f};
     log.insert(log.end(), row, row + 7);
   }
+  void to_alleles(const int32_t* cols, int n_cols, int n_alleles) {
+    for (Step& st : steps)
+      for (int32_t& id : st.ids) id = cols[id];
+    table_cols.assign(cols, cols + n_cols);
+    n_full = n_alleles;
+  }
 };
 
 extern "C" {
@@ -210,6 +220,13 @@ int gk_compat_log_miss(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows,
 int gk_compat_log(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag, int32_t vbeg,
                   int32_t vend, gk_dptr d_mask, int32_t words, int32_t n_allele, int32_t keep_empty, gk_lut* lut,
                   gk_dptr d_log);
+// weak: the host-only builds of this file (tests/asan) link stand-ins for the device entry points and have none for this
+// one; a job with a column list is refused there (gk_sample_search)
+__attribute__((weak)) int gk_compat_log_miss_cols(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag,
+                                                  int32_t vbeg, int32_t vend, gk_dptr d_mask, int32_t words, int32_t n_allele,
+                                                  int32_t keep_empty, gk_lut* lut, const int32_t* table_cols,
+                                                  int32_t n_table_cols, gk_dptr d_log, gk_dptr d_miss8, int64_t ldm,
+                                                  gk_dptr d_flags);
 int gk_miss_colsum(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int32_t n_cols, gk_dptr d_msum);
 int gk_compat_patch(gk_ctx* ctx, gk_lut* lut, gk_dptr d_log, int64_t n_rows, int32_t n_allele, gk_dptr d_miss8, int64_t ldm,
                     gk_dptr d_flags);
@@ -863,28 +880,51 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
   // gene i's table, mismatch sums, flag word and column sums (right behind the kernel that wrote the table: it is still
   // in the Infinity Cache), then a mark
   std::vector<uint32_t> sticky((size_t)n_jobs, 0);      // bit 0 of a gene's flag word survives its patches
+  // A job with a column list (table_cols) writes the tables of those alleles only: everything below works on its
+  // n_table_cols COLUMNS -- the kernels, the column sums, the searches on the table -- and allele ordinals are turned
+  // into column numbers on their way in (col_of) and back when a search leaves the call (gk_search::to_alleles).  The
+  // list is ascending, so every order among ids (ties of a sort, first occurrences) is the same in both numberings.
+  auto n_cols_of = [&](int i) { return jobs[i].n_table_cols > 0 ? jobs[i].n_table_cols : jobs[i].n_allele; };
+  auto col_of = [&](int owner, int32_t a, int32_t* col) -> int {
+    const gk_gene_job& o = jobs[owner];
+    if (a < 0 || a >= o.n_allele) { gk_set_error("candidate allele out of range"); return GK_ERR_ARG; }
+    if (o.n_table_cols <= 0) { *col = a; return GK_OK; }
+    const int32_t* const end = o.table_cols + o.n_table_cols;
+    const int32_t* const at = std::lower_bound(o.table_cols, end, a);
+    if (at == end || *at != a) {
+      gk_set_error("candidate allele %d is not among the columns of its table", (int)a);
+      return GK_ERR_ARG;
+    }
+    *col = (int32_t)(at - o.table_cols);
+    return GK_OK;
+  };
   auto write_table = [&](int i, bool patch) -> int {
     gk_gene_job& j = jobs[i];
+    const int nc = n_cols_of(i);
     int rc;
     if (patch) {      // only the entries that hold their product are touched (gk_compat_patch)
       j.patches++;
       sticky[i] |= flags[i] & 1u;
-      rc = gk_compat_patch(ctx, lut, j.d_L, j.n_rows, j.n_allele, j.d_miss8, j.ldm, j.d_flags);
+      rc = gk_compat_patch(ctx, lut, j.d_L, j.n_rows, nc, j.d_miss8, j.ldm, j.d_flags);
     } else {
       j.passes++;
       sticky[i] = 0;
-      rc = gk_compat_log_miss(ctx, tab, j.d_rows, j.n_rows, d_vflag, j.vbeg, j.vend, j.d_mask, j.words, j.n_allele, 0, lut,
-                              j.d_L, j.d_miss8, j.ldm, j.d_flags);
+      if (j.n_table_cols > 0)
+        rc = gk_compat_log_miss_cols(ctx, tab, j.d_rows, j.n_rows, d_vflag, j.vbeg, j.vend, j.d_mask, j.words, j.n_allele, 0,
+                                     lut, j.table_cols, j.n_table_cols, j.d_L, j.d_miss8, j.ldm, j.d_flags);
+      else
+        rc = gk_compat_log_miss(ctx, tab, j.d_rows, j.n_rows, d_vflag, j.vbeg, j.vend, j.d_mask, j.words, j.n_allele, 0, lut,
+                                j.d_L, j.d_miss8, j.ldm, j.d_flags);
     }
-    if (rc == GK_OK) rc = gk_miss_colsum(ctx, j.d_miss8, j.ldm, j.n_allele, j.d_msum);
+    if (rc == GK_OK) rc = gk_miss_colsum(ctx, j.d_miss8, j.ldm, nc, j.d_msum);
     if (rc == GK_OK && gk_fetch_queue(ctx, &flags[i], gk_ptr<void>(j.d_flags), sizeof(uint32_t)) != hipSuccess) rc = GK_ERR_HIP;
     if (rc) return rc;
-    std::vector<int32_t> cols((size_t)j.n_allele);
+    std::vector<int32_t> cols((size_t)nc);
     std::iota(cols.begin(), cols.end(), 0);
     if (gs[i]) gs[i]->abandon();                 // the pass before this one: its column sums are void
     gs[i].reset(new GeneSearch());
-    rc = gs[i]->init(ctx, GkTable{j.d_L, j.n_rows, nullptr}, j.d_L, j.n_rows, j.n_rows, j.n_allele, j.d_miss8, j.ldm, j.d_msum,
-                     cols.data(), j.n_allele, j.n_steps, j.top_n, argsort);
+    rc = gs[i]->init(ctx, GkTable{j.d_L, j.n_rows, nullptr}, j.d_L, j.n_rows, j.n_rows, nc, j.d_miss8, j.ldm, j.d_msum,
+                     cols.data(), nc, j.n_steps, j.top_n, argsort);
     if (rc == GK_OK) rc = gs[i]->colsum_enqueue();
     if (rc == GK_OK) rc = push(i, kTable);
     return rc;
@@ -953,6 +993,7 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
           rc = g.first_step();
           if (rc == GK_OK) rc = advance(it.gene, true);
         }
+        const int nc = n_cols_of(it.gene);               // columns of this gene's table
         std::vector<int> one_set;                        // the dependents whose steps offer one allele each
         for (int d : dependents[(size_t)it.gene]) {      // the table is final: the searches that read it begin
           if (rc) break;
@@ -963,10 +1004,11 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
           if (single) {
             gs[d].reset(new GeneSearch());
             gs[d]->S.reset(new gk_search());
-            gs[d]->S->n_allele = j.n_allele;
+            gs[d]->S->n_allele = nc;
             gs[d]->S->colsum = g.S->colsum;
-            const int32_t a0 = jd.step_cols[jd.step_cols_off[0]];
-            if (a0 < 0 || a0 >= j.n_allele) { gk_set_error("candidate allele out of range"); rc = GK_ERR_ARG; break; }
+            int32_t a0 = 0;
+            rc = col_of(it.gene, jd.step_cols[jd.step_cols_off[0]], &a0);
+            if (rc) break;
             Step s1;
             s1.n = 1;
             s1.value.push_back(g.S->colsum[(size_t)a0]);
@@ -978,17 +1020,21 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
             continue;
           }
           gs[d].reset(new GeneSearch());
-          std::vector<int32_t> every((size_t)j.n_allele);
+          std::vector<int32_t> every((size_t)nc);
           std::iota(every.begin(), every.end(), 0);
-          rc = gs[d]->init(ctx, GkTable{j.d_L, j.n_rows, nullptr}, j.d_L, j.n_rows, j.n_rows, j.n_allele, j.d_miss8, j.ldm, j.d_msum,
-                           every.data(), j.n_allele, jd.n_steps, jd.top_n, argsort);
+          rc = gs[d]->init(ctx, GkTable{j.d_L, j.n_rows, nullptr}, j.d_L, j.n_rows, j.n_rows, nc, j.d_miss8, j.ldm, j.d_msum,
+                           every.data(), nc, jd.n_steps, jd.top_n, argsort);
           if (rc) break;
           if (!j.bound_ok) gs[d]->bound = false;
           gs[d]->S->colsum = g.S->colsum;
           if (jd.n_step_cols > 0) {
             gs[d]->step_cols.resize((size_t)jd.n_step_cols);
-            for (int q = 0; q < jd.n_step_cols; ++q)
-              gs[d]->step_cols[(size_t)q].assign(jd.step_cols + jd.step_cols_off[q], jd.step_cols + jd.step_cols_off[q + 1]);
+            for (int q = 0; q < jd.n_step_cols && rc == GK_OK; ++q) {
+              std::vector<int32_t>& sc = gs[d]->step_cols[(size_t)q];
+              sc.assign(jd.step_cols + jd.step_cols_off[q], jd.step_cols + jd.step_cols_off[q + 1]);
+              for (int32_t& a : sc) { rc = col_of(it.gene, a, &a); if (rc) break; }
+            }
+            if (rc) break;
           }
           if (jd.n_steps > 0) {
             rc = gs[d]->first_step();
@@ -1001,8 +1047,9 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
           for (int d : one_set) {
             if (jobs[d].n_steps < k) continue;
             for (int q = 0; q < k; ++q) {
-              const int32_t a = jobs[d].step_cols[jobs[d].step_cols_off[q]];
-              if (a < 0 || a >= j.n_allele) { gk_set_error("candidate allele out of range"); rc = GK_ERR_ARG; }
+              int32_t a = 0;
+              const int r = col_of(it.gene, jobs[d].step_cols[jobs[d].step_cols_off[q]], &a);
+              if (r) rc = r;
               b->ids.push_back(a);
             }
             b->deps.push_back(d);
@@ -1052,6 +1099,8 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
   }
   for (int i : live) {
     gs[i]->finish();
+    const gk_gene_job& o = jobs[jobs[i].table_of >= 0 ? jobs[i].table_of : i];
+    if (o.n_table_cols > 0) gs[i]->S->to_alleles(o.table_cols, o.n_table_cols, o.n_allele);
     out[i] = gs[i]->S.release();
   }
   clock.lap(false);
@@ -1082,7 +1131,7 @@ int gk_sample_search(gk_ctx* ctx, gk_ctx** more_ctx, int32_t n_more, gk_tab* tab
   }
   for (int i = 0; i < n_jobs; ++i) out[i] = nullptr;
   std::vector<int> live;
-  bool any_special = false;      // table-only jobs, searches on another job's table, columns per step: pipelined form only
+  bool any_special = false;      // table-only jobs, searches on another job's table, columns per step or per table: pipelined form only
   for (int i = 0; i < n_jobs; ++i) {
     gk_gene_job& j = jobs[i];
     j.bound_ok = 0;
@@ -1092,14 +1141,20 @@ int gk_sample_search(gk_ctx* ctx, gk_ctx** more_ctx, int32_t n_more, gk_tab* tab
     GK_REQUIRE(j.n_rows >= 0 && j.n_allele >= 0 && j.n_steps >= 0 && j.top_n >= 1, "bad gene job");
     GK_REQUIRE(j.table_of >= -1 && j.table_of < n_jobs && j.table_of != i, "bad table reference");
     GK_REQUIRE(j.n_step_cols >= 0 && (j.n_step_cols == 0 || (j.step_cols && j.step_cols_off)), "bad step columns");
+    GK_REQUIRE(j.n_table_cols >= 0 && j.n_table_cols <= j.n_allele && (j.n_table_cols == 0 || j.table_cols), "bad table columns");
+    GK_REQUIRE(j.n_table_cols == 0 || gk_compat_log_miss_cols, "column lists need the device build");
+    for (int c = 0; c < j.n_table_cols; ++c)
+      GK_REQUIRE(j.table_cols[c] >= 0 && j.table_cols[c] < j.n_allele && (c == 0 || j.table_cols[c] > j.table_cols[c - 1]),
+                 "table columns must be allele ordinals, ascending and unique");
     if (j.table_of >= 0) {       // a search on another job's table: that job writes it
       const gk_gene_job& o = jobs[j.table_of];
       GK_REQUIRE(o.table_of < 0, "a table reference must name a job that writes its own table");
       GK_REQUIRE(j.n_steps >= 1, "a search on another job's table needs steps");
+      GK_REQUIRE(j.n_table_cols == 0, "a column list belongs to the job that writes the table");
       if (o.n_rows > 0 && o.n_allele > 0) { live.push_back(i); any_special = true; }
       continue;
     }
-    if (j.n_steps == 0 || j.n_step_cols > 0) any_special = true;
+    if (j.n_steps == 0 || j.n_step_cols > 0 || j.n_table_cols > 0) any_special = true;
     if (j.n_rows > 0 && j.n_allele > 0) {
       GK_REQUIRE(j.d_rows && (j.d_L || j.d_lidx) && j.d_mask && j.words >= 1, "gene job without tables");
       GK_REQUIRE(!j.d_miss8 || (j.d_msum && j.d_flags && j.ldm >= j.n_rows && j.ldm % 64 == 0), "bad mismatch table");
@@ -1114,7 +1169,7 @@ int gk_sample_search(gk_ctx* ctx, gk_ctx** more_ctx, int32_t n_more, gk_tab* tab
   for (int i : live) if (jobs[i].table_of < 0) flagged = flagged && jobs[i].d_miss8 && jobs[i].d_flags;
   if (n_more == 0 && float_tables && flagged)
     return sample_search_pipelined(ctx, tab, d_vflag, lut, jobs, n_jobs, live, argsort, log10_fn, out);
-  GK_REQUIRE(!any_special, "table-only jobs, searches on another job's table and per-step columns need float64 tables "
+  GK_REQUIRE(!any_special, "table-only jobs, searches on another job's table, per-step columns and column lists need float64 tables "
                            "with mismatch tables on one stream (the pipelined form)");
   return sample_search_lockstep(ctx, cx, tab, d_vflag, lut, jobs, n_jobs, live, argsort, log10_fn, out);
 }
@@ -1175,7 +1230,13 @@ int gk_search_export(gk_search* const* s, int32_t n, int64_t* totals, int64_t* m
 
 int gk_search_colsum(gk_search* s, double* out) {
   GK_REQUIRE(s && out, "null pointer");
-  std::copy(s->colsum.begin(), s->colsum.end(), out);
+  if (s->table_cols.empty()) {
+    std::copy(s->colsum.begin(), s->colsum.end(), out);
+    return GK_OK;
+  }
+  // a table of listed alleles: their sums at their ordinals, NaN for the alleles the table does not hold
+  std::fill(out, out + s->n_full, std::nan(""));
+  for (size_t c = 0; c < s->table_cols.size(); ++c) out[s->table_cols[c]] = s->colsum[c];
   return GK_OK;
 }
 

@@ -288,6 +288,28 @@ __global__ __launch_bounds__(kThreads) void transpose_mask(const uint32_t* mask,
   out[i] = mask[(int64_t)v * words + w];
 }
 
+// The same for a table over a LIST of the gene's alleles (exon-first: the full-model table of the candidate alleles only):
+// the listed columns' bits are gathered while the matrix is transposed -- output word w, bit b of variant v = bit
+// cols[32 w + b] of the input row (zero past the end of the list) -- so that the compatibility kernel runs unchanged on
+// n_cols alleles in words_out = ceil(n_cols / 32) words.  cols[] are allele ordinals < 32 * words.
+__global__ __launch_bounds__(kThreads) void transpose_gather_mask(const uint32_t* __restrict__ mask, int n_span, int words,
+                                                                  const int32_t* __restrict__ cols, int n_cols,
+                                                                  int words_out, uint32_t* __restrict__ out,
+                                                                  uint32_t* zero_word) {
+  if (zero_word && blockIdx.x == 0 && threadIdx.x == 0) *zero_word = 0;   // the flag word of the launches that follow
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= (int64_t)n_span * words_out) return;
+  const int w = (int)(i / n_span), v = (int)(i % n_span);
+  const uint32_t* const row = mask + (int64_t)v * words;
+  const int n_bits = min(32, n_cols - 32 * w);
+  uint32_t x = 0;
+  for (int b = 0; b < n_bits; ++b) {
+    const int a = cols[32 * w + b];
+    x |= ((row[a >> 5] >> (a & 31)) & 1u) << b;
+  }
+  out[i] = x;
+}
+
 // One wavefront per read pair, lanes = alleles (kSlots allele slots per lane; a gene of <= 256
 // alleles is one pass, and the last pass of a wider gene only carries the slots it needs).  Per chunk
 // of 64 variant ordinals, lane k loads ordinal k, its drop flag and the 2*kSlots bit-row words of
@@ -643,19 +665,39 @@ __global__ __launch_bounds__(kThreads) void patch_pending(double* __restrict__ L
   }
 }
 
+// table_cols (host, n_table_cols > 0): the tables hold these alleles of the gene only, column c = allele table_cols[c]
 template <bool kLog>
 int launch_compat(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag, int vbeg, int vend,
                   gk_dptr d_mask, int words, int n_allele, double* out, uint8_t* miss, uint16_t* nvar, LutView view,
                   int keep_empty, uint8_t* miss8 = nullptr, int64_t ldm = 0, uint32_t* bound_flags = nullptr,
-                  uint16_t* lidx = nullptr) {
+                  uint16_t* lidx = nullptr, const int32_t* table_cols = nullptr, int n_table_cols = 0) {
   const double empty_p = keep_empty ? 0.999 : 1.0;
+  const int words_in = words;
+  int32_t* d_cols = nullptr;
+  if (n_table_cols > 0) {      // the kernel sees a gene of the listed alleles
+    n_allele = n_table_cols;
+    words = (n_table_cols + 31) / 32;
+    GK_HIP(gk_pool_malloc(ctx, (void**)&d_cols, (size_t)n_table_cols * sizeof(int32_t)));
+    if (gk_send(ctx, d_cols, table_cols, (size_t)n_table_cols * sizeof(int32_t)) != hipSuccess) {
+      gk_pool_free(ctx, d_cols);
+      gk_set_error("compatibility table: sending the column list failed: %s", hipGetErrorString(hipGetLastError()));
+      return GK_ERR_HIP;
+    }
+  }
   int64_t want = ((n_rows + kTileRows - 1) / kTileRows + 7) / 8 * 8;      // a multiple of 8: see the tile order in the kernel
   const dim3 grid((unsigned)(want < 2048 ? (want < 8 ? 8 : want) : 2048)), block(kCompatThreads);
   const int64_t n_mask = (int64_t)(vend - vbeg) * words;
   uint32_t* mask_t = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&mask_t, (size_t)std::max<int64_t>(n_mask, 1) * sizeof(uint32_t)));
+  if (gk_pool_malloc(ctx, (void**)&mask_t, (size_t)std::max<int64_t>(n_mask, 1) * sizeof(uint32_t)) != hipSuccess) {
+    gk_pool_free(ctx, d_cols);
+    gk_set_error("out of device memory for the transposed bit matrix");
+    return GK_ERR_HIP;
+  }
   // the flag word starts at zero: cleared by the transposition when there is one (a fill of its own otherwise)
-  if (n_mask > 0)
+  if (n_mask > 0 && d_cols)
+    GK_KERNEL(transpose_gather_mask, dim3((unsigned)((n_mask + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream,
+              gk_ptr<uint32_t>(d_mask), vend - vbeg, words_in, d_cols, n_table_cols, words, mask_t, bound_flags);
+  else if (n_mask > 0)
     GK_KERNEL(transpose_mask, dim3((unsigned)((n_mask + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream,
               gk_ptr<uint32_t>(d_mask), vend - vbeg, words, mask_t, bound_flags);
   else if (bound_flags)
@@ -681,6 +723,7 @@ int launch_compat(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_d
 #undef GK_COMPAT_GO
   }
   gk_pool_free(ctx, mask_t);   // stream-ordered reuse: the next user of the block runs after these launches
+  gk_pool_free(ctx, d_cols);
   GK_HIP(hipGetLastError());
   return GK_OK;
 }
@@ -1125,6 +1168,29 @@ int gk_compat_log_miss(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows,
   return launch_compat<true>(ctx, tab, d_rows, n_rows, d_vflag, vbeg, vend, d_mask, words, n_allele,
                              gk_ptr<double>(d_log), nullptr, nullptr, gk_lut_view(lut), keep_empty,
                              gk_ptr<uint8_t>(d_miss8), ldm, gk_ptr<uint32_t>(d_flags));
+}
+
+/* gk_compat_log_miss for a LIST of the gene's alleles (exon-first: the candidates' columns of the full model,
+ * typing_mulit_allele.py:506-520, 740-746): table_cols = n_table_cols allele ordinals (host), ascending and unique; d_log
+ * is [n_table_cols][n_rows], d_miss8 [n_table_cols][ldm], column c = allele table_cols[c].  An entry depends on its read
+ * and its allele only, so the columns hold the bits the whole table holds in them. */
+int gk_compat_log_miss_cols(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag, int32_t vbeg,
+                            int32_t vend, gk_dptr d_mask, int32_t words, int32_t n_allele, int32_t keep_empty, gk_lut* lut,
+                            const int32_t* table_cols, int32_t n_table_cols, gk_dptr d_log, gk_dptr d_miss8, int64_t ldm,
+                            gk_dptr d_flags) {
+  gk_bind(ctx);
+  GK_REQUIRE(ctx && tab && lut, "null pointer");
+  GK_REQUIRE(words >= 1 && n_allele >= 0 && n_allele <= words * 32 && vend >= vbeg, "bad mask geometry");
+  GK_REQUIRE(table_cols && n_table_cols >= 1 && n_table_cols <= n_allele, "bad column list");
+  for (int c = 0; c < n_table_cols; ++c)
+    GK_REQUIRE(table_cols[c] >= 0 && table_cols[c] < n_allele && (c == 0 || table_cols[c] > table_cols[c - 1]),
+               "table columns must be allele ordinals, ascending and unique");
+  if (n_rows == 0) return GK_OK;
+  GK_REQUIRE(d_log && d_miss8 && d_flags, "null output");
+  GK_REQUIRE(ldm >= n_rows && ldm % 64 == 0, "mismatch table stride must be a multiple of 64 rows");
+  return launch_compat<true>(ctx, tab, d_rows, n_rows, d_vflag, vbeg, vend, d_mask, words, n_allele,
+                             gk_ptr<double>(d_log), nullptr, nullptr, gk_lut_view(lut), keep_empty,
+                             gk_ptr<uint8_t>(d_miss8), ldm, gk_ptr<uint32_t>(d_flags), nullptr, table_cols, n_table_cols);
 }
 
 /* After gk_compat_log_miss raised bit 2 of *d_flags (and not bit 3) and the value table has been resolved: the entries

@@ -444,13 +444,19 @@ class DeviceModel:
 
     def __init__(self, tab: Tabulation, rows: DeviceBuffer, n_rows: int, vflag: DeviceBuffer,
                  vbeg: int, vend: int, mask: DeviceBuffer, words: int, n_allele: int, logs: LogTable,
-                 want_miss: bool = False, keep_empty: bool = False, launch: bool = True, indexed: bool = False):
+                 want_miss: bool = False, keep_empty: bool = False, launch: bool = True, indexed: bool = False,
+                 table_cols: np.ndarray | None = None):
         """``keep_empty``: rows without any kept variant are part of the model and score 0.999 for every
         allele (``no_empty=False``, typing_mulit_allele.py:372-374).  ``launch=False``: the tables are only
         allocated; ``gk_sample_search`` fills them together with those of the sample's other genes.
         ``indexed`` (with ``launch=False`` and the integer bound): the table is kept as uint16 indices into the value
-        table (2 bytes per entry, ``lidx``); the float64 form ``L`` is made from it only when somebody reads it."""
+        table (2 bytes per entry, ``lidx``); the float64 form ``L`` is made from it only when somebody reads it.
+        ``table_cols`` (with ``launch=False``): the tables are allocated for these alleles only (ascending ordinals; column
+        c = allele ``table_cols[c]``) and ``gk_sample_search`` fills and searches them as such (exon-first: the candidates'
+        columns).  Whoever then reads ``L`` or the mismatch table by allele ordinal gets the all-allele tables, written on
+        that first read (``_allColumns``)."""
         self.tab, self.dev = tab, tab.dev
+        self._table_cols = None
         self._keep_empty = int(bool(keep_empty))
         self.rows, self.n_rows, self.n_allele = rows, n_rows, n_allele
         self.vflag = vflag
@@ -469,23 +475,44 @@ class DeviceModel:
         if n_rows == 0 or n_allele == 0:
             return
         want_index = bool(indexed and not launch and searchMode() == "bound" and n_rows < 16_000_000)
-        if not want_index:
-            self._L = self.dev.alloc((n_allele, n_rows), np.float64)
-        if searchMode() == "bound" and n_rows < 16_000_000:
-            self.ldm = (n_rows + 63) // 64 * 64
-            self.miss8 = self.dev.alloc((n_allele, self.ldm), np.uint8)
-            self.msum = self.dev.alloc(n_allele, np.uint32)
-            self._bound_flags = self.dev.alloc(1, np.uint32)
-            if want_index:
-                self.lidx = self.dev.alloc((n_allele, self.ldm), np.uint16)
+        if table_cols is not None and not launch and not want_index and searchMode() == "bound" and n_rows < 16_000_000:
+            self._table_cols = np.ascontiguousarray(table_cols, dtype=np.int32)
+        self._allocTables(len(self._table_cols) if self._table_cols is not None else n_allele, want_index)
         if launch:
             self._launchLog()
         if want_miss:
             self._launchProbs()
 
+    def _allocTables(self, n_cols: int, want_index: bool = False) -> None:
+        n_rows = self.n_rows
+        if not want_index:
+            self._L = self.dev.alloc((n_cols, n_rows), np.float64)
+        if searchMode() == "bound" and n_rows < 16_000_000:
+            self.ldm = (n_rows + 63) // 64 * 64
+            self.miss8 = self.dev.alloc((n_cols, self.ldm), np.uint8)
+            self.msum = self.dev.alloc(n_cols, np.uint32)
+            self._bound_flags = self.dev.alloc(1, np.uint32)
+            if want_index:
+                self.lidx = self.dev.alloc((n_cols, self.ldm), np.uint16)
+
+    def _allColumns(self) -> None:
+        """A model whose tables hold a list of alleles gets the tables of every allele (fresh allocations, written here):
+        the reductions below and ``log_probs`` address columns by allele ordinal."""
+        if self._table_cols is None:
+            return
+        self._table_cols = None
+        for b in (self._L, self.miss8, self.msum, self._bound_flags):
+            if b is not None:
+                b.free()
+        self._L = self.miss8 = self.msum = self._bound_flags = None
+        self._allocTables(self.n_allele)
+        self._launchLog()
+        self.finishLog()
+
     @property
     def L(self) -> DeviceBuffer | None:
         """The float64 table [allele][read]; made from the index form on first use when that is what the model holds."""
+        self._allColumns()
         if self._L is None and self.lidx is not None:
             if self._indexed:
                 self._L = self.dev.alloc((self.n_allele, self.n_rows), np.float64)
@@ -569,6 +596,7 @@ class DeviceModel:
     @property
     def boundOk(self) -> bool:
         """The mismatch table exists and no count came near the underflow range (call after ``finishLog``)."""
+        self._allColumns()
         if self.miss8 is None:
             return False
         if self._bound_ok is None:
@@ -579,6 +607,7 @@ class DeviceModel:
         """Candidates (t, j) = prev_ids[t] + [cols[j]] that can reach the top_n cut: those with
         M = sum_r min(miss) <= the top_n-th smallest M among ``first``.  Returns (candidates, M_T, flat indices
         ascending, their M) or None when more than ``cap`` qualify."""
+        self._allColumns()
         prev_ids, cols = _i32(prev_ids), _i32(cols)
         n_sets, c_prev = prev_ids.shape
         first = np.ascontiguousarray(first, dtype=np.uint8)

@@ -226,6 +226,8 @@ class TypingWithPosNegAllele(_OnLane):
         from . import _lib
         from ._lib import check, lib
         from .typing_mulit_allele import AlleleTypingExonFirst
+        from .utils import testHook
+        full_tables = testHook("full_tables") is not None      # tests: the table of every allele, whatever the candidates
         tab, logs = self._context()
         udev = tab.dev.urgent()
         prep_f = tab.prepared(udev, self._multiple)
@@ -296,13 +298,16 @@ class TypingWithPosNegAllele(_OnLane):
             result = p["typ_e"].result[-1]
             result.setNameGroup(p["groups"])
             rows_f, n_f, vflag_f, prepared_f = p["full"]
-            full = AlleleTyping(ReadSet(tab, rows_f, n_f, vflag_f), view.variants, force_homo=p["force"], top_n=top_n // 5,
-                                variant_correction=True, logs=logs, _vbeg=view.vbeg, _n_span=view.n_span, _mask=view.mask,
-                                _alleles=view.alleles, _novel=view.novel, _prepared=prepared_f, _defer_launch=True)
-            p["full_model"] = full
+
+            def full_model(table_cols=None):
+                return AlleleTyping(ReadSet(tab, rows_f, n_f, vflag_f), view.variants, force_homo=p["force"], top_n=top_n // 5,
+                                    variant_correction=True, logs=logs, _vbeg=view.vbeg, _n_span=view.n_span, _mask=view.mask,
+                                    _alleles=view.alleles, _novel=view.novel, _prepared=prepared_f, _defer_launch=True,
+                                    _table_cols=table_cols)
             if not result.value.shape[0]:
                 # no exon set: the reference types the gene with the full model (typing_mulit_allele.py:757-759)
                 logger.warning("[Allele] Cannot typing with exon-only reads. Typing with exon+intron")
+                p["full_model"] = full_model()
                 p["fallback"] = True
                 continue
             ranks = list(result.topRank(threshold=threshold))
@@ -311,14 +316,22 @@ class TypingWithPosNegAllele(_OnLane):
             if len(ranks) > 1024:
                 p["per_gene"] = True            # a flood of tied exon sets: the per-gene path stacks their searches per launch
                 continue
+            # The searches only ever offer the alleles of the candidate sets (addCandidate(candidate_allele), 506-520 and
+            # 740-746), so the table is written for those columns alone -- unless they are all of them.
+            allele_to_id = {a: i for i, a in enumerate(view.alleles)}
+            cand_steps = [[np.ascontiguousarray([allele_to_id[a] for a in names], dtype=np.int32)
+                           for names in result.allele_name_group[i]] for i in ranks]
+            table_cols = np.unique(np.concatenate([c for steps in cand_steps for c in steps])).astype(np.int32)
+            if full_tables or len(table_cols) == len(view.alleles):
+                table_cols = None
+            full = p["full_model"] = full_model(table_cols)
+            self.exon_info[gene]["table_columns"] = len(view.alleles) if table_cols is None else len(table_cols)
             job, _ = full.geneJob(cn, False)
             job.n_steps = 0                     # table + column sums; the searches are the jobs behind it
             p["job2"] = len(jobs2)
             jobs2.append(job)
             p["cands"] = []
-            for i in ranks:
-                steps = [np.ascontiguousarray([full.allele_to_id[a] for a in names], dtype=np.int32)
-                         for names in result.allele_name_group[i]]
+            for steps in cand_steps:
                 cols = np.ascontiguousarray(np.concatenate(steps), dtype=np.int32)
                 offs = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(x) for x in steps])]), dtype=np.int32)
                 keep_alive += [cols, offs]

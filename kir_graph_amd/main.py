@@ -282,14 +282,17 @@ def alleleTyping(processed_bam, cn_files: list[str], method: str = "full", relea
     ``processed_bam`` entries are names (the ``.json`` next to them is loaded) or (name, SampleData);
     ``release``: close every SampleData's tabulation once its results are taken (the pipeline does).
     The samples go through the process's typing lanes (``sampleTyper``): up to GK_SAMPLE_LANES at a time, results in
-    order -- the reference types them one after the other (main.py:178-220), the files are the same."""
+    order -- the reference types them one after the other (main.py:178-220), the files are the same.
+    As many samples again wait behind the lanes: the results are taken in order, so with only ``lanes`` samples handed
+    in, a lane that finishes before the oldest sample has nothing to start until that one is done and collected here
+    (the samples are tabulated already or come from files: one that waits holds nothing more than it held before)."""
     allele_files = []
     with sampleTyper(method, release=release) as lanes:
         for entry, cn_file in zip(processed_bam, cn_files):
             name, source = entry if isinstance(entry, tuple) else (entry, entry + ".json")
             logger.debug(f"[Allele] Allele typing ({method}) with CN {cn_file} ({name})")
             lanes.submit(source, (lambda f=cn_file: loadCN(f)), (name, cn_file, source))
-            if lanes.inFlight() >= lanes.lanes:
+            if lanes.inFlight() >= 2 * lanes.lanes:
                 allele_files.append(lanes.next())
         allele_files.extend(lanes.drain())
     return allele_files

@@ -455,11 +455,13 @@ class AlleleTyping:
                  no_empty: bool = True, variant_correction: bool = True, *, device: Device | None = None,
                  logs: LogTable | None = None, _vbeg: int = 0, _n_span: int | None = None,
                  _mask: DeviceBuffer | None = None, _alleles: list[str] | None = None, _defer_log: bool = False,
-                 _novel=None, _prepared: tuple | None = None, _defer_launch: bool = False):
+                 _novel=None, _prepared: tuple | None = None, _defer_launch: bool = False,
+                 _table_cols: np.ndarray | None = None):
         """``_prepared`` = (rows with a surviving id, their count, shared drop flags, shared tallies, (gene, vbeg, vend)):
         error correction and removal of empty reads already done for the whole sample (``Tabulation.prepared``).
         ``_defer_launch``: the tables are allocated, not written -- ``gk_sample_search`` writes them and runs the
-        search together with the sample's other genes (``kir_typing.TypingWithPosNegAllele``)."""
+        search together with the sample's other genes (``kir_typing.TypingWithPosNegAllele``).  ``_table_cols`` (with
+        ``_defer_launch``): the tables hold these allele ordinals only (``engine.DeviceModel``)."""
         self.top_n = top_n
         self._no_empty = no_empty
         self.force_homo = force_homo
@@ -505,7 +507,8 @@ class AlleleTyping:
         import os
         self._model = DeviceModel(tab, rows, n_rows, rs.vflag, _vbeg, _vbeg + n_span, _mask, words, n_allele,
                                   self._logs, keep_empty=not no_empty, launch=not _defer_launch,
-                                  indexed=_defer_launch and os.environ.get("GK_INDEX_TABLE", "0") == "1")
+                                  indexed=_defer_launch and os.environ.get("GK_INDEX_TABLE", "0") == "1",
+                                  table_cols=_table_cols if _defer_launch else None)
         self._colsum_all: np.ndarray | None = None
         self._pair_table: np.ndarray | None = None    # scores of all allele pairs (second step), when formed
         self._reads_cache = None
@@ -685,12 +688,14 @@ class AlleleTyping:
             homo = self._isHomozygous(cn) if verdict is None else verdict
         m = self._model
         vbeg, vend, mask, words = m._geom
+        cols = m._table_cols       # the tables hold these alleles only (the array lives as long as the model)
         job = GeneJob(d_rows=m.rows.ptr, n_rows=m.n_rows, d_mask=mask.ptr, d_L=m._L.ptr if m._L else 0,
                       d_miss8=m.miss8.ptr if m.miss8 else 0, ldm=m.ldm, d_msum=m.msum.ptr if m.msum else 0,
                       d_flags=m._bound_flags.ptr if m._bound_flags else 0, d_lidx=m.lidx.ptr if m.lidx else 0,
                       vbeg=vbeg, vend=vend, words=words, n_allele=m.n_allele, n_steps=1 if homo else cn,
                       top_n=self.top_n, bound_ok=0, passes=0, indexed=0, patches=0, table_of=-1, n_step_cols=0,
-                      step_cols=None, step_cols_off=None)
+                      step_cols=None, step_cols_off=None, table_cols=None if cols is None else cols.ctypes.data,
+                      n_table_cols=0 if cols is None else len(cols))
         return job, homo
 
     def adoptJob(self, job, handle, cn: int, homo: bool) -> TypingResult:
@@ -712,20 +717,23 @@ class AlleleTyping:
 
     def adoptTable(self, job, handle) -> None:
         """A table-only job of ``gk_sample_search`` (n_steps == 0): the model's table is final and its column sums are
-        known; the searches on it were other jobs of the call."""
+        known; the searches on it were other jobs of the call.  The job may have written the columns of a list of
+        alleles only (``m._table_cols``): the column sums of all alleles are then left to whoever asks first (``_colsums``)."""
         import ctypes as C
         from ._lib import check, lib
         m = self._model
         m._bound_ok = bool(job.bound_ok)
         m._indexed = False
         m._known_at_launch = -1
+        n_written = m.n_allele if m._table_cols is None else len(m._table_cols)
         if m.dev.call_log is not None:
             per_row = m.tab.n_ids / max(m.tab.n_valid, 1)
             for _ in range(max(1, int(job.passes))):
-                m.dev.call_log.append(("compat_kernel", m.n_rows, m.n_allele, per_row * m.n_rows, 8))
+                m.dev.call_log.append(("compat_kernel", m.n_rows, n_written, per_row * m.n_rows, 8))
             self._logLaunches(handle)       # the column sums of the whole table: this job's launch, nobody else logs it
-        self._colsum_all = np.empty(m.n_allele, dtype=np.float64)
-        check(lib().gk_search_colsum(handle, self._colsum_all.ctypes.data))
+        colsum = np.empty(m.n_allele, dtype=np.float64)
+        check(lib().gk_search_colsum(handle, colsum.ctypes.data))    # NaN for the alleles a list leaves out
+        self._colsum_all = colsum if m._table_cols is None else None
         self.result = []
 
     def addHomoResultForCn(self, cn: int) -> None:
