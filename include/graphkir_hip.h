@@ -473,6 +473,29 @@ typedef struct gk_em_job {
 int gk_sample_em(gk_ctx* ctx, gk_tab* tab, gk_em_job* jobs, int32_t n_jobs, int32_t iter_max, double diff_threshold,
                  double* prob_out, int64_t* count_out);
 
+/* Read bootstrap of the EM strategy: n_boot replicates of every job (gene) in ONE call -- one launch draws the replicate
+ * weights (n reads with replacement from the gene's n reads, n = the sum of its multiplicities, the empty set included),
+ * one launch runs the SQUAREM loop of gk_em_run for every (job, replicate), one wait.  Draw i of replicate b of stream g:
+ *   z = seed + (i+1)*0x9E3779B97F4A7C15 + (b+1)*0xBF58476D1CE4E5B9 + (g+1)*0x94D049BB133111EB   (64-bit, wrapping)
+ *   z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *   j = ((z >> 32) * n) >> 32, which falls on the set u with cum[u] <= j < cum[u+1] (cum: prefix sums of count)
+ * so a replicate depends on (seed, b, stream) alone, not on n_boot or on the other jobs of the call.  The empty set (only
+ * ever the first of ascending distinct sets) takes its draws and is then dropped.  Requires 1 <= n_boot <= 10000,
+ * words <= 16, n_allele <= words * 32, sum of count < 2^31.  n_jobs == 0 or a job without sets: outputs zero. */
+typedef struct gk_boot_job {
+  const uint32_t* sets;  /* host: distinct sets [n_sets][words], ascending, the empty set allowed */
+  const uint32_t* count; /* host: multiplicities [n_sets] */
+  int32_t n_sets;
+  int32_t words;
+  int32_t n_allele;
+  uint32_t stream;
+} gk_boot_job;
+int gk_em_bootstrap(gk_ctx* ctx, const gk_boot_job* jobs, int32_t n_jobs, int32_t n_boot, uint64_t seed,
+                    int32_t iter_max, double diff_threshold,
+                    double* prob_out,      /* [n_boot][sum n_allele], jobs one after the other */
+                    int32_t* iters_out,    /* [n_boot][n_jobs] */
+                    uint32_t* counts_out); /* nullable: [n_boot][sum n_sets], the replicate weights */
+
 /* ---- host ingest (no GPU): name-collated SAM text -> gk_mate records.
  * Native form of readPair (hisat2.py:228-276), of the field reads of filterRead / getNH (551-569,
  * 95-100) and of the CIGAR / MD / Zs consistency checks of recordToRawVariant (279-515).  Text is fed

@@ -71,6 +71,14 @@ class EmJob(C.Structure):
     ]
 
 
+class BootJob(C.Structure):
+    """``gk_boot_job`` (include/graphkir_hip.h): one gene of ``gk_em_bootstrap`` (host pointers)."""
+    _fields_ = [
+        ("sets", C.c_void_p), ("count", C.c_void_p),
+        ("n_sets", C.c_int32), ("words", C.c_int32), ("n_allele", C.c_int32), ("stream", C.c_uint32),
+    ]
+
+
 class TabInfo(C.Structure):
     _fields_ = [
         ("n_pairs", C.c_int64), ("n_valid", C.c_int64), ("n_ids", C.c_int64),
@@ -252,6 +260,8 @@ _SIGS = {
     "gk_h2d_async": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]),
     "gk_em_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                             C.c_double, C.c_void_p, C.POINTER(C.c_int32)]),
+    "gk_em_bootstrap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_double,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 EXPORTED = sorted(_SIGS)

@@ -189,13 +189,14 @@ class SampleTyper:
     release its HBM); its return value is the sample's result."""
 
     def __init__(self, method: str, lanes: int | None = None, top_n: int = 600, variant_correction: bool = True,
-                 finish=None):
+                 finish=None, **typer_kwargs):
         from concurrent.futures import ThreadPoolExecutor
         import queue
         self.method = "exonfirst_1" if method == "exonfirst" else method     # main.py:186-187
         self.lanes = sampleLanes() if lanes is None else max(1, lanes)
         self.top_n, self.variant_correction = top_n, variant_correction
         self.finish = finish
+        self.typer_kwargs = typer_kwargs      # further keywords of the strategy (the EM's bootstrap, bootstrap_seed)
         self._pool = ThreadPoolExecutor(max_workers=self.lanes, thread_name_prefix="gk-sample") if self.lanes > 1 else None
         self._free = queue.SimpleQueue()
         for lane in range(self.lanes):
@@ -230,7 +231,8 @@ class SampleTyper:
     def typeOne(self, data, gene_cn, item=None, lane: int = 0):
         """One sample on the calling thread, on lane ``lane``'s contexts."""
         from .kir_typing import selectKirTypingModel
-        typer = selectKirTypingModel(self.method, data, top_n=self.top_n, variant_correction=self.variant_correction)
+        typer = selectKirTypingModel(self.method, data, top_n=self.top_n, variant_correction=self.variant_correction,
+                                     **self.typer_kwargs)
         typer.slot_base = lane
         calls, warnings = typer.typing(gene_cn() if callable(gene_cn) else gene_cn)
         if self.finish is not None:

@@ -18,7 +18,7 @@ import numpy as np
 
 from ._lib import Device
 from .hisat2 import SampleData, loadReadsAndVariantsData
-from .typing_em import Hisat2AlleleResult, hisat2TypingPerGene
+from .typing_em import EmBootstrap, Hisat2AlleleResult, callsByAbundance, hisat2TypingPerGene
 from .typing_mulit_allele import (AlleleTyping, AlleleTypingExonFirst, ReadSet, StepList, isHetrozygous,
                                   sharedLogTable)
 from .utils import NumpyEncoder, logger
@@ -544,10 +544,16 @@ class TypingWithPosNegAllele(_OnLane):
 class TypingWithReport(_OnLane):
     """Abundance typing by the HISAT-genotype EM (153-204)."""
 
-    def __init__(self, filename_variant_json, device: Device | None = None):
+    def __init__(self, filename_variant_json, device: Device | None = None, bootstrap: int = 0, bootstrap_seed: int = 2022):
+        """``bootstrap`` > 0: after the point result, that many read-bootstrap replicates of every gene's EM in one
+        ``gk_em_bootstrap`` call (``self.bootstrap``: gene -> ``EmBootstrap``); 0: nothing but the point result."""
         super().__init__()
+        if int(bootstrap) < 0:
+            raise ValueError("bootstrap: the number of replicates cannot be negative")
         self._data = _sample(filename_variant_json, device)
         self.em_info: dict[str, dict] = {}      # per gene: iterations used, distinct candidate sets
+        self._n_boot, self._boot_seed = int(bootstrap), int(bootstrap_seed)
+        self.bootstrap: dict[str, EmBootstrap] = {}
 
     def typing(self, gene_cn: dict[str, int], min_reads_num: int = 100) -> tuple[list[str], list[str]]:
         """All genes of the sample through ``gk_sample_em``: candidate sets, distinct sets and the SQUAREM loops of every
@@ -589,11 +595,15 @@ class TypingWithReport(_OnLane):
                 self.em_info[todo[k][0]] = {"iterations": int(jobs[q].iterations), "distinct_sets": int(jobs[q].n_distinct)}
         predict_alleles, warning_genes = [], []
         self._result = {}
+        point_calls = {}
         for k, (gene, cn) in enumerate(todo):
             alleles, reads_num = self._callsOfReport(gene, cn, reports.get(k, []), views[k].n_rows if views[k].g is not None else 0)
+            point_calls[k] = alleles
             predict_alleles.extend(alleles)
             if reads_num < min_reads_num:
                 warning_genes.append(gene)
+        if self._n_boot > 0:
+            self._bootstrapGenes(tab, [(todo[k][0], todo[k][1], views[k], point_calls[k]) for k in live])
         return predict_alleles, warning_genes
 
     def typingPerGene(self, gene: str, cn: int) -> tuple[list[str], int]:
@@ -606,25 +616,43 @@ class TypingWithReport(_OnLane):
             report = hisat2TypingPerGene(tab, view.rows, view.n_rows, view.vbeg, view.vbeg + view.n_span,
                                          view.mask, t.words, view.alleles, info=info)
             self.em_info[gene] = info
-        return self._callsOfReport(gene, cn, report, view.n_rows)
+        called, n_rows = self._callsOfReport(gene, cn, report, view.n_rows)
+        if self._n_boot > 0 and report:
+            self._bootstrapGenes(tab, [(gene, cn, view, called)])
+        return called, n_rows
+
+    def _bootstrapGenes(self, tab, genes: list) -> None:
+        """The read bootstrap of the listed (gene, cn, view, point call) in ONE ``gk_em_bootstrap`` call: the distinct
+        candidate sets of every gene that has a report (``candidateSetsDistinct``), its replicates drawn on the stream
+        numbered like the gene in the index -- so a gene's replicates are the same whichever genes are typed with it."""
+        from .typing_em import bootstrapEM, candidateSetsDistinct, summariseBootstrap
+        genes = [e for e in genes if self._result.get(e[0])]
+        if not genes:
+            return
+        jobs = []
+        for gene, cn, v, called in genes:
+            t = self._data.index.tables[v.g]
+            sets, count = candidateSetsDistinct(tab, v.rows, v.n_rows, v.vbeg, v.vbeg + v.n_span, v.mask, t.words)
+            jobs.append((sets, count, len(v.alleles), v.g))
+        prob, iters = bootstrapEM(tab, jobs, self._n_boot, self._boot_seed)
+        at = 0
+        for q, (gene, cn, v, called) in enumerate(genes):
+            n = len(v.alleles)
+            self.bootstrap[gene] = summariseBootstrap(gene, cn, self._result[gene], called, v.alleles, prob[:, at:at + n],
+                                                      iters[:, q])
+            at += n
 
     def _callsOfReport(self, gene: str, cn: int, report: list, n_rows: int) -> tuple[list[str], int]:
         """Abundances -> calls (kir_typing.py:181-192): the copy numbers go to the alleles in descending abundance."""
         pure_gene = gene.split("*")[0]
-        # descending abundance; ties by allele name (the reference leaves them to set order)
-        report.sort(key=lambda r: (-r.prob, r.allele))
         if not report:
             self._result[gene] = report
             return [f"{pure_gene}*"] * cn, n_rows   # the reference raises AxisError here
-        est_prob = 1 / cn
-        called = []
-        for rec in report:
-            pred = max(1, round(rec.prob / est_prob))
-            called.extend([rec.allele] * min(cn, pred))
-            rec.cn = pred
-            cn -= pred
-            if cn <= 0:
-                break
+        # descending abundance; ties by allele name (the reference leaves them to set order)
+        called, order, pred = callsByAbundance([r.allele for r in report], [r.prob for r in report], cn)
+        report[:] = [report[i] for i in order]
+        for rec, k in zip(report, pred):
+            rec.cn = k
         self._result[gene] = report
         return called, n_rows
 
@@ -634,6 +662,11 @@ class TypingWithReport(_OnLane):
 
 def selectKirTypingModel(method: str, filename_variant_json, **kwargs: Any) -> Typing:
     """Select and initialise the typing strategy (207-228)."""
+    if method not in ("em", "report"):
+        # the read bootstrap belongs to the EM strategy (the likelihood strategies have their .possible.tsv)
+        kwargs.pop("bootstrap_seed", None)
+        if kwargs.pop("bootstrap", 0):
+            raise ValueError(f"bootstrap: only the em / report strategy has a read bootstrap, not {method!r}")
     if method in ("full", "pv"):
         return TypingWithPosNegAllele(filename_variant_json, **kwargs)
     if method.startswith("pv_exonfirst"):

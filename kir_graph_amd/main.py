@@ -236,6 +236,16 @@ def writeTyping(name: str, typer, called_alleles: list[str], warning_genes: list
     return name + ".tsv"
 
 
+def writeConfidence(name: str, bootstrap: dict) -> str:
+    """``{name}.confidence.tsv`` of one sample typed with ``--em-bootstrap``: per allele of every gene's EM report the
+    point values, the replicates' mean / sd / 2.5 % / 97.5 % abundance and the support of the call
+    (``typing_em.confidenceText``)."""
+    from .typing_em import confidenceText
+    with open(name + ".confidence.tsv", "w") as f:
+        f.write(confidenceText(bootstrap))
+    return name + ".confidence.tsv"
+
+
 def discoverAfterTyping(typer, called_alleles: list[str], name: str, result: str, index_ref: str) -> None:
     """Novel-variant discovery of one typed sample, on its tabulation in HBM (novel_discover.discoverSample):
     ``{result}.novel.variant.tsv / .tsv / .fa / .bam / .txt``, the reads piled up from ``{name}.no_multi.bam``."""
@@ -249,12 +259,15 @@ def discoverAfterTyping(typer, called_alleles: list[str], name: str, result: str
     data.pairs_text = None
 
 
-def sampleTyper(method: str, release: bool = True, novel_index: str | None = None) -> "cohort.SampleTyper":
+def sampleTyper(method: str, release: bool = True, novel_index: str | None = None, bootstrap: int = 0,
+                bootstrap_seed: int = 2022) -> "cohort.SampleTyper":
     """The typing stage of this process (``cohort.SampleTyper``: the sample lanes, search slots, urgent preamble and
     blocking waits that ``bench.py`` measures), finishing every sample the reference's way: its two files written, its
     tabulation released.  Submit ``(SampleData or hand-off file, copy numbers, (name, cn_file))``.
     ``novel_index`` (``--novel-discovery``): the index prefix; every typed sample then goes through novel_discover.py
-    (``{result}.novel.*``, typingNovelWrap of the reference's research/kg_main.py) before its tabulation is released."""
+    (``{result}.novel.*``, typingNovelWrap of the reference's research/kg_main.py) before its tabulation is released.
+    ``bootstrap`` > 0 (``--em-bootstrap``, EM strategy): the typer also runs that many read-bootstrap replicates and the
+    finish step writes ``{result}.confidence.tsv``."""
     def finish(typer, called_alleles, warning_genes, item):
         name, cn_file, source = item
         result = name + typingSuffix(name, cn_file, method)
@@ -271,9 +284,12 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
                 tab.close()
             logger.info(f"[Allele] {called_alleles} ({name})")
             written = writeTyping(result, typer, called_alleles, warning_genes)
+            if bootstrap > 0:
+                writeConfidence(result, typer.bootstrap)
         return written
 
-    return cohort.SampleTyper(method, finish=finish)
+    extra = {"bootstrap": bootstrap, "bootstrap_seed": bootstrap_seed} if bootstrap > 0 else {}
+    return cohort.SampleTyper(method, finish=finish, **extra)
 
 
 def alleleTyping(processed_bam, cn_files: list[str], method: str = "full", release: bool = False) -> list[str]:
@@ -349,6 +365,10 @@ def createParser() -> argparse.ArgumentParser:
                    help="After typing, look for novel variants of the called alleles in their reads: writes "
                         "{result}.novel.variant.tsv / .tsv / .fa / .bam / .txt per sample (needs the .no_multi.bam, so "
                         "not with --no-variant-json)")
+    p.add_argument("--em-bootstrap", type=int, default=0,
+                   help="EM strategy only: this many read-bootstrap replicates per gene after typing; writes "
+                        "{result}.confidence.tsv (abundance spread per allele, support of the call)")
+    p.add_argument("--em-bootstrap-seed", type=int, default=2022, help="Seed of the bootstrap draws")
     p.add_argument("--ranks", type=int, default=1,
                    help="Start this many rank processes (samples are sharded over them; ranks map to GPUs round robin, "
                         "so 3 x the GPU count keeps every GPU busy).  Not needed under torchrun / any launcher that "
@@ -368,6 +388,9 @@ def main(args: argparse.Namespace) -> None:
         raise NotImplementedError("WGS extraction (bwa) is outside this build: pass --step-skip-extraction")
     if args.plot:
         raise NotImplementedError("--plot is outside this build")
+    n_boot = int(getattr(args, "em_bootstrap", 0) or 0)
+    if n_boot < 0 or (n_boot > 0 and args.allele_strategy not in ("em", "report")):
+        raise ValueError("--em-bootstrap needs a positive count and --allele-strategy em (or report)")
 
     if not args.input_csv:
         if not args.r1 and not args.alignment:
@@ -439,7 +462,8 @@ def _runCohort(args, names, reads, cn_files, index, index_ref, cohort_name, comm
     method = {"pv": "full", "report": "em"}.get(args.allele_strategy, args.allele_strategy)
     pooled_fit = args.cn_cohort and not all(cn_files)
     novel = getattr(args, "novel_discovery", False)
-    lanes = sampleTyper(method, novel_index=index_ref if novel else None)
+    lanes = sampleTyper(method, novel_index=index_ref if novel else None, bootstrap=int(getattr(args, "em_bootstrap", 0) or 0),
+                        bootstrap_seed=int(getattr(args, "em_bootstrap_seed", 2022)))
     try:
         allele_files, my_cn = _typeShare(args, lanes, pick(names), pick(reads), my_cn, pick, index, index_ref, cohort_name,
                                          comm, kwargs, pooled_fit)

@@ -12,7 +12,8 @@ from process to process.
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from collections import Counter
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -114,3 +115,114 @@ def hisat2TypingPerGene(tab: Tabulation, rows: DeviceBuffer, n_rows: int, vbeg: 
         info["iterations"], info["distinct_sets"] = iters, len(sets[0])
     named = np.nonzero(count)[0]
     return [Hisat2AlleleResult(allele=alleles[a], count=int(count[a]), prob=float(prob[a])) for a in named]
+
+
+def callsByAbundance(alleles: list[str], prob: list[float], cn: int) -> tuple[list[str], list[int], list[int]]:
+    """Abundances -> calls (kir_typing.py:181-192): the copy numbers go to the alleles in descending abundance, ties by
+    allele name; an allele takes ``max(1, round(p * cn))`` copies until none are left.
+
+    Returns the called alleles, the order the alleles were visited in (indices into ``alleles``; all of them) and the
+    copies predicted for the visited ones (as many entries as were visited before the copies ran out)."""
+    order = sorted(range(len(alleles)), key=lambda i: (-prob[i], alleles[i]))
+    est_prob = 1 / cn
+    called: list[str] = []
+    pred: list[int] = []
+    for i in order:
+        k = max(1, round(float(prob[i]) / est_prob))
+        called.extend([alleles[i]] * min(cn, k))
+        pred.append(k)
+        cn -= k
+        if cn <= 0:
+            break
+    return called, order, pred
+
+
+@dataclass
+class EmBootstrap:
+    """Read bootstrap of one gene's EM report: ``prob[b, a]`` is the abundance of ``alleles[a]`` (the alleles of the
+    point report, in report order) in replicate ``b``, ``calls[b]`` the replicate's calls by the rule of the point call,
+    ``call_support`` the share of replicates whose calls equal the point call as a multiset, ``rows`` the lines of
+    ``{result}.confidence.tsv`` (one per allele: point values, replicate mean / sd / 2.5 % / 97.5 %, support)."""
+
+    alleles: list[str]
+    prob: np.ndarray
+    iterations: np.ndarray
+    calls: list[list[str]]
+    call_support: float
+    rows: list[dict] = field(default_factory=list)
+
+
+CONFIDENCE_COLUMNS = ["gene", "allele", "cn", "count", "prob", "boot_mean", "boot_sd", "boot_lo", "boot_hi", "support",
+                      "call_support"]
+
+
+def bootstrapEM(tab, genes: list[tuple[np.ndarray, np.ndarray, int, int]], n_boot: int,
+                seed: int, iter_max: int = 300, diff_threshold: float = 0.0001,
+                want_counts: bool = False):
+    """``n_boot`` bootstrap replicates of the EM of every gene in ONE ``gk_em_bootstrap`` call.
+
+    ``genes``: (distinct sets uint32 [n_sets][words] ascending, multiplicities, alleles, stream number) per gene, the
+    empty set included (``candidateSetsDistinct``).  Returns ``prob[n_boot, sum of alleles]`` (genes one after the
+    other) and ``iterations[n_boot, genes]``; with ``want_counts`` also the replicate weights ``[n_boot, sum of sets]``."""
+    from . import _lib
+    jobs = (_lib.BootJob * max(len(genes), 1))()
+    keep = []
+    for q, (sets, count, n_allele, stream) in enumerate(genes):
+        sets = np.ascontiguousarray(sets, dtype=np.uint32)
+        assert sets.ndim == 2, "distinct sets: uint32 [n_sets][words]"
+        count = np.asarray(count)
+        if len(count) and (count.min() < 0 or int(count.sum()) >= 1 << 31):
+            raise ValueError("bootstrapEM: multiplicities must be non-negative and sum to less than 2^31")
+        count = np.ascontiguousarray(count, dtype=np.uint32)
+        assert len(count) == len(sets)
+        keep += [sets, count]
+        jobs[q] = _lib.BootJob(sets=sets.ctypes.data, count=count.ctypes.data, n_sets=len(sets), words=max(sets.shape[1], 1),
+                               n_allele=int(n_allele), stream=int(stream))
+    total = sum(int(g[2]) for g in genes)
+    n_sets = sum(len(g[1]) for g in genes)
+    prob = np.zeros((n_boot, total), dtype=np.float64)
+    iters = np.zeros((n_boot, len(genes)), dtype=np.int32)
+    counts = np.zeros((n_boot, n_sets), dtype=np.uint32) if want_counts else None
+    dev = getattr(tab, "dev", tab)      # a tabulation, or the device context itself
+    check(lib().gk_em_bootstrap(dev.ctx, jobs, len(genes), n_boot,
+                                int(seed) & 0xFFFFFFFFFFFFFFFF, iter_max, diff_threshold, prob.ctypes.data, iters.ctypes.data,
+                                counts.ctypes.data if want_counts else None))
+    del keep
+    return (prob, iters, counts) if want_counts else (prob, iters)
+
+
+def summariseBootstrap(gene: str, cn: int, report: list[Hisat2AlleleResult], called: list[str], alleles: list[str],
+                       prob: np.ndarray, iterations: np.ndarray) -> EmBootstrap:
+    """The derived numbers of one gene (host; B x A is small).  ``report``: the point report as ``_callsOfReport`` left
+    it (sorted, copies filled in); ``called``: the point call; ``prob[B, len(alleles)]``: the replicates' abundances of
+    ALL alleles of the gene.  A replicate's report is the point report's alleles with the replicate's abundances."""
+    col = {a: i for i, a in enumerate(alleles)}
+    names = [r.allele for r in report]
+    x = np.ascontiguousarray(prob[:, [col[a] for a in names]], dtype=np.float64).reshape(len(prob), len(names))
+    n_boot = len(x)
+    calls = [callsByAbundance(names, x[b].tolist(), cn)[0] for b in range(n_boot)]
+    point = Counter(called)
+    tallies = [Counter(c) for c in calls]
+    call_support = sum(t == point for t in tallies) / n_boot
+    rows = []
+    for i, rec in enumerate(report):
+        need = max(1, point.get(rec.allele, 0))      # an allele that is not called: the replicates that call it at all
+        lo, hi = np.percentile(x[:, i], [2.5, 97.5])
+        rows.append({"gene": gene, "allele": rec.allele, "cn": int(rec.cn), "count": int(rec.count), "prob": float(rec.prob),
+                     "boot_mean": float(x[:, i].mean()), "boot_sd": float(x[:, i].std(ddof=1)) if n_boot > 1 else 0.0,
+                     "boot_lo": float(lo), "boot_hi": float(hi),
+                     "support": sum(t.get(rec.allele, 0) >= need for t in tallies) / n_boot,
+                     "call_support": call_support})
+    return EmBootstrap(alleles=names, prob=x, iterations=np.asarray(iterations).copy(), calls=calls,
+                       call_support=call_support, rows=rows)
+
+
+def confidenceText(bootstrap: dict[str, EmBootstrap]) -> str:
+    """``{result}.confidence.tsv``: tab separated, one row per allele of every gene's point report in report order,
+    floats as ``repr(float)``."""
+    lines = ["\t".join(CONFIDENCE_COLUMNS)]
+    for boot in bootstrap.values():
+        for row in boot.rows:
+            lines.append("\t".join(str(row[k]) if isinstance(row[k], (str, int)) else repr(float(row[k]))
+                                   for k in CONFIDENCE_COLUMNS))
+    return "\n".join(lines) + "\n"
