@@ -55,12 +55,12 @@ KERNEL_SOURCES = {
     "em_sets_hash": ["gk_em.hip", "gk_common.h"],
     "em_sets_verify": ["gk_em.hip", "gk_common.h"],
     "em_sets_emit": ["gk_em.hip", "gk_common.h"],
-    "em_kernel_genes": ["gk_em.hip", "gk_common.h"],
+    "em_kernel_genes": ["gk_em.hip", "gk_squarem.h", "gk_common.h"],
     "novel_assign": ["gk_novel.hip", "gk_common.h"],
     "novel_confusion": ["gk_novel.hip", "gk_common.h"],
     "novel_compact": ["gk_novel.hip", "gk_common.h"],
-    "boot_resample": ["gk_boot.hip"],
-    "boot_em_batch": ["gk_boot.hip"],
+    "boot_resample": ["gk_boot.hip", "gk_common.h"],
+    "boot_em_batch": ["gk_boot.hip", "gk_squarem.h", "gk_common.h"],
 }
 
 

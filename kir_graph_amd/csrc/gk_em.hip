@@ -15,21 +15,20 @@
 //                    words of the first pair of its hash: equal hashes of different sets raise a flag and the sets are
 //                    hashed again with another seed -- the classes are exact, never "probably" so.
 //   gk_em_run / gk_sample_em   hisatEMnp 107-188 on the distinct sets with multiplicities.  The reference builds a dense
-//                    0/1 read x allele float matrix and sweeps it 3-4 times per iteration; here a workgroup per gene runs
-//                    the whole SQUAREM loop on two sparse forms of the sets (members of a set / sets of an allele), 16
-//                    lanes per set or allele, the abundances in LDS.  Sums are evaluated in a fixed order, so results are
-//                    run-to-run deterministic; they agree with numpy's row-sequential sums to rounding (tolerance 1e-5
-//                    relative per BASELINE.json north_star).
+//                    0/1 read x allele float matrix and sweeps it 3-4 times per iteration; here a workgroup per gene
+//                    (em_kernel_genes) runs the whole SQUAREM loop on two sparse forms of the sets (members of a set /
+//                    sets of an allele).  The loop, the sparse forms and their builder are gk_squarem.h's, which the
+//                    bootstrap of gk_boot.hip instantiates too; this file holds the kernel that hands a gene to it and
+//                    the launch.  Results are run-to-run deterministic; they agree with numpy's row-sequential sums to
+//                    rounding (tolerance 1e-5 relative per BASELINE.json north_star).
 #include <algorithm>
 #include <type_traits>
 #include <vector>
 
 #include "gk_common.h"
+#include "gk_squarem.h"
 
 namespace {
-
-constexpr int kMaxWords = 16;    // up to 512 alleles per gene
-constexpr int kMaxAllele = kMaxWords * 32;
 
 // ------------------------------------------------------------------------------------------------ candidate sets
 constexpr int kSetThreads = 1024;        // 16 waves: one workgroup per CU (the bit rows of a gene fill most of its LDS)
@@ -317,16 +316,6 @@ __global__ __launch_bounds__(256) void em_sets_emit(const EmSetsJob* __restrict_
 constexpr int kEmThreads = 1024;
 constexpr int kEmScaleLds = 8192;        // sets whose 1 / (sum of member abundances) live in LDS; more go through HBM / L2
 
-// one gene of em_kernel_genes: its distinct sets in two sparse forms
-struct EmGene {
-  int64_t w_off;          // weight / scale [n_sets]
-  int64_t so_off;         // set_off [n_sets + 1]: members of set u = members[mem_off + set_off[u] .. set_off[u + 1])
-  int64_t mem_off;        // members: allele numbers (uint16), and al_sets: set numbers (uint32) -- both nnz entries
-  int64_t ao_off;         // al_off [n_allele + 1]: sets of allele a = al_sets[mem_off + al_off[a] .. al_off[a + 1])
-  int64_t prob_off;
-  int32_t n_sets, n_allele;
-};
-
 struct EmArrays {
   const double* weight;
   double* scale;
@@ -336,121 +325,22 @@ struct EmArrays {
   const uint32_t* al_sets;
 };
 
-struct EmLds {
-  double p[kMaxAllele], p1[kMaxAllele], p2[kMaxAllele], p3[kMaxAllele];
-  double scalar[4];
-  int flag;
-};
-
-__device__ inline double lanes16_sum(double v) {
-#pragma unroll
-  for (int d = 8; d >= 1; d >>= 1) v += __shfl_xor(v, d, 16);
-  return v;
-}
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-// next(p): q[a] = sum_u w_u * p[a] / (sum_{b in u} p[b]) over the sets that contain a, then normalised
-__device__ void em_step(const EmGene& g, const EmArrays& A, double* scale, const double* in, double* out, double* scalar) {
-  const int tid = threadIdx.x, l = tid & 15, grp = tid >> 4;
-  constexpr int kGroups = kEmThreads / 16;
-  const uint32_t* set_off = A.set_off + g.so_off;
-  const uint16_t* members = A.members + g.mem_off;
-  const uint32_t* al_off = A.al_off + g.ao_off;
-  const uint32_t* al_sets = A.al_sets + g.mem_off;
-  const double* weight = A.weight + g.w_off;
-  for (int u0 = 0; u0 < g.n_sets; u0 += kGroups) {
-    const int u = u0 + grp;
-    double t = 0.0;
-    if (u < g.n_sets)
-      for (uint32_t k = set_off[u] + l, e = set_off[u + 1]; k < e; k += 16) t += in[members[k]];
-    t = lanes16_sum(t);
-    if (u < g.n_sets && l == 0) scale[u] = t != 0.0 ? weight[u] / t : 0.0;
-  }
-  __syncthreads();
-  for (int a0 = 0; a0 < g.n_allele; a0 += kGroups) {
-    const int a = a0 + grp;
-    double s = 0.0;
-    if (a < g.n_allele)
-      for (uint32_t k = al_off[a] + l, e = al_off[a + 1]; k < e; k += 16) s += scale[al_sets[k]];
-    s = lanes16_sum(s);
-    if (a < g.n_allele && l == 0) out[a] = in[a] * s;
-  }
-  __syncthreads();
-  if (tid < 64) {
-    double t = 0.0;
-    for (int a = tid; a < g.n_allele; a += 64) t += out[a];
-    t = wave_sum(t);
-    if (tid == 0) scalar[0] = t;
-  }
-  __syncthreads();
-  const double tot = scalar[0];
-  for (int a = tid; a < g.n_allele; a += kEmThreads) out[a] = out[a] / tot;
-  __syncthreads();
-}
-
-__device__ void em_solve(EmLds& sh, const EmGene& g, const EmArrays& A, double* scale, int iter_max, double diff_threshold,
-                         double* prob_out, int* iters_out) {
-  const int tid = threadIdx.x;
-  const int n_allele = g.n_allele;
-  for (int a = tid; a < n_allele; a += kEmThreads) sh.p3[a] = 1.0;
-  __syncthreads();
-  em_step(g, A, scale, sh.p3, sh.p, sh.scalar);
-  int iters = 0;
-  for (iters = 0; iters < iter_max; ++iters) {
-    em_step(g, A, scale, sh.p, sh.p1, sh.scalar);
-    em_step(g, A, scale, sh.p1, sh.p2, sh.scalar);
-    if (tid < 64) {
-      double rs = 0.0, vs = 0.0;
-      for (int a = tid; a < n_allele; a += 64) {
-        const double r = sh.p1[a] - sh.p[a];
-        const double v = sh.p2[a] - sh.p1[a] - r;
-        rs += r * r;
-        vs += v * v;
-      }
-      rs = wave_sum(rs);
-      vs = wave_sum(vs);
-      if (tid == 0) { sh.scalar[1] = rs; sh.scalar[2] = vs; }
-    }
-    __syncthreads();
-    const double rs = sh.scalar[1], vs = sh.scalar[2];
-    if (vs > 0.0) {
-      const double gs = -sqrt(rs / vs);
-      for (int a = tid; a < n_allele; a += kEmThreads) {
-        const double r = sh.p1[a] - sh.p[a];
-        const double v = sh.p2[a] - sh.p1[a] - r;
-        const double x = sh.p[a] - r * gs * 2 + v * (gs * gs);
-        sh.p3[a] = x > 0.0 ? x : 0.0;
-      }
-      __syncthreads();
-      em_step(g, A, scale, sh.p3, sh.p1, sh.scalar);
-    }
-    if (tid < 64) {
-      double d = 0.0;
-      for (int a = tid; a < n_allele; a += 64) d += fabs(sh.p[a] - sh.p1[a]);
-      d = wave_sum(d);
-      if (tid == 0) sh.flag = d <= diff_threshold;
-    }
-    __syncthreads();
-    if (sh.flag) break;
-    for (int a = tid; a < n_allele; a += kEmThreads) sh.p[a] = sh.p1[a];
-    __syncthreads();
-  }
-  for (int a = tid; a < n_allele; a += kEmThreads) prob_out[a] = sh.p[a];
-  if (tid == 0) *iters_out = iters;
-}
-
 // the EM of every gene of a sample in ONE launch: workgroup g solves gene g (gk_sample_em; gk_em_run: one gene)
 __global__ __launch_bounds__(kEmThreads) void em_kernel_genes(const EmGene* __restrict__ genes, EmArrays A, int iter_max,
                                                               double diff_threshold, double* prob_out, int* iters_out) {
   extern __shared__ __align__(16) unsigned char em_lds[];
   EmLds& sh = *reinterpret_cast<EmLds*>(em_lds);
-  const EmGene g = genes[blockIdx.x];
-  double* scale = g.n_sets <= kEmScaleLds ? reinterpret_cast<double*>(em_lds + sizeof(EmLds)) : A.scale + g.w_off;
-  em_solve(sh, g, A, scale, iter_max, diff_threshold, prob_out + g.prob_off, iters_out + blockIdx.x);
+  const EmGene G = genes[blockIdx.x];
+  EmView<double> g;
+  g.weight = A.weight + G.w_off;
+  g.set_off = A.set_off + G.so_off;
+  g.members = A.members + G.mem_off;
+  g.al_off = A.al_off + G.ao_off;
+  g.al_sets = A.al_sets + G.mem_off;
+  g.scale = G.n_sets <= kEmScaleLds ? reinterpret_cast<double*>(em_lds + sizeof(EmLds)) : A.scale + G.s_off;
+  g.n_sets = G.n_sets;
+  g.n_allele = G.n_allele;
+  em_solve<kEmThreads>(sh, g, iter_max, diff_threshold, prob_out + G.prob_off, iters_out + blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -535,42 +425,14 @@ uint32_t slots_for(int64_t n_distinct_max) {
   return 1u << log2;
 }
 
-// the sparse forms of sorted, non-empty distinct sets for em_kernel_genes, appended to the sample's arrays
-struct EmHost {
-  std::vector<EmGene> genes;
+// the genes of an em_kernel_genes launch: their sparse forms and, one gene after the other, the weights of their sets
+struct EmHost : EmForms {
   std::vector<double> weight;
-  std::vector<uint32_t> set_off, al_off, al_sets;
-  std::vector<uint16_t> members;
-  int max_sets = 0;
   void add(const uint32_t* sets, const double* w, int n_sets, int words, int n_allele, int64_t prob_off) {
-    EmGene g{(int64_t)weight.size(), (int64_t)set_off.size(), (int64_t)members.size(), (int64_t)al_off.size(), prob_off, n_sets,
-             n_allele};
-    std::vector<uint32_t> per_allele((size_t)n_allele + 1, 0);
-    const size_t m0 = members.size();
-    for (int u = 0; u < n_sets; ++u) {
-      set_off.push_back((uint32_t)(members.size() - m0));
-      for (int q = 0; q < words; ++q) {
-        uint32_t bits = sets[(size_t)u * words + q];
-        while (bits) {
-          const int a = q * 32 + __builtin_ctz(bits);
-          bits &= bits - 1;
-          if (a >= n_allele) continue;
-          members.push_back((uint16_t)a);
-          per_allele[(size_t)a + 1]++;
-        }
-      }
-      weight.push_back(w[u]);
-    }
-    set_off.push_back((uint32_t)(members.size() - m0));
-    for (int a = 0; a < n_allele; ++a) per_allele[(size_t)a + 1] += per_allele[a];
-    al_off.insert(al_off.end(), per_allele.begin(), per_allele.end());
-    al_sets.resize(members.size());
-    std::vector<uint32_t> at(per_allele.begin(), per_allele.end() - 1);
-    for (int u = 0; u < n_sets; ++u)
-      for (uint32_t k = set_off[(size_t)g.so_off + u]; k < set_off[(size_t)g.so_off + u + 1]; ++k)
-        al_sets[m0 + at[members[m0 + k]]++] = (uint32_t)u;       // ascending set numbers per allele
-    genes.push_back(g);
-    max_sets = std::max(max_sets, n_sets);
+    EmGene& g = EmForms::add(sets, n_sets, words, n_allele);
+    g.w_off = g.s_off = (int64_t)weight.size();
+    g.prob_off = prob_off;
+    weight.insert(weight.end(), w, w + n_sets);
   }
 };
 
@@ -578,29 +440,23 @@ struct EmHost {
 int run_em(gk_ctx* ctx, EmHost& h, int64_t n_prob, int iter_max, double diff_threshold, std::vector<double>& probs,
            std::vector<int>& iters) {
   hipStream_t st = ctx->stream;
-  std::vector<void*> temps;
-  auto take = [&](void** p, size_t bytes) -> hipError_t {
-    hipError_t e = gk_pool_malloc(ctx, p, bytes ? bytes : 16);
-    if (e == hipSuccess) temps.push_back(*p);
-    return e;
-  };
-  auto done = [&](int rc) { for (void* p : temps) gk_pool_free(ctx, p); return rc; };
+  PoolTemps temps(ctx);
   EmGene* d_genes = nullptr;
   double *d_w = nullptr, *d_scale = nullptr, *d_prob = nullptr;
   uint32_t *d_so = nullptr, *d_ao = nullptr, *d_as = nullptr;
   uint16_t* d_mem = nullptr;
   int* d_it = nullptr;
-  if (take((void**)&d_genes, h.genes.size() * sizeof(EmGene)) != hipSuccess ||
-      take((void**)&d_w, h.weight.size() * sizeof(double)) != hipSuccess ||
-      take((void**)&d_scale, h.weight.size() * sizeof(double)) != hipSuccess ||
-      take((void**)&d_so, h.set_off.size() * sizeof(uint32_t)) != hipSuccess ||
-      take((void**)&d_mem, h.members.size() * sizeof(uint16_t)) != hipSuccess ||
-      take((void**)&d_ao, h.al_off.size() * sizeof(uint32_t)) != hipSuccess ||
-      take((void**)&d_as, h.al_sets.size() * sizeof(uint32_t)) != hipSuccess ||
-      take((void**)&d_prob, (size_t)std::max<int64_t>(n_prob, 1) * sizeof(double)) != hipSuccess ||
-      take((void**)&d_it, h.genes.size() * sizeof(int)) != hipSuccess) {
+  if (temps.take((void**)&d_genes, h.genes.size() * sizeof(EmGene)) != hipSuccess ||
+      temps.take((void**)&d_w, h.weight.size() * sizeof(double)) != hipSuccess ||
+      temps.take((void**)&d_scale, h.weight.size() * sizeof(double)) != hipSuccess ||
+      temps.take((void**)&d_so, h.set_off.size() * sizeof(uint32_t)) != hipSuccess ||
+      temps.take((void**)&d_mem, h.members.size() * sizeof(uint16_t)) != hipSuccess ||
+      temps.take((void**)&d_ao, h.al_off.size() * sizeof(uint32_t)) != hipSuccess ||
+      temps.take((void**)&d_as, h.al_sets.size() * sizeof(uint32_t)) != hipSuccess ||
+      temps.take((void**)&d_prob, (size_t)std::max<int64_t>(n_prob, 1) * sizeof(double)) != hipSuccess ||
+      temps.take((void**)&d_it, h.genes.size() * sizeof(int)) != hipSuccess) {
     gk_set_error("out of device memory for the EM of a sample");
-    return done(GK_ERR_HIP);
+    return temps.done(GK_ERR_HIP);
   }
   // the sources of these copies live until the stream is waited for below
   hipMemcpyAsync(d_genes, h.genes.data(), h.genes.size() * sizeof(EmGene), hipMemcpyHostToDevice, st);
@@ -616,7 +472,7 @@ int run_em(gk_ctx* ctx, EmHost& h, int64_t n_prob, int iter_max, double diff_thr
   if (lds > 48 * 1024 &&
       hipFuncSetAttribute((const void*)em_kernel_genes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
     gk_set_error("EM: %zu bytes of LDS refused", lds);
-    return done(GK_ERR_HIP);
+    return temps.done(GK_ERR_HIP);
   }
   const EmArrays A{d_w, d_scale, d_so, d_mem, d_ao, d_as};
   GK_PROF(ctx, "em_kernel_genes", GK_KERNEL(em_kernel_genes, dim3((unsigned)h.genes.size()), dim3(kEmThreads), lds, st, d_genes, A,
@@ -627,9 +483,9 @@ int run_em(gk_ctx* ctx, EmHost& h, int64_t n_prob, int iter_max, double diff_thr
   hipMemcpyAsync(iters.data(), d_it, h.genes.size() * sizeof(int), hipMemcpyDeviceToHost, st);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
     gk_set_error("EM: %s", hipGetErrorString(hipGetLastError()));
-    return done(GK_ERR_HIP);
+    return temps.done(GK_ERR_HIP);
   }
-  return done(GK_OK);
+  return temps.done(GK_OK);
 }
 
 }  // namespace
@@ -755,13 +611,7 @@ int gk_sample_em(gk_ctx* ctx, gk_tab* tab, gk_em_job* jobs, int32_t n_jobs, int3
     std::vector<int64_t> order;
   };
   std::vector<Work> work((size_t)n_jobs);
-  std::vector<void*> temps;
-  auto take = [&](void** p, size_t bytes) -> hipError_t {
-    hipError_t e = gk_pool_malloc(ctx, p, bytes ? bytes : 16);
-    if (e == hipSuccess) temps.push_back(*p);
-    return e;
-  };
-  auto done = [&](int rc) { for (void* p : temps) gk_pool_free(ctx, p); return rc; };
+  PoolTemps temps(ctx);
   int64_t out_off = 0;
   std::vector<int64_t> prob_off((size_t)n_jobs, 0);
   for (int i = 0; i < n_jobs; ++i) {
@@ -793,18 +643,18 @@ int gk_sample_em(gk_ctx* ctx, gk_tab* tab, gk_em_job* jobs, int32_t n_jobs, int3
   EmSetsJob* d_sj = nullptr;
   const size_t o_row = tag_bytes, o_small = tag_bytes + row_bytes, table_bytes = o_small + live.size() * 16;
   if (!live.empty()) {
-    if (take((void**)&table, table_bytes) != hipSuccess || take((void**)&d_sj, live.size() * sizeof(EmSetsJob)) != hipSuccess) {
+    if (temps.take((void**)&table, table_bytes) != hipSuccess || temps.take((void**)&d_sj, live.size() * sizeof(EmSetsJob)) != hipSuccess) {
       gk_set_error("out of device memory for the candidate sets of a sample");
-      return done(GK_ERR_HIP);
+      return temps.done(GK_ERR_HIP);
     }
     for (int i : live) {
       gk_em_job& j = jobs[i];
       Work& w = work[i];
-      if (take((void**)&w.d_sets, (size_t)j.n_rows * j.words * sizeof(uint32_t)) != hipSuccess ||
-          take((void**)&w.d_out_sets, (size_t)w.cap * j.words * sizeof(uint32_t)) != hipSuccess ||
-          take((void**)&w.d_out_count, (size_t)w.cap * sizeof(uint32_t)) != hipSuccess) {
+      if (temps.take((void**)&w.d_sets, (size_t)j.n_rows * j.words * sizeof(uint32_t)) != hipSuccess ||
+          temps.take((void**)&w.d_out_sets, (size_t)w.cap * j.words * sizeof(uint32_t)) != hipSuccess ||
+          temps.take((void**)&w.d_out_count, (size_t)w.cap * sizeof(uint32_t)) != hipSuccess) {
         gk_set_error("out of device memory for the candidate sets of a gene");
-        return done(GK_ERR_HIP);
+        return temps.done(GK_ERR_HIP);
       }
     }
   }
@@ -833,33 +683,33 @@ int gk_sample_em(gk_ctx* ctx, gk_tab* tab, gk_em_job* jobs, int32_t n_jobs, int3
         hipMemsetAsync(table + o_small, 0, live.size() * 16, st) != hipSuccess ||
         gk_send(ctx, d_sj, sj.data(), sj.size() * sizeof(EmSetsJob)) != hipSuccess) {
       gk_set_error("sample EM: %s", hipGetErrorString(hipGetLastError()));
-      return done(GK_ERR_HIP);
+      return temps.done(GK_ERR_HIP);
     }
     if (seed == 0) {
       const int rc = launch_sets(ctx, tab, sj, d_sj);
-      if (rc) return done(rc);
+      if (rc) return temps.done(rc);
     } else {
       launch_hash(ctx, sj, d_sj);      // the sets stand; only their hashes are taken again
     }
     launch_verify_emit(ctx, sj, d_sj);
     for (size_t q = 0; q < live.size(); ++q)
-      if (gk_fetch_queue(ctx, work[live[q]].back, sj[q].n_out, 8) != hipSuccess) { gk_fetch_cancel(ctx); return done(GK_ERR_HIP); }
+      if (gk_fetch_queue(ctx, work[live[q]].back, sj[q].n_out, 8) != hipSuccess) { gk_fetch_cancel(ctx); return temps.done(GK_ERR_HIP); }
     if (hipGetLastError() != hipSuccess || gk_fetch_wait(ctx) != hipSuccess) {
       gk_fetch_cancel(ctx);
       gk_set_error("sample EM: %s", hipGetErrorString(hipGetLastError()));
-      return done(GK_ERR_HIP);
+      return temps.done(GK_ERR_HIP);
     }
     bool collided = false;
     for (int i : live) collided = collided || (work[i].back[1] & 2u);
     if (!collided) break;
-    if (seed == 3) { gk_set_error("candidate sets: hash collisions under four seeds"); return done(GK_ERR_ASSERT); }
+    if (seed == 3) { gk_set_error("candidate sets: hash collisions under four seeds"); return temps.done(GK_ERR_ASSERT); }
   }
   for (int i : live) {
     Work& w = work[i];
     const uint32_t n = w.back[0];
     if ((w.back[1] & 1u) || n > w.cap) {
       gk_set_error("%u distinct candidate sets exceed the capacity %u of the one-call EM", n, w.cap);
-      return done(GK_ERR_CAPACITY);
+      return temps.done(GK_ERR_CAPACITY);
     }
     if (!n) continue;
     w.sets.resize((size_t)n * jobs[i].words);
@@ -867,10 +717,10 @@ int gk_sample_em(gk_ctx* ctx, gk_tab* tab, gk_em_job* jobs, int32_t n_jobs, int3
     if (gk_fetch_queue(ctx, w.sets.data(), w.d_out_sets, w.sets.size() * sizeof(uint32_t)) != hipSuccess ||
         gk_fetch_queue(ctx, w.mult.data(), w.d_out_count, w.mult.size() * sizeof(uint32_t)) != hipSuccess) {
       gk_fetch_cancel(ctx);
-      return done(GK_ERR_HIP);
+      return temps.done(GK_ERR_HIP);
     }
   }
-  if (gk_fetch_wait(ctx) != hipSuccess) { gk_fetch_cancel(ctx); return done(GK_ERR_HIP); }
+  if (gk_fetch_wait(ctx) != hipSuccess) { gk_fetch_cancel(ctx); return temps.done(GK_ERR_HIP); }
   // ---- phase 2 (host): numpy.unique's order, the reads naming each allele, the empty set dropped, the sparse forms
   EmHost h;
   std::vector<int> gene_job;
@@ -913,18 +763,18 @@ int gk_sample_em(gk_ctx* ctx, gk_tab* tab, gk_em_job* jobs, int32_t n_jobs, int3
       gene_job.push_back(i);
     }
   }
-  if (h.genes.empty()) return done(GK_OK);
+  if (h.genes.empty()) return temps.done(GK_OK);
   // ---- phase 3: every gene's SQUAREM loop in one launch
   std::vector<double> probs;
   std::vector<int> iters;
   const int rc = run_em(ctx, h, out_off, iter_max, diff_threshold, probs, iters);
-  if (rc) return done(rc);
+  if (rc) return temps.done(rc);
   for (size_t k = 0; k < h.genes.size(); ++k) {
     const int i = gene_job[k];
     jobs[i].iterations = iters[k];
     for (int a = 0; a < jobs[i].n_allele; ++a) prob_out[prob_off[i] + a] = probs[(size_t)(prob_off[i] + a)];
   }
-  return done(GK_OK);
+  return temps.done(GK_OK);
 }
 
 }  // extern "C"

@@ -214,6 +214,41 @@ def test_solver_equals_the_oracle_beyond_the_scale_row_in_lds(device):
     sameAsOracle(sets, count, alleles, 5, prob, iters[:, 0])
 
 
+# (words, n_allele, n_sets, empty first row, a big count every ... sets): the widths of the bit sets, and the numbers of
+# sets either side of the batch kernel's scale row leaving LDS (the point kernel keeps its own there) and past the point
+# kernel's limit of 8192 (both keep it in HBM).  Every case has sets of 100 000 reads: no replicate is empty.
+SAME_SOLVER_CASES = [
+    (1, 20, 17, False, 4),
+    (2, 33, 17, True, 4),
+    (16, 512, 17, False, 4),
+    (1, 24, LDS_SCALE_SETS, False, 1000),
+    (1, 24, LDS_SCALE_SETS + 1, False, 1000),
+    (1, 24, 8193, False, 1000),
+]
+
+
+@pytest.mark.parametrize("words,n_allele,n_sets,empty_first,big_every", SAME_SOLVER_CASES)
+def test_batch_solver_is_the_point_solver(device, words, n_allele, n_sets, empty_first, big_every):
+    """boot_em_batch and em_kernel_genes instantiate one solver (csrc/gk_squarem.h) whose sums do not depend on the
+    workgroup size: a replicate's counts handed to gk_em_run as weights (sets that drew no read included: weight 0 gives
+    scale 0 in both) give the replicate's abundances and step count, bit for bit."""
+    rng = np.random.default_rng(n_sets * 37 + words)
+    sets = randomSets(rng, n_sets, words, n_allele, empty_first)
+    count = mixedCounts(rng, n_sets, big_every)
+    prob, iters, got = bootstrapEM(device, [(sets, count, n_allele, 3)], 2, SEED, want_counts=True)
+    keep = sets.any(axis=1)
+    assert keep.sum() == n_sets - empty_first
+    uniq = np.ascontiguousarray(sets[keep])
+    for b in range(2):
+        weight = np.ascontiguousarray(got[b][keep].astype(np.float64))
+        assert weight.sum() > 0
+        point, point_iters = np.zeros(n_allele, dtype=np.float64), C.c_int32(-1)
+        _lib.check(_lib.lib().gk_em_run(device.ctx, uniq.ctypes.data, weight.ctypes.data, len(uniq), words, n_allele, 300, 1e-4,
+                                        point.ctypes.data, C.byref(point_iters)))
+        assert np.array_equal(prob[b], point), b
+        assert int(iters[b, 0]) == point_iters.value, b
+
+
 def test_point_result_does_not_change(typed):
     plain, plain_calls, boot, boot_calls = typed
     assert plain.bootstrap == {} and boot_calls == plain_calls
