@@ -16,6 +16,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import threading
+from typing import NamedTuple
 
 import numpy as np
 
@@ -36,11 +38,56 @@ def searchMode() -> str:
     the exact float64 sums only for the sets that can reach the cut; ``exact``: float64 sums for every candidate
     (GK_SEARCH=exact).  Both give the reference's bits; ``bound`` falls back to ``exact`` for a step whose order
     would depend on numpy's tie order among sets it did not sum."""
-    import os
     mode = os.environ.get("GK_SEARCH", "bound")
     if mode not in ("bound", "exact"):
         raise ValueError(f"GK_SEARCH={mode!r}: expected 'bound' or 'exact'")
     return mode
+
+
+class Surviving(NamedTuple):
+    """Variants with a surviving observation, grouped by gene (ordinals ascending inside a gene, as ``survivingCounts``
+    lists them): gene ``g`` is the slice ``bounds[g]:bounds[g + 1]`` of the three arrays."""
+    ordinals: np.ndarray    # int32
+    pos: np.ndarray         # uint32 positive tallies
+    neg: np.ndarray         # uint32 negative tallies
+    bounds: np.ndarray      # int64 [genes + 1]
+
+    def ofGene(self, g: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        a, b = int(self.bounds[g]), int(self.bounds[g + 1])
+        return self.ordinals[a:b], self.pos[a:b], self.neg[a:b]
+
+
+class PreparedGene(NamedTuple):
+    """One gene's part of a ``PreparedSample``: what ``AlleleTyping(_prepared=...)`` takes."""
+    rows: DeviceBuffer      # the gene's rows that kept an id (a slice of the sample's)
+    n_rows: int
+    vflag: DeviceBuffer     # drop flags of every variant of the sample (shared)
+    tally: DeviceBuffer     # tallies of every variant of the sample (shared)
+    tally_gene: tuple[int, int, int]    # (backbone ordinal, vbeg, vend)
+    surviving: tuple[np.ndarray, np.ndarray, np.ndarray] | None = None     # ``Surviving.ofGene``, when fetched already
+
+
+class PreparedSample(NamedTuple):
+    """``Tabulation.prepared()``: every gene of a sample after error correction and removal of empty reads."""
+    vflag: DeviceBuffer     # uint8 [variants]: corrected drop flags
+    cnt: DeviceBuffer       # uint32 [2 x variants]: tallies
+    rows: DeviceBuffer      # int32: rows that kept an id, grouped by gene
+    off: np.ndarray         # int64 [genes + 1]: gene g owns rows[off[g]:off[g + 1]]
+    surviving: Surviving
+
+    def gene(self, g: int, vbeg: int, vend: int, dev: Device | None = None) -> PreparedGene:
+        a, b = int(self.off[g]), int(self.off[g + 1])
+        return PreparedGene(DeviceSlice(self.rows, a, b - a, dev), b - a, self.vflag, self.cnt, (g, vbeg, vend),
+                            self.surviving.ofGene(g))
+
+
+def _groupByGene(gene_of: np.ndarray, o: np.ndarray, p: np.ndarray, q: np.ndarray, n_genes: int) -> Surviving:
+    """Grouped by gene once: a gene's tallies are a slice, and the zygosity verdicts of all genes one native call
+    (gk_site_verdict_genes)."""
+    order = np.argsort(gene_of, kind="stable")
+    bounds = np.searchsorted(gene_of[order], np.arange(n_genes + 1)).astype(np.int64)
+    return Surviving(np.ascontiguousarray(o[order], dtype=np.int32), np.ascontiguousarray(p[order], dtype=np.uint32),
+                     np.ascontiguousarray(q[order], dtype=np.uint32), bounds)
 
 
 class DeviceIndex:
@@ -124,87 +171,66 @@ class Tabulation:
     def close(self) -> None:
         if self.handle and not getattr(self, "_borrowed", False):
             for prep in (getattr(self, "_prepared", None) or {}).values():
-                for b in prep[:3]:
+                for b in (prep.vflag, prep.cnt, prep.rows):
                     b.free()
             self._prepared = {}
             lib().gk_tab_destroy(self.handle)
         self.handle = None
 
-    def prepared(self, dev: Device, multiple: bool = False, exon: bool = False):
-        """Error correction + removal of empty reads of EVERY gene at once (``gk_sample_prepare``), computed by
-        the first caller and shared by all gene threads: (drop flags, tallies, rows grouped by gene, bounds).
+    def prepared(self, dev: Device, multiple: bool = False, exon: bool = False) -> PreparedSample | None:
+        """Error correction + removal of empty reads of EVERY gene at once (``gk_sample_prepare_all``), computed by
+        the first caller and shared by all gene threads (``PreparedSample``).
         ``exon``: the same for the EXON model of every gene (``gk_sample_prepare_exon``: ids outside the exons dropped
         from every list, the correction applied twice, typing_mulit_allele.py:640-664).
         None for tabulations that were not made by ``gk_tabulate`` (no index handle / novel keys on the device)."""
         if self.dindex is None or not self.info.d_pair_src:      # host lists / compact files: no index handle in the library
             return None
-        import threading
         root = getattr(self, "_root", self)
         lock = root.__dict__.setdefault("_prep_lock", threading.Lock())
         store = root.__dict__.setdefault("_prepared", {})
+        key = (bool(multiple), True) if exon else bool(multiple)
         with lock:
-            prep = store.get((bool(multiple), True) if exon else bool(multiple))
-            if prep is None and exon:
-                nv = max(self.n_var_total, 1)
+            prep = store.get(key)
+            if prep is None:
                 host = self.dindex.host
-                flags = np.full(nv, 3, dtype=np.uint8)           # novel variants are never in an exon
-                flags[:host.n_variant][host.in_exon.astype(bool)] = 0
-                vflag = dev.put(flags)
+                nv = max(self.n_var_total, 1)
+                if exon:
+                    flags = np.full(nv, 3, dtype=np.uint8)           # novel variants are never in an exon
+                    flags[:host.n_variant][host.in_exon.astype(bool)] = 0
+                    vflag = dev.put(flags)
+                else:
+                    vflag = dev.alloc(nv, np.uint8)
                 cnt = dev.alloc(2 * nv, np.uint32)
                 rows = dev.alloc(max(self.n_valid, 1), np.int32)
                 off = np.zeros(len(host.genes) + 1, dtype=np.int64)
                 o, p, q = (np.empty(nv, dtype=t) for t in (np.int32, np.uint32, np.uint32))
                 n_surv = C.c_int64()
-                check(lib().gk_sample_prepare_exon(dev.ctx, self.handle, int(multiple), vflag.ptr, cnt.ptr, rows.ptr,
-                                                   off.ctypes.data, nv, o.ctypes.data, p.ctypes.data, q.ctypes.data,
-                                                   C.byref(n_surv)))
+                args = (dev.ctx, self.handle, int(multiple), vflag.ptr, cnt.ptr, rows.ptr, off.ctypes.data, nv,
+                        o.ctypes.data, p.ctypes.data, q.ctypes.data, C.byref(n_surv))
+                if exon:
+                    check(lib().gk_sample_prepare_exon(*args))
+                else:
+                    # error correction, empty reads, the surviving tallies of every gene (isHomozygous reads them per gene)
+                    # and the sample's novel keys in ONE library call with two waits (six when the three were separate
+                    # calls -- each wait sits behind the long kernels of the samples typed next to this one)
+                    want_novel = self._novel_keys is None and self.n_novel > 0
+                    novel_keys = np.empty(self.n_novel, dtype=np.uint64) if want_novel else None
+                    check(lib().gk_sample_prepare_all(*args, novel_keys.ctypes.data if want_novel else None))
+                    if want_novel:
+                        self._novel_keys = root._novel_keys = novel_keys
                 o, p, q = o[:n_surv.value], p[:n_surv.value], q[:n_surv.value]
                 gene_of = np.searchsorted(host.gene_vbeg, o, side="right") - 1
-                order = np.argsort(gene_of, kind="stable")
-                bounds = np.searchsorted(gene_of[order], np.arange(len(host.genes) + 1)).astype(np.int64)
-                grouped = (np.ascontiguousarray(o[order], dtype=np.int32), np.ascontiguousarray(p[order], dtype=np.uint32),
-                           np.ascontiguousarray(q[order], dtype=np.uint32), bounds)
-                prep = store[(bool(multiple), True)] = (vflag, cnt, rows, off, grouped)
-            if prep is None:
-                nv = max(self.n_var_total, 1)
-                vflag = dev.alloc(nv, np.uint8)
-                cnt = dev.alloc(2 * nv, np.uint32)
-                rows = dev.alloc(max(self.n_valid, 1), np.int32)
-                off = np.zeros(len(self.dindex.host.genes) + 1, dtype=np.int64)
-                # error correction, empty reads, the surviving tallies of every gene (isHomozygous reads them per gene) and
-                # the sample's novel keys in ONE library call with two waits (gk_sample_prepare_all; six when the three
-                # were separate calls -- each wait sits behind the long kernels of the samples typed next to this one)
-                o, p, q = (np.empty(nv, dtype=t) for t in (np.int32, np.uint32, np.uint32))
-                n_surv = C.c_int64()
-                want_novel = self._novel_keys is None and self.n_novel > 0
-                novel_keys = np.empty(self.n_novel, dtype=np.uint64) if want_novel else None
-                check(lib().gk_sample_prepare_all(dev.ctx, self.handle, int(multiple), vflag.ptr, cnt.ptr, rows.ptr,
-                                                  off.ctypes.data, nv, o.ctypes.data, p.ctypes.data, q.ctypes.data,
-                                                  C.byref(n_surv), novel_keys.ctypes.data if want_novel else None))
-                o, p, q = o[:n_surv.value], p[:n_surv.value], q[:n_surv.value]
-                if want_novel:
-                    self._novel_keys = root._novel_keys = novel_keys
-                n_index = self.dindex.host.n_variant
-                gene_of = np.searchsorted(self.dindex.host.gene_vbeg, o, side="right") - 1
-                if len(o) and int(o[-1]) >= n_index:
-                    is_novel = o >= n_index
-                    gene_of[is_novel] = (self.novelKeys()[o[is_novel] - n_index] >> np.uint64(56)).astype(gene_of.dtype)
-                # grouped by gene once (ordinals ascending inside a gene, as survivingCounts lists them): a gene's tallies
-                # are a slice, and the zygosity verdicts of all genes one native call (gk_site_verdict_genes)
-                order = np.argsort(gene_of, kind="stable")
-                bounds = np.searchsorted(gene_of[order], np.arange(len(self.dindex.host.genes) + 1)).astype(np.int64)
-                grouped = (np.ascontiguousarray(o[order], dtype=np.int32), np.ascontiguousarray(p[order], dtype=np.uint32),
-                           np.ascontiguousarray(q[order], dtype=np.uint32), bounds)
-                prep = store[bool(multiple)] = (vflag, cnt, rows, off, grouped)
+                if not exon and len(o) and int(o[-1]) >= host.n_variant:      # a novel variant names its gene in its key
+                    is_novel = o >= host.n_variant
+                    gene_of[is_novel] = (self.novelKeys()[o[is_novel] - host.n_variant] >> np.uint64(56)).astype(gene_of.dtype)
+                prep = store[key] = PreparedSample(vflag, cnt, rows, off, _groupByGene(gene_of, o, p, q, len(host.genes)))
         return prep
 
     @staticmethod
-    def survivingOfGene(prep, g: int):
+    def survivingOfGene(prep: PreparedSample, g: int):
         """(ordinals, positive tally, negative tally) of gene ``g`` out of ``prepared()``'s sample-wide list: what
         ``survivingCounts(cnt, vflag, gene=(g, vbeg, vend))`` returns, without a device call."""
-        o, p, q, bounds = prep[4]
-        a, b = int(bounds[g]), int(bounds[g + 1])
-        return o[a:b], p[a:b], q[a:b]
+        return prep.surviving.ofGene(g)
 
     def on(self, dev: Device) -> "Tabulation":
         """The same tabulation driven from another context (stream) of the same GPU.
@@ -401,7 +427,6 @@ class LogTable:
         self.n_host_evals = 0
         self.n_known = 0          # values with a defined log10 (== the library's count)
         self.n_undefined = 0      # entries seen by the last resolve() that could not be defined yet
-        import threading
         self._lock = threading.Lock()
 
     def collect(self, buf: DeviceBuffer, n: int) -> None:

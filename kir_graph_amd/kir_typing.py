@@ -9,19 +9,26 @@ reference CLI forwards ``report`` to a factory that does not know it, main.py:19
 """
 from __future__ import annotations
 
+import contextlib
+import ctypes as C
 import json
+import os
+import sys
 import threading
-from concurrent.futures import ThreadPoolExecutor
+import time
 from typing import Any
 
 import numpy as np
 
+from . import _lib
 from ._lib import Device
-from .hisat2 import SampleData, loadReadsAndVariantsData
-from .typing_em import EmBootstrap, Hisat2AlleleResult, callsByAbundance, hisat2TypingPerGene
+from .engine import PreparedGene, PreparedSample, searchMode
+from .hisat2 import SampleData, loadCompact, loadReadsAndVariantsData
+from .typing_em import (EmBootstrap, Hisat2AlleleResult, bootstrapEM, callsByAbundance, candidateSetsDistinct,
+                        hisat2TypingPerGene, summariseBootstrap)
 from .typing_mulit_allele import (AlleleTyping, AlleleTypingExonFirst, ReadSet, StepList, isHetrozygous,
                                   sharedLogTable)
-from .utils import NumpyEncoder, logger
+from .utils import NumpyEncoder, logger, testHook, traceOn
 
 _device: Device | None = None
 
@@ -46,7 +53,6 @@ def _sample(source, dev: Device | None) -> SampleData:
     dev = dev or defaultDevice()
     with _LOAD_LOCK:
         if str(source).endswith(".npz"):     # compact side-format (hisat2.writeCompact)
-            from .hisat2 import loadCompact
             data = loadCompact(str(source), dev)
         else:
             data = SampleData.fromHost(dev, loadReadsAndVariantsData(source))
@@ -64,11 +70,15 @@ class Typing:
         raise NotImplementedError
 
     def typing(self, gene_cn: dict[str, int], min_reads_num: int = 100) -> tuple[list[str], list[str]]:
+        return self._collect(((gene, *self.typingPerGene(gene, int(cn))) for gene, cn in gene_cn.items() if cn),
+                             min_reads_num)
+
+    @staticmethod
+    def _collect(entries, min_reads_num: int) -> tuple[list[str], list[str]]:
+        """(calls of every gene in turn, genes typed on fewer than ``min_reads_num`` reads) of the (gene, calls, reads)
+        that ``entries`` yields."""
         predict_alleles, warning_genes = [], []
-        for gene, cn in gene_cn.items():
-            if not cn:
-                continue
-            alleles, reads_num = self.typingPerGene(gene, int(cn))
+        for gene, alleles, reads_num in entries:
             predict_alleles.extend(alleles)
             if reads_num < min_reads_num:
                 warning_genes.append(gene)
@@ -82,9 +92,14 @@ class Typing:
         raise NotImplementedError
 
 
-def _lib_slice(buf, offset: int, count: int, dev):
-    from ._lib import DeviceSlice
-    return DeviceSlice(buf, offset, count, dev)
+def _noCall(gene: str, cn: int = 1) -> list[str]:
+    """The call of a copy that could not be typed: the gene's name and a bare ``*``."""
+    return [gene.split("*")[0] + "*"] * cn
+
+
+def _calls(gene: str, result) -> list[str]:
+    """The best allele set of a result as calls."""
+    return [x if x != "fail" else _noCall(gene)[0] for x in result.selectBest()]
 
 
 class _GeneView:
@@ -124,6 +139,23 @@ class _GeneView:
     @property
     def n_rows(self) -> int:
         return self._select()[1]
+
+    def prepared(self, prep: PreparedSample) -> PreparedGene:
+        """The gene's part of ``Tabulation.prepared()``."""
+        return prep.gene(self.g, self.vbeg, self.vbeg + self.n_span, self.tab.dev)
+
+    def model(self, logs, prepared: PreparedGene | None = None, *, cls=AlleleTyping, variants=None, mask=None,
+              alleles=None, **varying) -> AlleleTyping:
+        """The gene's likelihood model on its prepared rows (without them: on the rows selected here, which the model
+        corrects itself).  ``variants`` / ``mask`` / ``alleles``: another model of the same span (the exon groups)."""
+        if prepared is not None:
+            reads = ReadSet(self.tab, prepared.rows, prepared.n_rows, prepared.vflag)
+            varying["_prepared"] = prepared
+        else:
+            reads = ReadSet(self.tab, self.rows, self.n_rows)
+        return cls(reads, self.variants if variants is None else variants, logs=logs, _vbeg=self.vbeg, _n_span=self.n_span,
+                   _mask=self.mask if mask is None else mask, _alleles=self.alleles if alleles is None else alleles,
+                   _novel=self.novel, **varying)
 
     def groupCache(self) -> dict:
         """Per-gene store of the exon allele groups (index-only data, computed on first use)."""
@@ -168,8 +200,6 @@ def _searchSlot():
     """Context manager that admits GK_SEARCH_SLOTS whole-sample searches of this process at a time (0 / unset: any
     number).  Two searches fill the GPU; a third next to them only lengthens all three (and the tail of a short run),
     while the preamble of the samples that wait is already done -- the next search starts the moment a slot is free."""
-    import contextlib
-    import os
     n = int(os.environ.get("GK_SEARCH_SLOTS", "0") or 0)
     if n <= 0:
         return contextlib.nullcontext()
@@ -205,8 +235,6 @@ class TypingWithPosNegAllele(_OnLane):
         return super().typing(gene_cn, min_reads_num)
 
     def _wholeSampleExonFirst(self) -> bool:
-        import os
-        from .engine import searchMode
         return (self._exon_first and not self._exon_only and os.environ.get("GK_INDEX_TABLE", "0") != "1"
                 and searchMode() == "bound")
 
@@ -221,12 +249,6 @@ class TypingWithPosNegAllele(_OnLane):
            all of them pipelined on the marks of the stream like the genes of the plain strategy.
         A gene the two calls do not cover (no exon reads: the reference falls back to the full model there; no reads at
         all; not in the index) takes the per-gene path on this thread.  Same results as ``AlleleTypingExonFirst``."""
-        import ctypes as C
-        import os
-        from . import _lib
-        from ._lib import check, lib
-        from .typing_mulit_allele import AlleleTypingExonFirst
-        from .utils import testHook
         full_tables = testHook("full_tables") is not None      # tests: the table of every allele, whatever the candidates
         tab, logs = self._context()
         udev = tab.dev.urgent()
@@ -239,71 +261,41 @@ class TypingWithPosNegAllele(_OnLane):
         views = [_GeneView(self._data, gene, self._multiple, tab=tab) for gene, _ in todo]
         verd_e = self._zygosityVerdicts(tab, prep_e, [(v.g, cn) for v, (_, cn) in zip(views, todo)])
 
-        def slice_of(prep, view):
-            vflag, cnt, rows_all, off = prep[:4]
-            a, b = int(off[view.g]), int(off[view.g + 1])
-            rows = _lib_slice(rows_all, a, b - a, tab.dev)
-            return rows, b - a, vflag, (rows, b - a, vflag, cnt, (view.g, view.vbeg, view.vbeg + view.n_span),
-                                        type(tab).survivingOfGene(prep, view.g))
-
-        def run(jobs_list, vflag):
-            jobs = (_lib.GeneJob * len(jobs_list))(*jobs_list)
-            handles = (C.c_void_p * len(jobs_list))()
-            with _searchSlot():
-                check(lib().gk_sample_search(tab.dev.ctx, None, 0, tab.handle, vflag.ptr, logs.handle, jobs, len(jobs_list),
-                                             _lib.NUMPY_ARGSORT, _lib.NUMPY_LOG10, handles))
-            return jobs, handles
-
-        def destroy(handles):
-            for h in handles:
-                if h:
-                    lib().gk_search_destroy(C.c_void_p(h))
-
         # ---- 1. the exon models
         plan: dict[int, dict] = {}             # position in todo -> what the two calls hold for the gene
         jobs1 = []
         for k, ((gene, cn), view) in enumerate(zip(todo, views)):
             if view.g is None or not view.alleles:
                 continue
-            rows_e, n_e, vflag_e, prepared_e = slice_of(prep_e, view)
-            rows_f, n_f, vflag_f, prepared_f = slice_of(prep_f, view)
-            if n_e == 0 or n_f == 0:
+            prepared_e, prepared_f = view.prepared(prep_e), view.prepared(prep_f)
+            if prepared_e.n_rows == 0 or prepared_f.n_rows == 0:
                 continue                        # the per-gene path below (the reference's fall-backs live there)
             allele_group, grouped, group_names, exon_mask = AlleleTypingExonFirst.exonGroups(
                 view.variants, view.n_span, view.groupCache(), tab.dev)
             force = False if isHetrozygous(gene) else None
-            typ_e = AlleleTyping(ReadSet(tab, rows_e, n_e, vflag_e), grouped, force_homo=force, top_n=top_n,
-                                 variant_correction=True, logs=logs, _vbeg=view.vbeg, _n_span=view.n_span, _mask=exon_mask,
-                                 _alleles=group_names, _novel=view.novel, _prepared=prepared_e, _defer_launch=True)
+            typ_e = view.model(logs, prepared_e, variants=grouped, mask=exon_mask, alleles=group_names, force_homo=force,
+                               top_n=top_n, variant_correction=True, _defer_launch=True)
             job, homo = typ_e.geneJob(cn, verd_e.get(view.g) if cn > 1 else False)
             plan[k] = {"typ_e": typ_e, "homo_e": homo, "job1": len(jobs1), "groups": allele_group,
-                       "full": (rows_f, n_f, vflag_f, prepared_f), "force": force}
+                       "full": prepared_f, "force": force}
             jobs1.append(job)
         self.tables_rewritten = self.tables_patched = 0
         self.exon_info: dict[str, dict] = {}     # per gene: exon groups, exon sets found, candidate searches run
         if jobs1:
-            jobs, handles = run(jobs1, prep_e[0])
-            try:
+            with self._searchBatch(tab, logs, prep_e.vflag, jobs1) as (jobs, handles):
                 for k, p in plan.items():
                     q = p["job1"]
                     p["typ_e"].adoptJob(jobs[q], C.c_void_p(handles[q]), todo[k][1], p["homo_e"])
-                    self.tables_rewritten += max(0, int(jobs[q].passes) - 1)
-                    self.tables_patched += int(jobs[q].patches)
-            finally:
-                destroy(handles)
         # ---- 2. the full tables and the candidate searches on them
         jobs2, keep_alive = [], []
         for k, p in plan.items():
             (gene, cn), view = todo[k], views[k]
             result = p["typ_e"].result[-1]
             result.setNameGroup(p["groups"])
-            rows_f, n_f, vflag_f, prepared_f = p["full"]
 
             def full_model(table_cols=None):
-                return AlleleTyping(ReadSet(tab, rows_f, n_f, vflag_f), view.variants, force_homo=p["force"], top_n=top_n // 5,
-                                    variant_correction=True, logs=logs, _vbeg=view.vbeg, _n_span=view.n_span, _mask=view.mask,
-                                    _alleles=view.alleles, _novel=view.novel, _prepared=prepared_f, _defer_launch=True,
-                                    _table_cols=table_cols)
+                return view.model(logs, p["full"], force_homo=p["force"], top_n=top_n // 5, variant_correction=True,
+                                  _defer_launch=True, _table_cols=table_cols)
             if not result.value.shape[0]:
                 # no exon set: the reference types the gene with the full model (typing_mulit_allele.py:757-759)
                 logger.warning("[Allele] Cannot typing with exon-only reads. Typing with exon+intron")
@@ -343,61 +335,43 @@ class TypingWithPosNegAllele(_OnLane):
                 p["cands"].append((len(jobs2), len(steps)))
                 jobs2.append(cand)
         if jobs2:
-            jobs, handles = run(jobs2, prep_f[0])
-            try:
+            with self._searchBatch(tab, logs, prep_f.vflag, jobs2) as (jobs, handles):
                 for k, p in plan.items():
                     if "job2" not in p:
                         continue
-                    q = p["job2"]
                     full = p["full_model"]
-                    full.adoptTable(jobs[q], C.c_void_p(handles[q]))
-                    self.tables_rewritten += max(0, int(jobs[q].passes) - 1)
-                    self.tables_patched += int(jobs[q].patches)
+                    full.adoptTable(jobs[p["job2"]], C.c_void_p(handles[p["job2"]]))
                     steps = full.adoptSearches([handles[qc] for qc, _ in p["cands"]])
                     merged = steps.lastSteps().sortByScoreAndEveness()          # mergeCandidates (783-793)
                     merged.print()
                     results = StepList(p["typ_e"].result, steps, [merged])
                     p["results"], p["final"] = results, merged
-            finally:
-                destroy(handles)
         # ---- calls, in the order of the copy-number table
-        predict_alleles, warning_genes = [], []
         self._result = {}
-        for k, ((gene, cn), view) in enumerate(zip(todo, views)):
-            p = plan.get(k)
-            pure_gene = gene.split("*")[0]
-            if p is None or p.get("per_gene"):
-                alleles, reads_num = self.typingPerGene(gene, cn)       # not in the index / no reads: the per-gene path
-            elif p.get("fallback"):
-                p["full_model"]._model._launchLog()                     # its table was left to a call that never came
-                res = p["full_model"].typing(cn)
-                # the reference keeps the exon-first object's (failed) result here (kir_typing.py:126): no rows of this
-                # gene in .possible.tsv, the calls from the full model
-                self._result[gene] = p["typ_e"].result
-                alleles = [x if x != "fail" else f"{pure_gene}*" for x in res.selectBest()]
-                reads_num = p["typ_e"].getReadsNum()
-            else:
-                self._result[gene] = p["results"]
-                alleles = [x if x != "fail" else f"{pure_gene}*" for x in p["final"].selectBest()]
-                reads_num = p["typ_e"].getReadsNum()
-            predict_alleles.extend(alleles)
-            if reads_num < min_reads_num:
-                warning_genes.append(gene)
+
+        def entries():
+            for k, (gene, cn) in enumerate(todo):
+                p = plan.get(k)
+                if p is None or p.get("per_gene"):
+                    yield gene, *self.typingPerGene(gene, cn)              # not in the index / no reads: the per-gene path
+                    continue
+                if p.get("fallback"):
+                    p["full_model"]._model._launchLog()                     # its table was left to a call that never came
+                    final = p["full_model"].typing(cn)
+                    # the reference keeps the exon-first object's (failed) result here (kir_typing.py:126): no rows of this
+                    # gene in .possible.tsv, the calls from the full model
+                    self._result[gene] = p["typ_e"].result
+                else:
+                    self._result[gene], final = p["results"], p["final"]
+                yield gene, _calls(gene, final), p["typ_e"].getReadsNum()
+        calls = self._collect(entries(), min_reads_num)
         self._result = {gene: self._result[gene] for gene, _ in todo if gene in self._result}
-        return predict_alleles, warning_genes
+        return calls
 
     def _wholeSample(self) -> bool:
-        import os
-        from .engine import searchMode
         return not self._exon_first and not self._exon_only and self._variant_correction and searchMode() in ("bound", "exact")
 
     def _typingWholeSample(self, gene_cn: dict[str, int], min_reads_num: int) -> tuple[list[str], list[str]]:
-        import ctypes as C
-        import os
-        from . import _lib
-        from ._lib import check, lib
-        import time
-        from .utils import traceOn
         trace = traceOn("bench")     # host timeline on stderr (tools/host_timeline.py)
         t_in = time.perf_counter()
         tab, logs = self._context()
@@ -407,7 +381,6 @@ class TypingWithPosNegAllele(_OnLane):
         if prep is None:                 # not a gk_tabulate tabulation (host lists / compact files)
             return super().typing(gene_cn, min_reads_num)
         t_prep = time.perf_counter()
-        vflag, cnt, rows_all, off = prep[:4]
         todo = [(gene, int(cn)) for gene, cn in gene_cn.items() if cn]
         entries = []                     # (gene, cn, typ or None, job, homo)
         views = [_GeneView(self._data, gene, self._multiple, tab=tab) for gene, _ in todo]
@@ -416,64 +389,59 @@ class TypingWithPosNegAllele(_OnLane):
             if view.g is None or not view.alleles:
                 entries.append((gene, cn, None, None, False))
                 continue
-            a, b = int(off[view.g]), int(off[view.g + 1])
-            rows = _lib_slice(rows_all, a, b - a, tab.dev)
-            prepared = (rows, b - a, vflag, cnt, (view.g, view.vbeg, view.vbeg + view.n_span),
-                        type(tab).survivingOfGene(prep, view.g))
-            typ = AlleleTyping(ReadSet(tab, rows, b - a, vflag), view.variants,
-                               force_homo=False if isHetrozygous(gene) else None, top_n=self._top_n,
-                               variant_correction=True, logs=logs, _vbeg=view.vbeg, _n_span=view.n_span, _mask=view.mask,
-                               _alleles=view.alleles, _novel=view.novel, _prepared=prepared, _defer_launch=True)
-            if b - a == 0:
+            prepared = view.prepared(prep)
+            typ = view.model(logs, prepared, force_homo=False if isHetrozygous(gene) else None, top_n=self._top_n,
+                             variant_correction=True, _defer_launch=True)
+            if prepared.n_rows == 0:
                 entries.append((gene, cn, typ, None, False))
                 continue
             job, homo = typ.geneJob(cn, verdicts.get(view.g) if cn > 1 else False)
             entries.append((gene, cn, typ, job, homo))
         live = [e for e in entries if e[3] is not None]
         if live:
-            jobs = (_lib.GeneJob * len(live))(*[e[3] for e in live])
-            handles = (C.c_void_p * len(live))()
-            more = (C.c_void_p * 1)()
             if trace:
-                import sys
-                import threading
                 print(f"[trace] pre {threading.get_native_id()} {t_in:.6f} {t_prep:.6f} {time.perf_counter():.6f}", file=sys.stderr, flush=True)
-            with _searchSlot():
-                check(lib().gk_sample_search(tab.dev.ctx, more, 0, tab.handle, vflag.ptr, logs.handle, jobs, len(live),
-                                             _lib.NUMPY_ARGSORT, _lib.NUMPY_LOG10, handles))
-            self.tables_rewritten = sum(max(0, int(jobs[k].passes) - 1) for k in range(len(live)))
-            self.tables_patched = sum(int(jobs[k].patches) for k in range(len(live)))
-            try:
+            self.tables_rewritten = self.tables_patched = 0
+            with self._searchBatch(tab, logs, prep.vflag, [e[3] for e in live], more=(C.c_void_p * 1)()) as (jobs, handles):
                 for k, (gene, cn, typ, _, homo) in enumerate(live):
                     typ.adoptJob(jobs[k], C.c_void_p(handles[k]), cn, homo)
-            finally:
-                for h in handles:
-                    if h:
-                        lib().gk_search_destroy(C.c_void_p(h))
-        predict_alleles, warning_genes = [], []
         self._result = {}
-        for gene, cn, typ, job, _ in entries:
-            pure_gene = gene.split("*")[0]
-            if typ is None:
-                self._result[gene] = []
-                alleles, reads_num = [f"{pure_gene}*"] * cn, 0
-            else:
+
+        def calls():
+            for gene, cn, typ, job, _ in entries:
+                if typ is None:
+                    self._result[gene] = []
+                    yield gene, _noCall(gene, cn), 0
+                    continue
                 res = typ.result[-1] if job is not None else typ.typing(cn)     # no rows: the reference's empty results
                 self._result[gene] = typ.result
-                alleles = [x if x != "fail" else f"{pure_gene}*" for x in res.selectBest()]
-                reads_num = typ.getReadsNum()
-            predict_alleles.extend(alleles)
-            if reads_num < min_reads_num:
-                warning_genes.append(gene)
-        return predict_alleles, warning_genes
+                yield gene, _calls(gene, res), typ.getReadsNum()
+        return self._collect(calls(), min_reads_num)
+
+    @contextlib.contextmanager
+    def _searchBatch(self, tab, logs, vflag, job_list: list, more=None):
+        """One ``gk_sample_search`` call over ``job_list`` (``GeneJob``s; ``vflag``: the drop flags of the prepared sample
+        they belong to) inside a search slot: yields (the jobs as the library left them, the handles of their searches),
+        counts the tables the call wrote again or patched, and destroys the handles on the way out."""
+        jobs = (_lib.GeneJob * len(job_list))(*job_list)
+        handles = (C.c_void_p * len(job_list))()
+        try:
+            with _searchSlot():
+                _lib.check(_lib.lib().gk_sample_search(tab.dev.ctx, more, 0, tab.handle, vflag.ptr, logs.handle, jobs, len(jobs),
+                                                       _lib.NUMPY_ARGSORT, _lib.NUMPY_LOG10, handles))
+            self.tables_rewritten += sum(max(0, int(j.passes) - 1) for j in jobs)    # a job on another job's table has none
+            self.tables_patched += sum(int(j.patches) for j in jobs)
+            yield jobs, handles
+        finally:
+            for h in handles:
+                if h:
+                    _lib.lib().gk_search_destroy(C.c_void_p(h))
 
     @staticmethod
     def _zygosityVerdicts(tab, prep, wanted: list[tuple[int | None, int]]) -> dict[int, bool]:
         """isHomozygous (typing_mulit_allele.py:807-857) of every listed (backbone ordinal, cn) in ONE native call on the
         sample's grouped tallies (``gk_site_verdict_genes``); a gene is asked once per sample."""
-        import ctypes as C
-        from ._lib import check, lib
-        o, p, q, bounds = prep[4]
+        o, p, q, bounds = prep.surviving
         tables = tab.labelTables()
         if tables is None:
             return {}
@@ -483,7 +451,7 @@ class TypingWithPosNegAllele(_OnLane):
             if g is not None:
                 cn[g] = c
         out = np.zeros(len(cn), dtype=np.int32)
-        check(lib().gk_site_verdict_genes(keys_all.ctypes.data, len(keys_all), ins_code.ctypes.data, len(ins_code),
+        _lib.check(_lib.lib().gk_site_verdict_genes(keys_all.ctypes.data, len(keys_all), ins_code.ctypes.data, len(ins_code),
                                           o.ctypes.data, p.ctypes.data, q.ctypes.data, bounds.ctypes.data, len(cn),
                                           cn.ctypes.data, out.ctypes.data))
         return {g: bool(out[g]) for g, c in wanted if g is not None and c > 1}
@@ -493,40 +461,23 @@ class TypingWithPosNegAllele(_OnLane):
         force_homo = False if isHetrozygous(gene) else None
         tab, logs = self._context()
         view = _GeneView(self._data, gene, self._multiple, tab=tab)
-        pure_gene = gene.split("*")[0]
         if view.g is None or not view.alleles:
             # gene absent from the sample's variants: the reference yields "fail" calls (or crashes
             # in createHomoResult for cn >= 2 with automatic zygosity; soft-fail here)
             self._result[gene] = []
-            return [f"{pure_gene}*"] * cn, 0
+            return _noCall(gene, cn), 0
         if not self._exon_first and not self._exon_only:
+            # error correction and empty-read removal were done for every gene of the sample in one go, where they can be
             prep = tab.prepared(tab.dev, self._multiple) if self._variant_correction else None
-            if prep is not None:
-                # error correction and empty-read removal were done for every gene of the sample in one go
-                vflag, cnt, rows_all, off = prep[:4]
-                a, b = int(off[view.g]), int(off[view.g + 1])
-                rows = _lib_slice(rows_all, a, b - a, tab.dev)
-                reads = ReadSet(tab, rows, b - a, vflag)
-                prepared = (rows, b - a, vflag, cnt, (view.g, view.vbeg, view.vbeg + view.n_span),
-                            type(tab).survivingOfGene(prep, view.g))
-            else:
-                reads, prepared = ReadSet(tab, view.rows, view.n_rows), None
-            typ: AlleleTyping = AlleleTyping(
-                reads, view.variants, force_homo=force_homo, top_n=self._top_n,
-                variant_correction=self._variant_correction, logs=logs, _vbeg=view.vbeg,
-                _n_span=view.n_span, _mask=view.mask, _alleles=view.alleles, _novel=view.novel, _defer_log=True,
-                _prepared=prepared)
+            typ = view.model(logs, view.prepared(prep) if prep is not None else None, force_homo=force_homo,
+                             top_n=self._top_n, variant_correction=self._variant_correction, _defer_log=True)
         else:
-            reads = ReadSet(tab, view.rows, view.n_rows)
-            typ = AlleleTypingExonFirst(
-                reads, view.variants, force_homo=force_homo, top_n=self._top_n, exon_only=self._exon_only,
-                candidate_set_threshold=self._exon_candidate_threshold, logs=logs, _vbeg=view.vbeg,
-                _n_span=view.n_span, _mask=view.mask, _alleles=view.alleles, _exon_flags=view.exonFlags(),
-                _novel=view.novel, _group_cache=view.groupCache())
+            typ = view.model(logs, cls=AlleleTypingExonFirst, force_homo=force_homo, top_n=self._top_n,
+                             exon_only=self._exon_only, candidate_set_threshold=self._exon_candidate_threshold,
+                             _exon_flags=view.exonFlags(), _group_cache=view.groupCache())
         res = typ.typing(cn)
         self._result[gene] = typ.result
-        alleles = [a if a != "fail" else f"{pure_gene}*" for a in res.selectBest()]
-        return alleles, typ.getReadsNum()
+        return _calls(gene, res), typ.getReadsNum()
 
     def getAllPossibleTyping(self) -> list[dict[Any, Any]]:
         rows = []
@@ -560,10 +511,6 @@ class TypingWithReport(_OnLane):
         gene in ONE library call on one host thread and one stream (a workgroup per gene solves its EM), instead of a
         thread and a stream per gene with three waits each.  A gene with more than 2^18 distinct candidate sets sends the
         sample to the per-gene calls (``typingPerGene``: they size for it).  Same reports either way (kir_typing.py:163-195)."""
-        import ctypes as C
-        import os
-        from . import _lib
-        from ._lib import lib
         tab, _ = self._context()
         todo = [(gene, int(cn)) for gene, cn in gene_cn.items() if cn]
         views = [_GeneView(self._data, gene, multiple=False, tab=tab) for gene, _ in todo]
@@ -577,7 +524,7 @@ class TypingWithReport(_OnLane):
                                      vend=v.vbeg + v.n_span, words=t.words, n_allele=len(v.alleles), n_distinct=0, iterations=0)
             total = sum(len(views[k].alleles) for k in live)
             prob, count = np.zeros(total, dtype=np.float64), np.zeros(total, dtype=np.int64)
-            rc = lib().gk_sample_em(tab.dev.ctx, tab.handle, jobs, len(live), 300, 0.0001, prob.ctypes.data, count.ctypes.data)
+            rc = _lib.lib().gk_sample_em(tab.dev.ctx, tab.handle, jobs, len(live), 300, 0.0001, prob.ctypes.data, count.ctypes.data)
             if rc == -5:                    # GK_ERR_CAPACITY: a gene with a flood of distinct sets -- the per-gene calls size for it
                 return super().typing(gene_cn, min_reads_num)
             _lib.check(rc)
@@ -593,18 +540,12 @@ class TypingWithReport(_OnLane):
                 at += len(names)
                 reports[k] = [Hisat2AlleleResult(allele=names[a], count=int(c[a]), prob=float(p[a])) for a in np.nonzero(c)[0]]
                 self.em_info[todo[k][0]] = {"iterations": int(jobs[q].iterations), "distinct_sets": int(jobs[q].n_distinct)}
-        predict_alleles, warning_genes = [], []
         self._result = {}
-        point_calls = {}
-        for k, (gene, cn) in enumerate(todo):
-            alleles, reads_num = self._callsOfReport(gene, cn, reports.get(k, []), views[k].n_rows if views[k].g is not None else 0)
-            point_calls[k] = alleles
-            predict_alleles.extend(alleles)
-            if reads_num < min_reads_num:
-                warning_genes.append(gene)
+        point = [self._callsOfReport(gene, cn, reports.get(k, []), views[k].n_rows if views[k].g is not None else 0)
+                 for k, (gene, cn) in enumerate(todo)]
         if self._n_boot > 0:
-            self._bootstrapGenes(tab, [(todo[k][0], todo[k][1], views[k], point_calls[k]) for k in live])
-        return predict_alleles, warning_genes
+            self._bootstrapGenes(tab, [(todo[k][0], todo[k][1], views[k], point[k][0]) for k in live])
+        return self._collect(((gene, *point[k]) for k, (gene, _) in enumerate(todo)), min_reads_num)
 
     def typingPerGene(self, gene: str, cn: int) -> tuple[list[str], int]:
         tab, _ = self._context()
@@ -625,7 +566,6 @@ class TypingWithReport(_OnLane):
         """The read bootstrap of the listed (gene, cn, view, point call) in ONE ``gk_em_bootstrap`` call: the distinct
         candidate sets of every gene that has a report (``candidateSetsDistinct``), its replicates drawn on the stream
         numbered like the gene in the index -- so a gene's replicates are the same whichever genes are typed with it."""
-        from .typing_em import bootstrapEM, candidateSetsDistinct, summariseBootstrap
         genes = [e for e in genes if self._result.get(e[0])]
         if not genes:
             return
@@ -644,10 +584,9 @@ class TypingWithReport(_OnLane):
 
     def _callsOfReport(self, gene: str, cn: int, report: list, n_rows: int) -> tuple[list[str], int]:
         """Abundances -> calls (kir_typing.py:181-192): the copy numbers go to the alleles in descending abundance."""
-        pure_gene = gene.split("*")[0]
         if not report:
             self._result[gene] = report
-            return [f"{pure_gene}*"] * cn, n_rows   # the reference raises AxisError here
+            return _noCall(gene, cn), n_rows   # the reference raises AxisError here
         # descending abundance; ties by allele name (the reference leaves them to set order)
         called, order, pred = callsByAbundance([r.allele for r in report], [r.prob for r in report], cn)
         report[:] = [report[i] for i in order]

@@ -337,7 +337,7 @@ class NovelDiscovery:
         typing made them, otherwise one pass over the gene's rows."""
         prep = self.tab.prepared(self.dev, False)
         if prep is not None:
-            return prep[0]
+            return prep.vflag
         vflag = self.dev.alloc(max(self.tab.n_var_total, 1), np.uint8).zero()
         self.tab.errorCorrection(rows, n, vflag, span=(vbeg, vend))
         return vflag

@@ -29,7 +29,7 @@ import threading
 import numpy as np
 
 from ._lib import Device, DeviceBuffer
-from .engine import DeviceModel, LogTable, Tabulation
+from .engine import DeviceModel, LogTable, PreparedGene, Tabulation
 from .index import buildMask
 from .msa2hisat import Variant
 from .utils import logger
@@ -455,10 +455,10 @@ class AlleleTyping:
                  no_empty: bool = True, variant_correction: bool = True, *, device: Device | None = None,
                  logs: LogTable | None = None, _vbeg: int = 0, _n_span: int | None = None,
                  _mask: DeviceBuffer | None = None, _alleles: list[str] | None = None, _defer_log: bool = False,
-                 _novel=None, _prepared: tuple | None = None, _defer_launch: bool = False,
+                 _novel=None, _prepared: PreparedGene | None = None, _defer_launch: bool = False,
                  _table_cols: np.ndarray | None = None):
-        """``_prepared`` = (rows with a surviving id, their count, shared drop flags, shared tallies, (gene, vbeg, vend)):
-        error correction and removal of empty reads already done for the whole sample (``Tabulation.prepared``).
+        """``_prepared`` (``engine.PreparedGene``, or its six fields as a plain tuple): error correction and removal of
+        empty reads already done for the whole sample (``Tabulation.prepared``, ``PreparedSample.gene``).
         ``_defer_launch``: the tables are allocated, not written -- ``gk_sample_search`` writes them and runs the
         search together with the sample's other genes (``kir_typing.TypingWithPosNegAllele``).  ``_table_cols`` (with
         ``_defer_launch``): the tables hold these allele ordinals only (``engine.DeviceModel``)."""
@@ -490,8 +490,9 @@ class AlleleTyping:
         self._surviving = None
         if _prepared is not None:
             assert variant_correction and no_empty
-            rows, n_rows, _, self._tally, self._tally_gene = _prepared[:5]   # rs.vflag IS the shared, corrected one
-            self._surviving = _prepared[5] if len(_prepared) > 5 else None      # this gene's surviving tallies, if fetched already
+            pg = PreparedGene(*_prepared)                      # its vflag IS rs.vflag: the shared, corrected one
+            rows, n_rows, self._tally, self._tally_gene = pg.rows, pg.n_rows, pg.tally, pg.tally_gene
+            self._surviving = pg.surviving                     # this gene's surviving tallies, if fetched already
         else:
             if variant_correction:
                 self._tally = tab.errorCorrection(rs.rows, rs.n_rows, rs.vflag, span=self._span, keep=True)

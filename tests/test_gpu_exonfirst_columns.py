@@ -144,7 +144,7 @@ def _tableAndSearch(device, seed: int, allele_range, n_pairs: int):
     from kir_graph_amd.hisat2 import SampleData
     from kir_graph_amd.index import GkIndex
     from kir_graph_amd.kir_typing import _GeneView
-    from kir_graph_amd.typing_mulit_allele import AlleleTyping, ReadSet, sharedLogTable
+    from kir_graph_amd.typing_mulit_allele import sharedLogTable
     from kir_graph_amd import synth
     sidx = synth.makeIndex(seed=seed, n_genes=1, var_range=(80, 120), allele_range=allele_range, len_range=(2500, 3000))
     gene = sidx.genes[0]
@@ -157,17 +157,14 @@ def _tableAndSearch(device, seed: int, allele_range, n_pairs: int):
     logs = sharedLogTable(device)
     prep = tab.prepared(device, False)
     assert prep is not None
-    vflag, cnt, rows_all, off = prep[:4]
+    vflag = prep.vflag
     view = _GeneView(data, gene, False, tab=tab)
     n_allele = len(view.alleles)
-    a, b = int(off[view.g]), int(off[view.g + 1])
-    rows = _lib.DeviceSlice(rows_all, a, b - a, device)
-    prepared = (rows, b - a, vflag, cnt, (view.g, view.vbeg, view.vbeg + view.n_span), type(tab).survivingOfGene(prep, view.g))
+    prepared = view.prepared(prep)
 
     def run(table_cols, offered):
-        full = AlleleTyping(ReadSet(tab, rows, b - a, vflag), view.variants, force_homo=False, top_n=10, variant_correction=True,
-                            logs=logs, _vbeg=view.vbeg, _n_span=view.n_span, _mask=view.mask, _alleles=view.alleles,
-                            _novel=view.novel, _prepared=prepared, _defer_launch=True, _table_cols=table_cols)
+        full = view.model(logs, prepared, force_homo=False, top_n=10, variant_correction=True, _defer_launch=True,
+                          _table_cols=table_cols)
         job, _ = full.geneJob(2, False)
         job.n_steps = 0
         cols = np.array(offered, dtype=np.int32)
