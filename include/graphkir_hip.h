@@ -496,6 +496,22 @@ int gk_em_bootstrap(gk_ctx* ctx, const gk_boot_job* jobs, int32_t n_jobs, int32_
                     int32_t* iters_out,    /* [n_boot][n_jobs] */
                     uint32_t* counts_out); /* nullable: [n_boot][sum n_sets], the replicate weights */
 
+/* Read bootstrap of a likelihood call (no reference counterpart; extends typing_mulit_allele.py:540-542, 569): a replicate
+ * rescores the candidate sets the point search ranked with resampled read weights -- no search runs again.
+ * gk_boot_row_counts: d_W uint32 [n_boot][ldw] (ldw >= n_rows): d_W[b][r] = draws of replicate boot_first + b on row r,
+ *   out of n_rows draws with the generator of gk_em_bootstrap above (draw i falls on row j).  The call zeroes the n_rows
+ *   used entries of every row first; entries r >= n_rows are not touched.  Queued on the context's stream.
+ *   1 <= n_rows < 2^31, 1 <= n_boot <= 10000, boot_first >= 0. */
+int gk_boot_row_counts(gk_ctx* ctx, int64_t n_rows, int32_t n_boot, int32_t boot_first, uint64_t seed, uint32_t stream,
+                       gk_dptr d_W, int64_t ldw);
+/* gk_weighted_sums (extends typing_mulit_allele.py:540-542: the read reduction of a set's per-read maximum, weighted):
+ *   out[b * n_sets + t] = sum_r d_W[b][r] * d_V[t][r], r < n_rows.  d_V double [n_sets][ld] (gk_setmax's output, line 569).
+ *   The sum has a FIXED order: the same bits on every run and for every n_boot / n_sets the pair (b, t) appears in.
+ *   Entries r >= n_rows of either table are never read.  1 <= n_sets <= 256, 1 <= n_boot <= 10000; GK_ERR_CAPACITY when
+ *   n_rows / 4096 * n_boot * n_sets exceeds 2^28 (pass the replicates in slices). */
+int gk_weighted_sums(gk_ctx* ctx, gk_dptr d_V, int64_t ld, int64_t n_rows, int32_t n_sets, gk_dptr d_W, int64_t ldw,
+                     int32_t n_boot, double* out);
+
 /* ---- host ingest (no GPU): name-collated SAM text -> gk_mate records.
  * Native form of readPair (hisat2.py:228-276), of the field reads of filterRead / getNH (551-569,
  * 95-100) and of the CIGAR / MD / Zs consistency checks of recordToRawVariant (279-515).  Text is fed

@@ -262,6 +262,10 @@ _SIGS = {
                             C.c_double, C.c_void_p, C.POINTER(C.c_int32)]),
     "gk_em_bootstrap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_double,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gk_boot_row_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_uint64,
+                                     C.c_int64]),
+    "gk_weighted_sums": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, C.c_int64, C.c_int32,
+                                   C.c_void_p]),
 }
 
 EXPORTED = sorted(_SIGS)

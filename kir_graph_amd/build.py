@@ -10,7 +10,7 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 SOURCES = ["gk_runtime.hip", "gk_scan.hip", "gk_tabulate.hip", "gk_typing.hip", "gk_lut.hip",
            "gk_search.hip", "gk_bound.hip", "gk_em.hip", "gk_cn.hip", "gk_depth.hip", "gk_sampack.cpp", "gk_bamread.cpp", "gk_textout.cpp",
-           "gk_comm.cpp", "gk_hostsearch.cpp", "gk_novel.hip", "gk_boot.hip"]
+           "gk_comm.cpp", "gk_hostsearch.cpp", "gk_novel.hip", "gk_boot.hip", "gk_callboot.hip"]
 
 
 def hipcc() -> str:
@@ -61,6 +61,9 @@ KERNEL_SOURCES = {
     "novel_compact": ["gk_novel.hip", "gk_common.h"],
     "boot_resample": ["gk_boot.hip", "gk_common.h"],
     "boot_em_batch": ["gk_boot.hip", "gk_squarem.h", "gk_common.h"],
+    "callboot_draw": ["gk_callboot.hip", "gk_common.h"],
+    "callboot_sums": ["gk_callboot.hip", "gk_common.h"],
+    "callboot_fold": ["gk_callboot.hip", "gk_common.h"],
 }
 
 

@@ -703,6 +703,24 @@ class DeviceModel:
                                 ids.shape[1], out.ctypes.data))
         return out
 
+    def tableFor(self, ids: np.ndarray) -> tuple[DeviceBuffer, int, np.ndarray]:
+        """(the float64 table the search left in HBM, its leading dimension, ``ids`` as column numbers of that table).
+        A model whose table holds a list of alleles (``table_cols``) hands out THAT table and translates the ordinals --
+        never the all-allele table ``L`` would write; an allele the table does not hold is an error.  Only a model that
+        holds the index form alone goes through ``L``."""
+        ids = np.asarray(ids, dtype=np.int64)
+        self.finishLog()
+        if self._L is None:
+            return self.L, self.n_rows, _i32(ids)
+        cols = self._table_cols
+        if cols is None:
+            return self._L, self.n_rows, _i32(ids)
+        at = np.minimum(np.searchsorted(cols, ids), len(cols) - 1)
+        if not np.array_equal(cols[at], ids):
+            missing = np.unique(ids[cols[at] != ids])[:8].tolist()
+            raise KeyError(f"alleles {missing} are not among the {len(cols)} columns of this model's table")
+        return self._L, self.n_rows, _i32(at)
+
     def setmax(self, ids: np.ndarray) -> np.ndarray:
         """Host copy of allele_prob (R x T) for the given sets -- API parity only, not on the hot path."""
         ids = _i32(ids)

@@ -22,6 +22,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Device
+from .call_bootstrap import MAX_BOOT, MAX_TOP, CallBootstrap, bootstrapCall, homoFactor
 from .engine import PreparedGene, PreparedSample, searchMode
 from .hisat2 import SampleData, loadCompact, loadReadsAndVariantsData
 from .typing_em import (EmBootstrap, Hisat2AlleleResult, bootstrapEM, callsByAbundance, candidateSetsDistinct,
@@ -215,8 +216,18 @@ class TypingWithPosNegAllele(_OnLane):
 
     def __init__(self, filename_variant_json, top_n: int = 300, multiple: bool = False, exon_first: bool = False,
                  exon_only: bool = False, exon_candidate_threshold: float = .9, variant_correction: bool = False,
-                 device: Device | None = None):
+                 device: Device | None = None, call_bootstrap: int = 0, call_bootstrap_seed: int = 2022,
+                 call_bootstrap_top: int = 32):
+        """``call_bootstrap`` > 0: every gene's adopted result is rescored in that many read-bootstrap replicates
+        (``call_bootstrap.bootstrapCall`` on its first ``call_bootstrap_top`` candidate sets; ``self.call_bootstrap``:
+        gene -> ``CallBootstrap``); 0: nothing but the point result, and nothing more is launched."""
         super().__init__()
+        if not 0 <= int(call_bootstrap) <= MAX_BOOT:
+            raise ValueError(f"call_bootstrap: the number of replicates must lie in 0 .. {MAX_BOOT}")
+        if not 1 <= int(call_bootstrap_top) <= MAX_TOP:
+            raise ValueError(f"call_bootstrap_top: the candidate sets kept must lie in 1 .. {MAX_TOP}")
+        self._call_boot = (int(call_bootstrap), int(call_bootstrap_seed), int(call_bootstrap_top))
+        self.call_bootstrap: dict[str, CallBootstrap] = {}
         self._data = _sample(filename_variant_json, device)
         self._multiple = multiple
         self._top_n = top_n
@@ -363,6 +374,7 @@ class TypingWithPosNegAllele(_OnLane):
                     self._result[gene] = p["typ_e"].result
                 else:
                     self._result[gene], final = p["results"], p["final"]
+                self._bootstrapCall(gene, cn, final)
                 yield gene, _calls(gene, final), p["typ_e"].getReadsNum()
         calls = self._collect(entries(), min_reads_num)
         self._result = {gene: self._result[gene] for gene, _ in todo if gene in self._result}
@@ -415,6 +427,7 @@ class TypingWithPosNegAllele(_OnLane):
                     continue
                 res = typ.result[-1] if job is not None else typ.typing(cn)     # no rows: the reference's empty results
                 self._result[gene] = typ.result
+                self._bootstrapCall(gene, cn, res)
                 yield gene, _calls(gene, res), typ.getReadsNum()
         return self._collect(calls(), min_reads_num)
 
@@ -477,7 +490,24 @@ class TypingWithPosNegAllele(_OnLane):
                              _exon_flags=view.exonFlags(), _group_cache=view.groupCache())
         res = typ.typing(cn)
         self._result[gene] = typ.result
+        self._bootstrapCall(gene, cn, res)
         return _calls(gene, res), typ.getReadsNum()
+
+    def _bootstrapCall(self, gene: str, cn: int, result) -> None:
+        """With ``call_bootstrap`` > 0: the read bootstrap of the result just adopted for ``gene`` (while the sample's
+        tables are in HBM), its replicates drawn on the stream numbered like the gene in the index -- so they are the
+        same whichever genes are typed with it, and whichever driver path typed it.  A gene without rows, with a failed
+        result or with ``cn == 0`` gets no entry."""
+        n_boot, seed, top = self._call_boot
+        if n_boot <= 0:
+            return
+        self.call_bootstrap.pop(gene, None)
+        g = self._data.index.gene_id.get(gene)
+        if cn <= 0 or g is None or result is None or result.isFail():
+            return
+        boot = bootstrapCall(result, homoFactor(result), n_boot, seed, g, top)
+        if boot is not None:
+            self.call_bootstrap[gene] = boot
 
     def getAllPossibleTyping(self) -> list[dict[Any, Any]]:
         rows = []
@@ -606,6 +636,12 @@ def selectKirTypingModel(method: str, filename_variant_json, **kwargs: Any) -> T
         kwargs.pop("bootstrap_seed", None)
         if kwargs.pop("bootstrap", 0):
             raise ValueError(f"bootstrap: only the em / report strategy has a read bootstrap, not {method!r}")
+    else:
+        # ... and the rescoring of candidate sets to the likelihood strategies (the EM has its --em-bootstrap)
+        kwargs.pop("call_bootstrap_seed", None)
+        kwargs.pop("call_bootstrap_top", None)
+        if kwargs.pop("call_bootstrap", 0):
+            raise ValueError(f"call_bootstrap: only the likelihood strategies rescore candidate sets, not {method!r}")
     if method in ("full", "pv"):
         return TypingWithPosNegAllele(filename_variant_json, **kwargs)
     if method.startswith("pv_exonfirst"):

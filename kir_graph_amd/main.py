@@ -246,6 +246,16 @@ def writeConfidence(name: str, bootstrap: dict) -> str:
     return name + ".confidence.tsv"
 
 
+def writeCallConfidence(name: str, bootstrap: dict) -> str:
+    """``{name}.call_confidence.tsv`` of one sample typed by a likelihood strategy with ``--call-bootstrap``: per
+    candidate set of every gene its point value, the share of replicates it wins and the replicates' mean / 2.5 % /
+    97.5 % distance to the called set (``call_bootstrap.callConfidenceText``)."""
+    from .call_bootstrap import callConfidenceText
+    with open(name + ".call_confidence.tsv", "w") as f:
+        f.write(callConfidenceText(bootstrap))
+    return name + ".call_confidence.tsv"
+
+
 def discoverAfterTyping(typer, called_alleles: list[str], name: str, result: str, index_ref: str) -> None:
     """Novel-variant discovery of one typed sample, on its tabulation in HBM (novel_discover.discoverSample):
     ``{result}.novel.variant.tsv / .tsv / .fa / .bam / .txt``, the reads piled up from ``{name}.no_multi.bam``."""
@@ -260,14 +270,17 @@ def discoverAfterTyping(typer, called_alleles: list[str], name: str, result: str
 
 
 def sampleTyper(method: str, release: bool = True, novel_index: str | None = None, bootstrap: int = 0,
-                bootstrap_seed: int = 2022) -> "cohort.SampleTyper":
+                bootstrap_seed: int = 2022, call_bootstrap: int = 0, call_bootstrap_seed: int = 2022,
+                call_bootstrap_top: int = 32) -> "cohort.SampleTyper":
     """The typing stage of this process (``cohort.SampleTyper``: the sample lanes, search slots, urgent preamble and
     blocking waits that ``bench.py`` measures), finishing every sample the reference's way: its two files written, its
     tabulation released.  Submit ``(SampleData or hand-off file, copy numbers, (name, cn_file))``.
     ``novel_index`` (``--novel-discovery``): the index prefix; every typed sample then goes through novel_discover.py
     (``{result}.novel.*``, typingNovelWrap of the reference's research/kg_main.py) before its tabulation is released.
     ``bootstrap`` > 0 (``--em-bootstrap``, EM strategy): the typer also runs that many read-bootstrap replicates and the
-    finish step writes ``{result}.confidence.tsv``."""
+    finish step writes ``{result}.confidence.tsv``.
+    ``call_bootstrap`` > 0 (``--call-bootstrap``, likelihood strategies): the typer rescores every gene's candidate sets
+    in that many read-bootstrap replicates and the finish step writes ``{result}.call_confidence.tsv``."""
     def finish(typer, called_alleles, warning_genes, item):
         name, cn_file, source = item
         result = name + typingSuffix(name, cn_file, method)
@@ -286,9 +299,14 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
             written = writeTyping(result, typer, called_alleles, warning_genes)
             if bootstrap > 0:
                 writeConfidence(result, typer.bootstrap)
+            if call_bootstrap > 0:
+                writeCallConfidence(result, typer.call_bootstrap)
         return written
 
     extra = {"bootstrap": bootstrap, "bootstrap_seed": bootstrap_seed} if bootstrap > 0 else {}
+    if call_bootstrap > 0:
+        extra.update(call_bootstrap=call_bootstrap, call_bootstrap_seed=call_bootstrap_seed,
+                     call_bootstrap_top=call_bootstrap_top)
     return cohort.SampleTyper(method, finish=finish, **extra)
 
 
@@ -369,11 +387,32 @@ def createParser() -> argparse.ArgumentParser:
                    help="EM strategy only: this many read-bootstrap replicates per gene after typing; writes "
                         "{result}.confidence.tsv (abundance spread per allele, support of the call)")
     p.add_argument("--em-bootstrap-seed", type=int, default=2022, help="Seed of the bootstrap draws")
+    p.add_argument("--call-bootstrap", type=int, default=None,
+                   help="Likelihood strategies (full / pv / exonfirst) only: rescore every gene's candidate sets in this "
+                        "many read-bootstrap replicates after typing; writes {result}.call_confidence.tsv (share of "
+                        "replicates each candidate wins, spread of its distance to the called set)")
+    p.add_argument("--call-bootstrap-seed", type=int, default=2022, help="Seed of the call bootstrap's draws")
+    p.add_argument("--call-bootstrap-top", type=int, default=32,
+                   help="Candidate sets of a gene the call bootstrap rescores (1 .. 256, in rank order)")
     p.add_argument("--ranks", type=int, default=1,
                    help="Start this many rank processes (samples are sharded over them; ranks map to GPUs round robin, "
                         "so 3 x the GPU count keeps every GPU busy).  Not needed under torchrun / any launcher that "
                         "sets RANK and WORLD_SIZE.")
     return p
+
+
+def _callBootstrapArgs(args: argparse.Namespace) -> dict:
+    """The ``sampleTyper`` keywords of ``--call-bootstrap`` (none when the flag is not given); a count that is not
+    positive, a ``--call-bootstrap-top`` outside 1 .. 256 or the EM strategy is an error."""
+    n = getattr(args, "call_bootstrap", None)
+    if n is None:
+        return {}
+    top = int(getattr(args, "call_bootstrap_top", 32))
+    if int(n) <= 0 or int(n) > 10000 or not 1 <= top <= 256 or args.allele_strategy in ("em", "report"):
+        raise ValueError("--call-bootstrap needs a count in 1 .. 10000, a --call-bootstrap-top in 1 .. 256 and a likelihood "
+                         "strategy (--allele-strategy full, pv or exonfirst)")
+    return {"call_bootstrap": int(n), "call_bootstrap_seed": int(getattr(args, "call_bootstrap_seed", 2022)),
+            "call_bootstrap_top": top}
 
 
 def main(args: argparse.Namespace) -> None:
@@ -391,6 +430,7 @@ def main(args: argparse.Namespace) -> None:
     n_boot = int(getattr(args, "em_bootstrap", 0) or 0)
     if n_boot < 0 or (n_boot > 0 and args.allele_strategy not in ("em", "report")):
         raise ValueError("--em-bootstrap needs a positive count and --allele-strategy em (or report)")
+    _callBootstrapArgs(args)
 
     if not args.input_csv:
         if not args.r1 and not args.alignment:
@@ -463,7 +503,7 @@ def _runCohort(args, names, reads, cn_files, index, index_ref, cohort_name, comm
     pooled_fit = args.cn_cohort and not all(cn_files)
     novel = getattr(args, "novel_discovery", False)
     lanes = sampleTyper(method, novel_index=index_ref if novel else None, bootstrap=int(getattr(args, "em_bootstrap", 0) or 0),
-                        bootstrap_seed=int(getattr(args, "em_bootstrap_seed", 2022)))
+                        bootstrap_seed=int(getattr(args, "em_bootstrap_seed", 2022)), **_callBootstrapArgs(args))
     try:
         allele_files, my_cn = _typeShare(args, lanes, pick(names), pick(reads), my_cn, pick, index, index_ref, cohort_name,
                                          comm, kwargs, pooled_fit)

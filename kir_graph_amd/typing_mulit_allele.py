@@ -76,7 +76,8 @@ class TypingResult:
     def isFail(self) -> bool:
         return not len(self.value)
 
-    def selectBest(self, filter_fraction: bool = True, filter_minor: bool = False) -> list[str]:
+    def bestRank(self, filter_fraction: bool = True, filter_minor: bool = False) -> int:
+        """The row ``selectBest`` picks: the first one that passes the filters, row 0 when none does."""
         ids: Iterable[int] = range(len(self.fraction))
         if filter_fraction and len(self.fraction):
             floor = (1 / self.n) / 2
@@ -84,7 +85,10 @@ class TypingResult:
         if filter_minor:
             ids = [i for i in ids
                    if np.abs(self.value_sum_indv[i]).min() / np.abs(self.value_sum_indv[i]).max() > 0.8]
-        best = (list(ids) or [0])[0]
+        return (list(ids) or [0])[0]
+
+    def selectBest(self, filter_fraction: bool = True, filter_minor: bool = False) -> list[str]:
+        best = self.bestRank(filter_fraction, filter_minor)
         if not self.isFail():
             logger.debug(f"[Allele] Select best rank: {best}")
             assert len(self.allele_name[best]) == self.n
