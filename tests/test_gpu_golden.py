@@ -3,6 +3,7 @@ the reference's lists / calls out, through the product's text decoder and the HI
 import gzip
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -11,6 +12,9 @@ from kir_graph_amd.hisat2 import extractVariant, pairLines
 from kir_graph_amd.index import GkIndex
 from kir_graph_amd.kir_typing import selectKirTypingModel
 from kir_graph_amd.msa2hisat import Variant
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from compat_reference import check_t14_calls, check_t14_steps  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -179,3 +183,26 @@ def test_a_parked_sample_comes_back_with_the_reference_lists(device, tmp_path):
     novel = [[v.id, v.typ, v.pos, v.val, v.length, v.ref] for v in back.variants if str(v.id).startswith("nv")]
     assert novel == t12["novel"]
     back.tab.close()
+
+
+@pytest.mark.parametrize("method", ["full", "exonfirst_1"])
+@pytest.mark.parametrize("which", ["a", "b"])
+def test_typing_where_products_underflow(device, tmp_path, monkeypatch, which, method):
+    """T14 (fixture made by the reference itself): long rows that mismatch an allele 98 .. 300 times -- subnormal products,
+    +0.0, log10 = -inf; in sample b every set of the heavy gene scores -inf.  The HIP path gives the reference's steps:
+    -inf exactly where it has it, no NaN, finite values within 1e-9, ids, names and calls wherever no tie decides."""
+    monkeypatch.setenv("GK_SEARCH", "bound")
+    t14 = load("t14_underflow.json.gz")
+    want = t14["samples"][which]["methods"][method]
+    assert "raised" not in want
+    gidx = index_from(t14["index"], tmp_path)
+    Variant.novel_id = 0
+    data = extractVariant(pairLines(t14["lines"] + t14["samples"][which]["extra_lines"]), gidx, dev=device)
+    assert len(data.reads()) == t14["samples"][which]["n_reads"]
+    typer = selectKirTypingModel(method, data, top_n=t14["top_n"], variant_correction=True)
+    calls, warn = typer.typing(t14["gene_cn"])
+    assert warn == want["warnings"]
+    for gene, steps in want["genes"].items():
+        check_t14_steps(typer._result[gene], steps, lambda r: [list(row) for row in r.allele_name])
+    check_t14_calls(calls, want, t14["gene_cn"])
+    data.tab.close()

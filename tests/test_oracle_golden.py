@@ -9,6 +9,7 @@ import gzip
 import io
 import json
 import os
+import sys
 import tempfile
 
 import numpy as np
@@ -17,6 +18,9 @@ import pytest
 
 from kir_graph_amd.index import getVariants
 from oracle import cn as ocn, em as oem, tabulate as ot, typing as oty
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from compat_reference import check_t14_calls, check_t14_steps  # noqa: E402
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -275,3 +279,28 @@ def test_tabulate_reads_beyond_the_128_byte_record():
     novel = [[v.id, v.typ, v.pos, v.val, v.length, v.ref] for v in data["variants"] if str(v.id).startswith("nv")]
     assert novel == t12["novel"]
     assert t12["most_positives"] > 44        # more events than two gk_mate records could hold
+
+
+@pytest.mark.parametrize("method", ["full", "exonfirst_1"])
+@pytest.mark.parametrize("which", ["a", "b"])
+def test_typing_where_products_underflow(which, method):
+    """T14: the reference's own typing of the hand-built samples whose long rows mismatch an allele 98 .. 300 times --
+    subnormal products, +0.0, log10 = -inf; in sample b every set of the heavy gene scores -inf.  The reference raises
+    on neither sample and emits no NaN; the oracle is pinned to it where no synthetic sample ever went."""
+    t14 = load("t14_underflow.json.gz")
+    want = t14["samples"][which]["methods"][method]
+    assert "raised" not in want
+    lines = t14["lines"] + t14["samples"][which]["extra_lines"]
+    data = ot.tabulateLines(lines, getVariants(write_index(t14["index"])))
+    assert len(data["reads"]) == t14["samples"][which]["n_reads"]
+    typer = oty.makeTyper(method, data, top_n=t14["top_n"], variant_correction=True)
+    calls, warn = typer.typing(t14["gene_cn"])
+    assert warn == want["warnings"]
+    heavy = want["genes"][t14["heavy_gene"]]
+    if method == "full":
+        assert np.isneginf(unhex(heavy[0]["value"])).any() and (which == "a" or np.isneginf(unhex(heavy[-1]["value"])).all())
+    for gene, steps in want["genes"].items():
+        check_t14_steps(typer.results[gene], steps, lambda r: r.allele_name)
+        assert oty.selectBest(typer.results[gene][-1]) == steps[-1]["best"] or \
+            np.count_nonzero(unhex(steps[-1]["value"]) == unhex(steps[-1]["value"])[0]) > 1
+    check_t14_calls(calls, want, t14["gene_cn"])
