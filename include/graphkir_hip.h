@@ -327,6 +327,14 @@ int gk_compat_log_miss_cols(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_
                             int32_t vbeg, int32_t vend, gk_dptr d_mask, int32_t words, int32_t n_allele,
                             int32_t keep_empty, gk_lut* lut, const int32_t* table_cols, int32_t n_table_cols,
                             gk_dptr d_log, gk_dptr d_miss8, int64_t ldm, gk_dptr d_flags);
+/* gk_compat_log_miss_cols followed by gk_miss_colsum for a list of AT MOST 8 alleles, by kernels of their own (a wavefront
+ * walks 8 rows at a time, 16 for a list of at most 4: csrc/gk_compat_narrow.hip): d_log, d_miss8 and *d_flags as above,
+ * d_msum uint32 [n_table_cols] = the column sums of the mismatch bytes; every output bit-identical to what the two calls
+ * leave. */
+int gk_compat_log_miss_narrow(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag,
+                              int32_t vbeg, int32_t vend, gk_dptr d_mask, int32_t words, int32_t n_allele,
+                              int32_t keep_empty, gk_lut* lut, const int32_t* table_cols, int32_t n_table_cols,
+                              gk_dptr d_log, gk_dptr d_miss8, int64_t ldm, gk_dptr d_flags, gk_dptr d_msum);
 /* Bits 2 and 3 of *d_flags after gk_compat_log_miss: bit 2 = some product had no log10 in the value table yet; its entry
  * of d_log holds the PRODUCT itself (strictly positive, which no log10 of a probability is) until gk_compat_patch, after
  * the table has been resolved (gk_lut_resolve*), puts the log10 and the mismatch byte there -- one pass over this gene's

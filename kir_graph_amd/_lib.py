@@ -203,6 +203,9 @@ _SIGS = {
     "gk_compat_log_miss_cols": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_int32, C.c_int32,
                                           C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_uint64, C.c_uint64, C.c_int64, C.c_uint64]),
+    "gk_compat_log_miss_narrow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_int32, C.c_int32,
+                                            C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.c_uint64, C.c_uint64, C.c_int64, C.c_uint64, C.c_uint64]),
     "gk_compat_log_miss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_int32, C.c_int32,
                                      C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64,
                                      C.c_int64, C.c_uint64]),

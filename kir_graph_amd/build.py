@@ -10,7 +10,7 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 SOURCES = ["gk_runtime.hip", "gk_scan.hip", "gk_tabulate.hip", "gk_typing.hip", "gk_lut.hip",
            "gk_search.hip", "gk_bound.hip", "gk_em.hip", "gk_cn.hip", "gk_depth.hip", "gk_sampack.cpp", "gk_bamread.cpp", "gk_textout.cpp",
-           "gk_comm.cpp", "gk_hostsearch.cpp", "gk_novel.hip", "gk_boot.hip", "gk_callboot.hip"]
+           "gk_comm.cpp", "gk_hostsearch.cpp", "gk_novel.hip", "gk_boot.hip", "gk_callboot.hip", "gk_compat_narrow.hip"]
 
 
 def hipcc() -> str:
@@ -32,6 +32,7 @@ def outOfDate(lib: Path) -> bool:
 KERNEL_SOURCES = {
     "compat_kernel": ["gk_typing.hip", "gk_lut.h", "gk_common.h"],
     "patch_pending": ["gk_typing.hip", "gk_lut.h", "gk_common.h"],
+    "compat_rows8": ["gk_compat_narrow.hip", "gk_lut.h", "gk_common.h"],
     "count_ids_genes": ["gk_typing.hip", "gk_common.h"],
     "flag_nonempty": ["gk_typing.hip", "gk_common.h"],
     "flag_pairs": ["gk_typing.hip", "gk_common.h"],

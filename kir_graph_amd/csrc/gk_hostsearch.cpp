@@ -227,6 +227,12 @@ __attribute__((weak)) int gk_compat_log_miss_cols(gk_ctx* ctx, gk_tab* tab, gk_d
                                                   int32_t keep_empty, gk_lut* lut, const int32_t* table_cols,
                                                   int32_t n_table_cols, gk_dptr d_log, gk_dptr d_miss8, int64_t ldm,
                                                   gk_dptr d_flags);
+// weak for the same reason: without it a list of at most 8 columns takes gk_compat_log_miss_cols + gk_miss_colsum
+__attribute__((weak)) int gk_compat_log_miss_narrow(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag,
+                                                    int32_t vbeg, int32_t vend, gk_dptr d_mask, int32_t words, int32_t n_allele,
+                                                    int32_t keep_empty, gk_lut* lut, const int32_t* table_cols,
+                                                    int32_t n_table_cols, gk_dptr d_log, gk_dptr d_miss8, int64_t ldm,
+                                                    gk_dptr d_flags, gk_dptr d_msum);
 int gk_miss_colsum(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int32_t n_cols, gk_dptr d_msum);
 int gk_compat_patch(gk_ctx* ctx, gk_lut* lut, gk_dptr d_log, int64_t n_rows, int32_t n_allele, gk_dptr d_miss8, int64_t ldm,
                     gk_dptr d_flags);
@@ -902,6 +908,7 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
     gk_gene_job& j = jobs[i];
     const int nc = n_cols_of(i);
     int rc;
+    bool summed = false;      // the kernel that wrote the bytes has formed their column sums
     if (patch) {      // only the entries that hold their product are touched (gk_compat_patch)
       j.patches++;
       sticky[i] |= flags[i] & 1u;
@@ -909,14 +916,21 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
     } else {
       j.passes++;
       sticky[i] = 0;
-      if (j.n_table_cols > 0)
+      // a list of at most 8 columns: 8 rows per wavefront (gk_compat_narrow.hip); GK_TEST_HOOKS=wide_compat keeps the
+      // kernel of the wide tables for them
+      static const bool wide_compat = gk_test_hook("wide_compat");
+      if (j.n_table_cols > 0 && j.n_table_cols <= 8 && gk_compat_log_miss_narrow && !wide_compat) {
+        rc = gk_compat_log_miss_narrow(ctx, tab, j.d_rows, j.n_rows, d_vflag, j.vbeg, j.vend, j.d_mask, j.words, j.n_allele, 0,
+                                       lut, j.table_cols, j.n_table_cols, j.d_L, j.d_miss8, j.ldm, j.d_flags, j.d_msum);
+        summed = true;
+      } else if (j.n_table_cols > 0)
         rc = gk_compat_log_miss_cols(ctx, tab, j.d_rows, j.n_rows, d_vflag, j.vbeg, j.vend, j.d_mask, j.words, j.n_allele, 0,
                                      lut, j.table_cols, j.n_table_cols, j.d_L, j.d_miss8, j.ldm, j.d_flags);
       else
         rc = gk_compat_log_miss(ctx, tab, j.d_rows, j.n_rows, d_vflag, j.vbeg, j.vend, j.d_mask, j.words, j.n_allele, 0, lut,
                                 j.d_L, j.d_miss8, j.ldm, j.d_flags);
     }
-    if (rc == GK_OK) rc = gk_miss_colsum(ctx, j.d_miss8, j.ldm, nc, j.d_msum);
+    if (rc == GK_OK && !summed) rc = gk_miss_colsum(ctx, j.d_miss8, j.ldm, nc, j.d_msum);
     if (rc == GK_OK && gk_fetch_queue(ctx, &flags[i], gk_ptr<void>(j.d_flags), sizeof(uint32_t)) != hipSuccess) rc = GK_ERR_HIP;
     if (rc) return rc;
     std::vector<int32_t> cols((size_t)nc);

@@ -133,6 +133,8 @@ def _priced(kernel: str, calls: list[tuple]) -> tuple[float, float, str, float]:
         elif kernel == "compat_kernel":
             b, o = compatLaunch(*c[1:5])
             bound, peak = "valu", laneOpsPeak("compat_kernel")
+        elif kernel == "compat_rows8":       # 8 rows per wave: the lists in, 9 bytes per entry out -- an HBM stream
+            b, o = compatLaunch(*c[1:5])[0], 0.0
         elif kernel == "tab_count":
             b, o = tabLaunch(*c[1:4])
         elif kernel in ("fraction_chunks", "setsum_leaves"):

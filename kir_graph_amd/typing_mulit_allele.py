@@ -46,6 +46,17 @@ def nativeSearch() -> bool:
     return True
 
 
+def compatKernelOf(table_cols) -> str:
+    """The kernel that writes a gene's table in ``gk_sample_search``, as ``Device.call_log`` names it: a column list of
+    at most 8 alleles takes ``compat_rows8`` (csrc/gk_compat_narrow.hip) unless GK_TEST_HOOKS=wide_compat keeps
+    ``compat_kernel`` for it, every other table ``compat_kernel``."""
+    import os
+    if table_cols is None or not 0 < len(table_cols) <= 8:
+        return "compat_kernel"
+    hooks = os.environ.get("GK_TEST_HOOKS", "").split(",")
+    return "compat_kernel" if "wide_compat" in hooks else "compat_rows8"
+
+
 _GROUP_CACHE_LOCK = threading.Lock()      # guards the per-gene exon-group caches (AlleleTypingExonFirst)
 
 
@@ -711,8 +722,10 @@ class AlleleTyping:
         m._known_at_launch = -1
         if m.dev.call_log is not None:
             per_row = m.tab.n_ids / max(m.tab.n_valid, 1)
+            n_written = m.n_allele if m._table_cols is None else len(m._table_cols)
             for _ in range(max(1, int(job.passes))):
-                m.dev.call_log.append(("compat_kernel", m.n_rows, m.n_allele, per_row * m.n_rows, 2 if m._indexed else 8))
+                m.dev.call_log.append((compatKernelOf(m._table_cols), m.n_rows, n_written, per_row * m.n_rows,
+                                       2 if m._indexed else 8))
         self.result = []
         self._adoptSearch(handle, 1 if homo else cn)
         if homo:
@@ -734,7 +747,7 @@ class AlleleTyping:
         if m.dev.call_log is not None:
             per_row = m.tab.n_ids / max(m.tab.n_valid, 1)
             for _ in range(max(1, int(job.passes))):
-                m.dev.call_log.append(("compat_kernel", m.n_rows, n_written, per_row * m.n_rows, 8))
+                m.dev.call_log.append((compatKernelOf(m._table_cols), m.n_rows, n_written, per_row * m.n_rows, 8))
             self._logLaunches(handle)       # the column sums of the whole table: this job's launch, nobody else logs it
         colsum = np.empty(m.n_allele, dtype=np.float64)
         check(lib().gk_search_colsum(handle, colsum.ctypes.data))    # NaN for the alleles a list leaves out
