@@ -170,6 +170,15 @@ int gk_tabulate_corrected(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates, int64_t n
 int gk_tabulate_spilled(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates, int64_t n_pairs, gk_dptr d_corr,
                         gk_dptr d_gene_pos0, const gk_mate_wide* wide, const int64_t* spill_pair, int64_t n_spill,
                         gk_tab** out);
+/* Same for a sample that lies in HBM in the COMPACT form of gk_mates_compact / gk_mates_compact_host (below): d_compact =
+ * uint32 word offsets [2 * n_pairs + 1], then the words the mates use.  The passes and the lists are those of
+ * gk_tabulate_spilled on the expanded records (gk_mates_expand); the 128-byte records are never written.  Pass 1 stages
+ * the run of words of a workgroup's 256 mates in LDS, GK_COMPACT_STAGE_WORDS of them at most (what lies beyond -- a run
+ * of long mates -- is read from global memory). */
+#define GK_COMPACT_STAGE_WORDS 4352
+int gk_tabulate_compact(gk_ctx* ctx, gk_index* idx, gk_dptr d_compact, int64_t n_pairs, gk_dptr d_corr,
+                        gk_dptr d_gene_pos0, const gk_mate_wide* wide, const int64_t* spill_pair, int64_t n_spill,
+                        gk_tab** out);
 /* Same handle from host CSR lists (the `.variant.json` hand-off of hisat2.py:847-866 loaded by
  * loadReadsAndVariantsData): off[4*n_valid+1] in list order lpv, rpv, lnv, rnv; ordinals < n_var_total. */
 int gk_tab_from_csr(gk_ctx* ctx, int32_t n_var_total, int64_t n_valid, const uint32_t* off, const uint32_t* ids,
@@ -225,6 +234,13 @@ int gk_sample_prepare_all(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d_
 int gk_sample_prepare_exon(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d_vflag, gk_dptr d_cnt, gk_dptr d_rows,
                            int64_t* gene_off_out, int64_t max_out, int32_t* ord_out, uint32_t* pos_out, uint32_t* neg_out,
                            int64_t* n_out);
+/* gk_sample_prepare_exon for a sample whose full model has been prepared with the same `multiple`: d_cnt_full is the
+ * d_cnt that gk_sample_prepare / gk_sample_prepare_all filled (the tallies of the uncorrected lists).  The first of the
+ * two tallies is read out of it -- the full tally where the incoming flag bit is clear, zero where it is set -- instead
+ * of walking every list again; every output is what gk_sample_prepare_exon writes.  d_cnt_full == 0: that call. */
+int gk_sample_prepare_exon_from(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d_vflag, gk_dptr d_cnt, gk_dptr d_rows,
+                                int64_t* gene_off_out, int64_t max_out, int32_t* ord_out, uint32_t* pos_out,
+                                uint32_t* neg_out, int64_t* n_out, gk_dptr d_cnt_full);
 
 /* ---- compatibility: reads2AlleleProb (typing_mulit_allele.py:340-381).
  * d_mask uint32 [vend-vbeg][words]: allele bit rows of the gene's index variants.
@@ -605,6 +621,9 @@ int gk_bam_write_lines_tagged(const char* path, const char* header_text, int64_t
  * concatenated position space, gene_off[n_gene] = total; depth_out holds gene_off[n_gene] values. */
 int gk_depth(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, int32_t multiple, const int64_t* gene_off,
              int32_t n_gene, uint32_t* depth_out);
+/* The same from the sample's records in the compact form (d_compact as for gk_tabulate_compact). */
+int gk_depth_compact(gk_ctx* ctx, gk_tab* tab, gk_dptr d_compact, int32_t multiple, const int64_t* gene_off,
+                     int32_t n_gene, uint32_t* depth_out);
 
 /* the `samtools depth -aa` text of that table ("gene\tpos\tdepth", positions 1-based, no header), as
  * samtools_utils.readSamtoolsDepth / kir_cn.predictSamplesCN read it (samtools_utils.py:17-22) */

@@ -46,6 +46,7 @@ SPILLED = 0xFF
 CIG_M, CIG_I, CIG_D, CIG_S = 0, 1, 2, 4
 NM_ABSENT = 255
 MAX_CIG, MAX_MM, MAX_INS, MAX_EV = 14, 16, 6, 22
+COMPACT_STAGE_WORDS = 4352      # GK_COMPACT_STAGE_WORDS: words of a workgroup's compact run that pass 1 stages in LDS
 
 
 class GeneJob(C.Structure):
@@ -120,6 +121,8 @@ _SIGS = {
                                      C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "gk_tabulate_corrected": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_uint64,
                                         C.POINTER(C.c_void_p)]),
+    "gk_tabulate_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_uint64,
+                                     C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "gk_tab_from_csr": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.POINTER(C.c_void_p)]),
     "gk_tab_get_info": (C.c_int, [C.c_void_p, C.POINTER(TabInfo)]),
@@ -191,6 +194,7 @@ _SIGS = {
     "gk_packer_spill_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gk_packer_string": (C.c_char_p, [C.c_void_p, C.c_int64]),
     "gk_depth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gk_depth_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "gk_depth_write_tsv": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "gk_cn_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                             C.c_int32, C.c_int32, C.c_double, C.c_void_p]),
@@ -229,6 +233,8 @@ _SIGS = {
                                  C.POINTER(C.c_int32)]),
     "gk_sample_prepare_exon": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "gk_sample_prepare_exon_from": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_uint64]),
     "gk_sample_em": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
     "gk_mates_compact": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
     "gk_mates_expand": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_uint64]),

@@ -156,7 +156,8 @@ def sampleFootprint(data, method: str) -> int:
     else:
         per_read = 9.2 * mean_alleles * (2 if method.startswith(("exonfirst", "pv_exonfirst")) else 1)
     lists = 4.0 * int(tab.n_ids) + 48.0 * n
-    records = 256.0 * int(tab.n_pairs) if getattr(tab, "mates", None) is not None else 0.0
+    mates = getattr(tab, "mates", None)       # 128-byte records, or the compact words (packed.DeviceCompactMates)
+    records = float(getattr(mates, "nbytes", 256.0 * int(tab.n_pairs))) if mates is not None else 0.0
     return int(1.15 * per_read * n + lists + records)
 
 
@@ -207,6 +208,13 @@ class SampleTyper:
         import threading
         self._room = threading.Condition()
         self._inflight_bytes, self._budget = 0, None
+        # What the process holds by now -- the index alone is ~10^5 Variant and allele objects -- leaves the collector's
+        # generations until the typer is closed: a full collection while samples are typed otherwise walks all of it
+        # behind the interpreter lock, ~40 ms in which no lane launches a kernel (12 configs[1] samples on three lanes:
+        # 7.2 - 9.9 ms per sample without such collections, 9.2 - 13.3 ms with them).  Nothing is collected here (a
+        # collection is what costs the time); what the samples allocate from now on is collected as ever.
+        import gc
+        gc.freeze()
 
     def _admit(self, data) -> int:
         need = sampleFootprint(data, self.method)
@@ -269,6 +277,8 @@ class SampleTyper:
         if self._pool is not None:
             self._pool.shutdown(wait=True)
             self._pool = None
+        import gc
+        gc.unfreeze()
 
     def __enter__(self):
         return self

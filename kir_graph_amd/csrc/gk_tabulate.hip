@@ -14,12 +14,15 @@
 // without private memory).  The sorted variant key table (<= ~0.5 MB) stays L2 resident and is
 // entered through a 16-bp bucket table, so a lookup is two bucket reads plus a <= 3-step bisection
 // instead of a 16-step one.  Outputs are one CSR (uint32 offsets, uint32 ordinals) in the factor
-// order lpv, rpv, lnv, rnv.
+// order lpv, rpv, lnv, rnv.  A sample that lies in HBM in the compact form (gk_mates_compact: only the
+// words a mate uses, behind word offsets) is tabulated from that form (gk_tabulate_compact): pass 1 stages
+// the workgroup's run of words instead of record heads (CompactView) and no 128-byte record is written.
 //
 // Two passes (count, emit) around one exclusive scan; novel variants are deduplicated in a device
 // hash table keyed by the packed variant key, ranked by first appearance through a bitmap over
 // (mate, event) sequence numbers, so that the numbering equals the reference's sequential counter.
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "gk_common.h"
@@ -93,6 +96,62 @@ struct HeadView {
   __device__ bool passes() const { return (flag() & 2u) && nm() != GK_NM_ABSENT && nm() <= 4u; }
 };
 static_assert(kCigWord + GK_MAX_CIG / 2 <= kHeadWords, "the CIGAR lies in the staged head");
+
+// a mate in the compact form (gk_mates_compact / gk_mates_compact_host): only the words it uses -- header, CIGAR words,
+// mismatches, inserted-string ids -- one after the other.  The 256 mates of a workgroup own ONE contiguous run of the
+// sample's words (7 - 8 words per mate on 150-base reads, 32 at most); its first kStageWords words are staged in LDS, a
+// word beyond them (a run of long mates) is read where it lies in global memory.  `run` / `g` point at the run's first
+// word, `base` is the mate's first word inside the run.  A field the mate does not carry reads as 0, as it does in the
+// expanded record.
+constexpr int kStageWords = GK_COMPACT_STAGE_WORDS;      // 17 KB: the LDS the staged heads of the record form take
+static_assert(kStageWords == kThreads * kHeadLd, "the compact run is staged in the LDS budget of the staged heads");
+struct CompactView {
+  static constexpr int kCapCig = GK_MAX_CIG, kCapMm = GK_MAX_MM, kCapIns = GK_MAX_INS, kCapEv = kMaxEv;
+  const uint32_t* run;      // LDS: words [0, kStageWords) of the workgroup's run
+  const uint32_t* g;        // the run in global memory
+  uint32_t base;            // the mate's header
+  uint32_t o_mm, o_ins;     // its mismatches and inserted-string ids (offsets inside the run)
+  uint32_t n_ins_w;
+  uint32_t h0, h1, h2;      // the header words
+  __device__ uint32_t word(uint32_t i) const { return i < (uint32_t)kStageWords ? run[i] : g[i]; }
+  __device__ void open(uint32_t at) {
+    base = at;
+    h0 = word(at); h1 = word(at + 1); h2 = word(at + 2);
+    const uint32_t nc = (h2 >> 8) & 0xFFu;
+    const bool sp = nc == GK_SPILLED;            // header + ins[0] (mate_used_words)
+    const uint32_t n_cw = sp ? 0u : (min(nc, (uint32_t)GK_MAX_CIG) + 1u) / 2u;
+    const uint32_t n_mw = sp ? 0u : min((h2 >> 16) & 0xFFu, (uint32_t)GK_MAX_MM);
+    n_ins_w = sp ? 1u : min(h2 >> 24, (uint32_t)GK_MAX_INS);
+    o_mm = at + kCigWord + n_cw;
+    o_ins = o_mm + n_mw;
+  }
+  __device__ bool spilled() const { return n_cig() == GK_SPILLED; }
+  __device__ uint32_t pos0() const { return h0; }
+  __device__ uint32_t flag() const { return h1 & 0xFFFFu; }
+  __device__ uint32_t ref() const { return (h1 >> 16) & 0xFFu; }
+  __device__ uint32_t nm() const { return h2 & 0xFFu; }
+  __device__ uint32_t n_cig() const { return (h2 >> 8) & 0xFFu; }
+  __device__ uint32_t n_mm() const { return (h2 >> 16) & 0xFFu; }
+  __device__ uint32_t cig(int i) const {      // i < min(n_cig, kCapCig): inside the mate's CIGAR words
+    const uint32_t x = word(base + kCigWord + ((uint32_t)i >> 1));
+    return (i & 1) ? (x >> 16) : (x & 0xFFFFu);
+  }
+  __device__ uint32_t mm_off(int i) const { return word(o_mm + (uint32_t)i) & 0xFFFFu; }      // i < min(n_mm, kCapMm)
+  __device__ uint32_t mm_base(int i) const { return (word(o_mm + (uint32_t)i) >> 16) & 0xFFu; }
+  __device__ uint32_t ins(int i) const {      // a CIGAR may name more insertions than the mate carries strings for
+    const bool has = (uint32_t)i < n_ins_w;
+    const uint32_t x = word(has ? o_ins + (uint32_t)i : base);
+    return has ? x : 0u;
+  }
+  __device__ bool passes() const { return (flag() & 2u) && nm() != GK_NM_ABSENT && nm() <= 4u; }
+};
+
+// the first min(n_run, kStageWords) words of the workgroup's run -> LDS, coalesced
+__device__ inline void stage_run(const uint32_t* g, uint32_t n_run, uint32_t* run) {
+  const uint32_t n = min(n_run, (uint32_t)kStageWords);
+  for (uint32_t i = threadIdx.x; i < n; i += kThreads) run[i] = g[i];
+  __syncthreads();
+}
 
 // a record of the wide format (gk_mate_wide), read where it lies in global memory: such pairs are rare
 struct WideView {
@@ -534,7 +593,10 @@ __device__ inline uint32_t window_negatives(const IndexView& ix, const EvRow& ev
 
 // pass 1: validity, counts, novel registration.  One lane per mate; mates of a pair sit in
 // adjacent lanes so the pair verdict is one lane shuffle.
-__global__ __launch_bounds__(kThreads) void tab_count(const gk_mate* mates, int64_t n_mates, IndexView ix,
+// kCompact: `mates` is null and the sample comes as its compact words (c_off [n_mates + 1] word offsets, c_words).
+template <bool kCompact>
+__global__ __launch_bounds__(kThreads) void tab_count(const gk_mate* mates, const uint32_t* __restrict__ c_off,
+                                                      const uint32_t* __restrict__ c_words, int64_t n_mates, IndexView ix,
                                                       NovelTable nt, uint32_t* cnt /*[4*n_pairs+1]*/,
                                                       uint32_t* valid /*[n_pairs]*/, int* err_flags,
                                                       uint4* ev_save /*[n_mates]: events 0 .. 3*/,
@@ -545,12 +607,23 @@ __global__ __launch_bounds__(kThreads) void tab_count(const gk_mate* mates, int6
   // LDS holds the heads of the staged records only (17 KB per workgroup); a mate's first four event words and the kept
   // bits of the first 128 candidates of its window ride in registers and leave as ONE dense 16-byte store each (a wave
   // writes 1 KB of full lines); what goes beyond (rare) lives in the mate's overflow rows
+  // -- or, of a sample in the compact form, the workgroup's run of words in the same 17 KB
   __shared__ uint32_t rec[kThreads * kHeadLd];
   const int64_t m0 = (int64_t)blockIdx.x * kThreads;
-  stage_heads(mates, m0, n_mates, rec);
   const int64_t m = m0 + threadIdx.x;
   const bool in = m < n_mates;
-  const HeadView r{rec + threadIdx.x * kHeadLd, reinterpret_cast<const uint32_t*>(mates + (in ? m : 0))};
+  typename std::conditional<kCompact, CompactView, HeadView>::type r;
+  if constexpr (kCompact) {
+    const uint32_t run0 = c_off[m0], run1 = c_off[min<int64_t>(m0 + kThreads, n_mates)];
+    const uint32_t at = c_off[in ? m : m0] - run0;      // a lane past the end reads the workgroup's first mate and counts nothing
+    stage_run(c_words + run0, run1 - run0, rec);
+    r.run = rec; r.g = c_words + run0;
+    r.open(at);
+  } else {
+    stage_heads(mates, m0, n_mates, rec);
+    r.w = rec + threadIdx.x * kHeadLd;
+    r.g = reinterpret_cast<const uint32_t*>(mates + (in ? m : 0));
+  }
   EvRow ev{{0u, 0u, 0u, 0u}, ev_more + (in ? m : 0) * kEvMore, nt.keys};
   const bool ok = in && r.passes() && !r.spilled();   // wide pairs: tab_count_wide writes their counts afterwards
   const bool ok_other = __shfl_xor((int)ok, 1, 64) != 0;
@@ -820,7 +893,9 @@ __global__ __launch_bounds__(64) void tab_emit_wide(const gk_mate_wide* wide, co
     if (negative_kept(ix.key[i], i, ix, EvView{evw}, wk.n, wk.any_n, wk.right)) ids[at++] = (uint32_t)i;
 }
 
-__global__ __launch_bounds__(kThreads) void gather_pairs(const gk_mate* mates, const int32_t* pair_src, int64_t n_valid,
+// mates == null: the sample in the compact form (word offsets c_off, words c_words)
+__global__ __launch_bounds__(kThreads) void gather_pairs(const gk_mate* mates, const uint32_t* c_off, const uint32_t* c_words,
+                                                         const int32_t* pair_src, int64_t n_valid,
                                                          const uint32_t* off_in, uint32_t* off_out, uint8_t* gene,
                                                          uint8_t* nh, uint32_t total) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
@@ -832,7 +907,7 @@ __global__ __launch_bounds__(kThreads) void gather_pairs(const gk_mate* mates, c
   const int64_t p = pair_src[i];
 #pragma unroll
   for (int k = 0; k < 4; ++k) off_out[4 * i + k] = off_in[4 * p + k];
-  const uint32_t w1 = reinterpret_cast<const uint32_t*>(mates + 2 * p)[1];
+  const uint32_t w1 = mates ? reinterpret_cast<const uint32_t*>(mates + 2 * p)[1] : c_words[c_off[2 * p] + 1u];
   gene[i] = (uint8_t)((w1 >> 16) & 0xFFu);
   nh[i] = (uint8_t)(w1 >> 24);
 }
@@ -1007,13 +1082,32 @@ int gk_tabulate_corrected(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, int64_t
   return gk_tabulate_spilled(ctx, idx, d_mates_p, n_pairs, d_corr, d_gene_pos0, nullptr, nullptr, 0, out);
 }
 
-static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, int64_t n_pairs, gk_dptr d_corr,
+static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, gk_dptr d_compact, int64_t n_pairs, gk_dptr d_corr,
                                gk_dptr d_gene_pos0, const gk_mate_wide* wide, const int64_t* spill_pair,
                                int64_t n_spill, uint32_t log2cap, bool* table_too_small, gk_tab** out);
+static int tabulate_sample(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, gk_dptr d_compact, int64_t n_pairs, gk_dptr d_corr,
+                           gk_dptr d_gene_pos0, const gk_mate_wide* wide, const int64_t* spill_pair, int64_t n_spill,
+                           gk_tab** out);
 
 int gk_tabulate_spilled(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, int64_t n_pairs, gk_dptr d_corr,
                         gk_dptr d_gene_pos0, const gk_mate_wide* wide, const int64_t* spill_pair, int64_t n_spill,
                         gk_tab** out) {
+  return tabulate_sample(ctx, idx, d_mates_p, 0, n_pairs, d_corr, d_gene_pos0, wide, spill_pair, n_spill, out);
+}
+
+/* gk_tabulate_spilled for a sample that is in HBM in the compact form of gk_mates_compact / gk_mates_compact_host
+ * (uint32 word offsets [2 * n_pairs + 1], then the words): the same passes, the same lists, without the 128-byte
+ * records -- pass 1 stages a workgroup's run of words where it staged the heads of its records. */
+int gk_tabulate_compact(gk_ctx* ctx, gk_index* idx, gk_dptr d_compact, int64_t n_pairs, gk_dptr d_corr,
+                        gk_dptr d_gene_pos0, const gk_mate_wide* wide, const int64_t* spill_pair, int64_t n_spill,
+                        gk_tab** out) {
+  GK_REQUIRE(d_compact, "null compact records");
+  return tabulate_sample(ctx, idx, 0, d_compact, n_pairs, d_corr, d_gene_pos0, wide, spill_pair, n_spill, out);
+}
+
+static int tabulate_sample(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, gk_dptr d_compact, int64_t n_pairs, gk_dptr d_corr,
+                           gk_dptr d_gene_pos0, const gk_mate_wide* wide, const int64_t* spill_pair, int64_t n_spill,
+                           gk_tab** out) {
   // Hash table of the novel variants: a slot per mate to begin with, 2^22 at most (distinct novel variants are few -- read errors
   // repeat, positions are finite -- while the worst case, every event of every mate novel, would need 44 slots per
   // mate: 2^24 slots, i.e. 200 MB to clear and three passes over them per sample).  A sample that fills half of it
@@ -1025,15 +1119,15 @@ int gk_tabulate_spilled(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, int64_t n
   while ((1ull << log2max) < (uint64_t)(2 * std::max<int64_t>(n_pairs, 0)) * GK_WIDE_EVENTS * 2 && log2max < 30) ++log2max;   // a slot number is 30 bits of an event word
   for (;;) {
     bool too_small = false;
-    const int rc = tabulate_with_table(ctx, idx, d_mates_p, n_pairs, d_corr, d_gene_pos0, wide, spill_pair, n_spill, log2cap,
-                                       &too_small, out);
+    const int rc = tabulate_with_table(ctx, idx, d_mates_p, d_compact, n_pairs, d_corr, d_gene_pos0, wide, spill_pair, n_spill,
+                                       log2cap, &too_small, out);
     if (!too_small) return rc;
     if (log2cap >= log2max) return rc;
     log2cap = std::min(log2cap + 3, log2max);
   }
 }
 
-static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, int64_t n_pairs, gk_dptr d_corr,
+static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, gk_dptr d_compact, int64_t n_pairs, gk_dptr d_corr,
                                gk_dptr d_gene_pos0, const gk_mate_wide* wide, const int64_t* spill_pair,
                                int64_t n_spill, uint32_t log2cap, bool* table_too_small, gk_tab** out) {
   gk_bind(ctx);
@@ -1044,8 +1138,11 @@ static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, in
                "wide pairs must name pairs of the sample, ascending");
   GK_REQUIRE((d_corr == 0) == (d_gene_pos0 == 0), "correction table and position offsets come together");
   GK_REQUIRE(n_pairs < (1ll << 26), "more than 2^26 pairs per call");
-  const gk_mate* mates = gk_ptr<const gk_mate>(d_mates_p);
+  const gk_mate* mates = gk_ptr<const gk_mate>(d_mates_p);      // null for a sample in the compact form
   const int64_t n_mates = 2 * n_pairs;
+  const uint32_t* c_off = gk_ptr<const uint32_t>(d_compact);
+  const uint32_t* c_words = c_off ? c_off + n_mates + 1 : nullptr;
+  GK_REQUIRE(n_mates == 0 || mates || c_off, "no records");
   hipStream_t st = ctx->stream;
   gk_tab* tab = new gk_tab();
   tab->ctx = ctx; tab->idx = idx; tab->n_pairs = n_pairs; tab->n_var = idx->n_var;
@@ -1080,8 +1177,12 @@ static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, in
                      gk_ptr<uint8_t>(d_corr), gk_ptr<int64_t>(d_gene_pos0), idx->d_del_bits, idx->d_lb_a, idx->d_lb_t,
                      idx->d_gene_pbase, idx->d_snp_ord};
   if (n_mates) {
-    GK_PROF(ctx, "tab_count", GK_KERNEL(tab_count, dim3(nblk(n_mates)), dim3(kThreads), 0, st, mates, n_mates, ix,
-                       nt, cnt, valid, d_err, ev_save, ev_more, lo_save, mask_save, mask_more));
+    if (mates)
+      GK_PROF(ctx, "tab_count", GK_KERNEL(tab_count<false>, dim3(nblk(n_mates)), dim3(kThreads), 0, st, mates, c_off, c_words, n_mates,
+                         ix, nt, cnt, valid, d_err, ev_save, ev_more, lo_save, mask_save, mask_more));
+    else
+      GK_PROF(ctx, "tab_count", GK_KERNEL(tab_count<true>, dim3(nblk(n_mates)), dim3(kThreads), 0, st, mates, c_off, c_words, n_mates,
+                         ix, nt, cnt, valid, d_err, ev_save, ev_more, lo_save, mask_save, mask_more));
   }
   int64_t* d_spill_pair = nullptr;
   uint32_t* wide_ev = nullptr;
@@ -1142,11 +1243,18 @@ static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, in
                      d_spill_pair, n_spill, prefix, tab->d_novel_key));
 
   GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_ids, (size_t)(tab->n_ids + 1) * sizeof(uint32_t)));
+  gk_mate* expanded = nullptr;
   if (n_mates) {
     // pass 2: from what pass 1 saved; the second walk only when some window did not fit the saved bits
     const bool two_walks = gk_test_hook("two_walks");   // tests: the second walk for every sample
     if ((err & 4) || two_walks) {
-      GK_PROF(ctx, "tab_emit", GK_KERNEL(tab_emit, dim3(nblk(n_mates)), dim3(kThreads), 0, st, mates, n_mates, ix, nt,
+      const gk_mate* records = mates;
+      if (!records) {      // rare: the second walk reads 128-byte records, expanded here for the length of this call
+        GK_HIP(gk_pool_malloc(ctx, (void**)&expanded, (size_t)n_mates * sizeof(gk_mate)));
+        GK_KERNEL(mates_unpack_words, dim3(nblk(n_mates)), dim3(kThreads), 0, st, c_off, c_words, n_mates, expanded);
+        records = expanded;
+      }
+      GK_PROF(ctx, "tab_emit", GK_KERNEL(tab_emit, dim3(nblk(n_mates)), dim3(kThreads), 0, st, records, n_mates, ix, nt,
                          cnt, valid, tab->d_ids));
     } else {
       GK_PROF(ctx, "tab_expand", GK_KERNEL(tab_expand, dim3(nblk(n_mates, kExpandThreads)), dim3(kExpandThreads), 0, st, n_mates, idx->n_var,
@@ -1165,13 +1273,13 @@ static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, in
   GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_off, (size_t)(4 * tab->n_valid + 1) * sizeof(uint32_t)));
   GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_pair_gene, (size_t)tab->n_valid + 1));
   GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_pair_nh, (size_t)tab->n_valid + 1));
-  GK_PROF(ctx, "gather_pairs", GK_KERNEL(gather_pairs, dim3(nblk(tab->n_valid + 1)), dim3(kThreads), 0, st, mates, tab->d_pair_src,
-                     tab->n_valid, cnt, tab->d_off, tab->d_pair_gene, tab->d_pair_nh, (uint32_t)tab->n_ids));
+  GK_PROF(ctx, "gather_pairs", GK_KERNEL(gather_pairs, dim3(nblk(tab->n_valid + 1)), dim3(kThreads), 0, st, mates, c_off, c_words,
+                     tab->d_pair_src, tab->n_valid, cnt, tab->d_off, tab->d_pair_gene, tab->d_pair_nh, (uint32_t)tab->n_ids));
   GK_HIP(hipGetLastError());
   GK_HIP(hipStreamSynchronize(st));
   gk_pool_free(ctx,cnt); gk_pool_free(ctx,valid); gk_pool_free(ctx,d_err); gk_pool_free(ctx,bitmap); gk_pool_free(ctx,prefix); gk_pool_free(ctx,wide_bits);
   gk_pool_free(ctx,ev_save); gk_pool_free(ctx,lo_save); gk_pool_free(ctx,mask_save); gk_pool_free(ctx,ev_more); gk_pool_free(ctx,mask_more);
-  gk_pool_free(ctx,d_spill_pair); gk_pool_free(ctx,wide_ev);
+  gk_pool_free(ctx,d_spill_pair); gk_pool_free(ctx,wide_ev); gk_pool_free(ctx,expanded);
   gk_pool_free(ctx,nt.keys); gk_pool_free(ctx,nt.seq); gk_pool_free(ctx,nt.rank);
   if (err & 2) {
     gk_set_error("a filter-passing mate carries more variant events than its record format allows (%d, wide %d)", kMaxEv,

@@ -116,6 +116,20 @@ __global__ __launch_bounds__(kThreads) void apply_correction(const uint32_t* cnt
   vflag[v] = f;
 }
 
+// The exon model's first tally out of the full model's (gk_sample_prepare_exon_from): the full preparation tallied the
+// same rows of the same partition with every drop flag zero, so a tally that skips the ids whose flag bit is set is the
+// full tally where the bit is clear and zero where it is set -- nv loads instead of a walk over every list.
+__global__ __launch_bounds__(kThreads) void mask_tallies(const uint32_t* __restrict__ full_pos,
+                                                         const uint32_t* __restrict__ full_neg,
+                                                         const uint8_t* __restrict__ vflag, int64_t n,
+                                                         uint32_t* __restrict__ cnt_pos, uint32_t* __restrict__ cnt_neg) {
+  const int64_t v = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (v >= n) return;
+  const uint8_t f = vflag[v];
+  cnt_pos[v] = (f & 1) ? 0u : full_pos[v];
+  cnt_neg[v] = (f & 2) ? 0u : full_neg[v];
+}
+
 __global__ __launch_bounds__(kThreads) void flag_nonempty(const int32_t* rows, int64_t n_rows, const uint32_t* off,
                                                           const uint32_t* ids, const uint8_t* vflag, uint32_t* flag,
                                                           uint32_t* zero, int n_zero) {
@@ -953,7 +967,8 @@ struct Survivors {        // what gk_variant_surviving would fetch, asked for to
 }  // namespace
 
 static int sample_prepare(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d_vflag, gk_dptr d_cnt, gk_dptr d_rows,
-                          int64_t* gene_off_out, const Survivors* surv, bool keep_vflag = false, int rounds = 1);
+                          int64_t* gene_off_out, const Survivors* surv, bool keep_vflag = false, int rounds = 1,
+                          gk_dptr d_cnt_full = 0);
 
 int gk_sample_prepare(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d_vflag, gk_dptr d_cnt, gk_dptr d_rows,
                       int64_t* gene_off_out) {
@@ -987,8 +1002,23 @@ int gk_sample_prepare_exon(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d
   return sample_prepare(ctx, tab, multiple, d_vflag, d_cnt, d_rows, gene_off_out, &s, true, 2);
 }
 
+/* gk_sample_prepare_exon for a sample whose FULL model has been prepared already with the same `multiple`
+ * (gk_sample_prepare / gk_sample_prepare_all): d_cnt_full is that call's d_cnt, the tallies of the uncorrected lists.  The
+ * first of the two tallies is then taken from it (mask_tallies) instead of walking every list once more; everything after
+ * it -- the first correction, the second tally and correction, the removal of empty rows -- is gk_sample_prepare_exon's.
+ * d_cnt_full == 0: gk_sample_prepare_exon. */
+int gk_sample_prepare_exon_from(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d_vflag, gk_dptr d_cnt, gk_dptr d_rows,
+                                int64_t* gene_off_out, int64_t max_out, int32_t* ord_out, uint32_t* pos_out,
+                                uint32_t* neg_out, int64_t* n_out, gk_dptr d_cnt_full) {
+  GK_REQUIRE(ord_out && pos_out && neg_out && n_out && max_out >= 0, "null pointer");
+  GK_REQUIRE(d_cnt_full != d_cnt || !d_cnt, "the full model's tallies and the exon model's are two buffers");
+  Survivors s;
+  s.max_out = max_out; s.ord = ord_out; s.pos = pos_out; s.neg = neg_out; s.n_out = n_out; s.novel_key = nullptr;
+  return sample_prepare(ctx, tab, multiple, d_vflag, d_cnt, d_rows, gene_off_out, &s, true, 2, d_cnt_full);
+}
+
 static int sample_prepare(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d_vflag, gk_dptr d_cnt, gk_dptr d_rows,
-                          int64_t* gene_off_out, const Survivors* surv, bool keep_vflag, int rounds) {
+                          int64_t* gene_off_out, const Survivors* surv, bool keep_vflag, int rounds, gk_dptr d_cnt_full) {
   gk_bind(ctx);
   GK_REQUIRE(ctx && tab && tab->idx && d_vflag && d_cnt && d_rows && gene_off_out, "null pointer");
   if (surv) *surv->n_out = 0;
@@ -1051,11 +1081,16 @@ static int sample_prepare(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d_
   GK_HIP(hipMemsetAsync(maybe, 0, (size_t)tab->n_valid, st));      // pairs outside the partition: never asked for
   for (int round = 0; round < rounds; ++round) {      // the exon model corrects its lists twice (typing_mulit_allele.py:644-645, 664)
     if (round) GK_HIP(hipMemsetAsync(cnt, 0, (size_t)(2 * nv) * sizeof(uint32_t), st));
-    GK_PROF(ctx, "count_ids_genes",
-            GK_KERNEL(count_ids_genes, dim3((unsigned)n_wg), dim3(kThreads), (size_t)max_local * 8 + kThreads * sizeof(uint32_t), st, part.d_rows,
-                      (const int32_t*)d_tab, (const int64_t*)(d_tab + o_row0), (const int64_t*)(d_tab + o_row1),
-                      tab->idx->d_gene_vbeg, max_local, tab->d_off, tab->d_ids, vflag, cnt, cnt + nv,
-                      round == rounds - 1 ? maybe : (uint8_t*)nullptr));
+    if (round == 0 && rounds > 1 && d_cnt_full) {      // the full model's tallies of these rows are at hand (never the last round: no `maybe`)
+      const uint32_t* full = gk_ptr<const uint32_t>(d_cnt_full);
+      GK_PROF(ctx, "mask_tallies", GK_KERNEL(mask_tallies, dim3(nblk(nv)), dim3(kThreads), 0, st, full, full + nv, vflag, nv, cnt, cnt + nv));
+    } else {
+      GK_PROF(ctx, "count_ids_genes",
+              GK_KERNEL(count_ids_genes, dim3((unsigned)n_wg), dim3(kThreads), (size_t)max_local * 8 + kThreads * sizeof(uint32_t), st, part.d_rows,
+                        (const int32_t*)d_tab, (const int64_t*)(d_tab + o_row0), (const int64_t*)(d_tab + o_row1),
+                        tab->idx->d_gene_vbeg, max_local, tab->d_off, tab->d_ids, vflag, cnt, cnt + nv,
+                        round == rounds - 1 ? maybe : (uint8_t*)nullptr));
+    }
     GK_PROF(ctx, "apply_correction", GK_KERNEL(apply_correction, dim3(nblk(nv)), dim3(kThreads), 0, st, cnt, cnt + nv, nv, vflag));
   }
   // rows with a surviving id, compacted in place of the grouping (stable: the groups stay contiguous and ordered)

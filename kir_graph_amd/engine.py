@@ -4,7 +4,8 @@ Device-resident state of the typing path and thin wrappers over the C ABI.
 Layout in HBM (one sample at a time per GPU; sizes for 1 M pairs, ~2 k alleles):
 
 * index keys ``u64[V]`` + per-gene allele bit rows ``u32[V_g][A_g/32]`` (< 1 MB, resident for the run)
-* mate records ``64 B x 2 x pairs``  (128 MB)
+* mate records in their compact form: ``u32`` word offsets + ~7.5 words per mate (~70 MB; the 128-byte records,
+  256 MB, only when a caller asks for them)
 * tabulation CSR: ``u32`` offsets ``[4 x valid + 1]`` and ``u32`` variant ordinals (~50 per pair)
 * per gene: row list ``i32[R]``, variant flags ``u8[V + novel]``,
   probabilities / log-probabilities column-major ``f64[A][R]`` (so every reduction over reads
@@ -125,11 +126,14 @@ class Tabulation:
         if isinstance(mates, np.ndarray):
             assert mates.dtype == _lib.MATE_DTYPE
             self.mates = self.dev.put(mates)
-        elif hasattr(mates, "toDevice"):      # packed.CompactMates: copied compact, expanded in HBM
+        elif hasattr(mates, "toDevice"):      # packed.CompactMates: copied compact on this context's stream, tabulated as such
             self.mates = mates.toDevice(self.dev)
         else:
             self.mates = mates
         self.n_pairs = self.mates.size // 2
+        # packed.DeviceCompactMates: the compact words are tabulated where they lie (gk_tabulate_compact); the 128-byte
+        # records are never written
+        compact = getattr(self.mates, "words", None) if hasattr(self.mates, "records") else None
         h = C.c_void_p()
         d_table = d_pos0 = None
         if correction is not None:
@@ -137,10 +141,18 @@ class Tabulation:
             assert table.dtype == np.uint8 and table.shape == (int(pos0[-1]), 5) and len(pos0) == len(dindex.host.genes) + 1
             d_table = self.dev.put(np.ascontiguousarray(table).reshape(-1) if table.size else np.zeros(1, np.uint8))
             d_pos0 = self.dev.put(np.ascontiguousarray(pos0, dtype=np.int64))
+        wide = which = None
         if spill is not None and len(spill[1]):
             wide = np.ascontiguousarray(spill[0], dtype=_lib.MATE_WIDE_DTYPE)
             which = np.ascontiguousarray(spill[1], dtype=np.int64)
             assert len(wide) == 2 * len(which)
+        if compact is not None:
+            check(lib().gk_tabulate_compact(self.dev.ctx, dindex.handle, compact.ptr, self.n_pairs,
+                                            d_table.ptr if d_table else 0, d_pos0.ptr if d_pos0 else 0,
+                                            wide.ctypes.data if wide is not None else None,
+                                            which.ctypes.data if which is not None else None,
+                                            len(which) if which is not None else 0, C.byref(h)))
+        elif wide is not None:
             check(lib().gk_tabulate_spilled(self.dev.ctx, dindex.handle, self.mates.ptr, self.n_pairs,
                                             d_table.ptr if d_table else 0, d_pos0.ptr if d_pos0 else 0,
                                             wide.ctypes.data, which.ctypes.data, len(which), C.byref(h)))
@@ -159,7 +171,8 @@ class Tabulation:
             raise AssertionError("variant window has left > right (graphkir/hisat2.py:744)")
         self._novel_keys = None
         if self.dev.call_log is not None:
-            self.dev.call_log.append(("tab_count", self.n_pairs, self.n_valid, self.n_ids))
+            self.dev.call_log.append(("tab_count", self.n_pairs, self.n_valid, self.n_ids)
+                                     + ((compact.nbytes,) if compact is not None else ()))      # the bytes pass 1 reads
 
     @property
     def n_var_total(self) -> int:
@@ -181,7 +194,8 @@ class Tabulation:
         """Error correction + removal of empty reads of EVERY gene at once (``gk_sample_prepare_all``), computed by
         the first caller and shared by all gene threads (``PreparedSample``).
         ``exon``: the same for the EXON model of every gene (``gk_sample_prepare_exon``: ids outside the exons dropped
-        from every list, the correction applied twice, typing_mulit_allele.py:640-664).
+        from every list, the correction applied twice, typing_mulit_allele.py:640-664; ``gk_sample_prepare_exon_from``
+        when the full model of the same ``multiple`` has been prepared: its tallies spare the first walk).
         None for tabulations that were not made by ``gk_tabulate`` (no index handle / novel keys on the device)."""
         if self.dindex is None or not self.info.d_pair_src:      # host lists / compact files: no index handle in the library
             return None
@@ -208,7 +222,13 @@ class Tabulation:
                 args = (dev.ctx, self.handle, int(multiple), vflag.ptr, cnt.ptr, rows.ptr, off.ctypes.data, nv,
                         o.ctypes.data, p.ctypes.data, q.ctypes.data, C.byref(n_surv))
                 if exon:
-                    check(lib().gk_sample_prepare_exon(*args))
+                    # the full model of the same `multiple`, when it has been prepared (exon-first prepares it first), has
+                    # tallied these very rows with no id dropped: the exon model's first tally is read out of its counts
+                    full = store.get(bool(multiple))
+                    if full is not None:
+                        check(lib().gk_sample_prepare_exon_from(*args, full.cnt.ptr))
+                    else:
+                        check(lib().gk_sample_prepare_exon(*args))
                 else:
                     # error correction, empty reads, the surviving tallies of every gene (isHomozygous reads them per gene)
                     # and the sample's novel keys in ONE library call with two waits (six when the three were separate

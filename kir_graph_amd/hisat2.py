@@ -253,7 +253,8 @@ class ParkedRecords:
 
     What waits in HBM is the sample's packed records in compact form (``gk_mates_compact``: ~30 bytes per mate, ~150 MB
     per 5 M reads) instead of its tabulation (~1 GB): the lists are made again from them when the sample's turn comes
-    (``restore``: expansion + ``gk_tabulate``, a millisecond or two) -- same records, same index, same first novel id, so
+    (``restore``: ``gk_tabulate_compact`` on the parked words, or expansion + ``gk_tabulate`` for a sample that came as
+    128-byte records; a millisecond or two) -- same records, same index, same first novel id, so
     the same lists and the same ``nv`` ids."""
 
     def __init__(self, data: "SampleData"):
@@ -266,11 +267,19 @@ class ParkedRecords:
         self.n_pairs, self.novel_base = tab.n_pairs, tab.novel_base
         self.expect = (tab.n_valid, tab.n_ids, tab.n_novel)
         self.spill, self.correction = getattr(tab, "_spill", None), getattr(tab, "_correction", None)
-        ptr, nbytes = C.c_uint64(), C.c_int64()
-        check(lib().gk_mates_compact(self.dev.ctx, tab.mates.ptr, 2 * self.n_pairs, C.byref(ptr), C.byref(nbytes)))
-        self.ptr, self.nbytes = ptr.value, int(nbytes.value)
+        self._words = None
+        words = getattr(tab.mates, "words", None) if hasattr(tab.mates, "records") else None
+        if words is not None:
+            # packed.DeviceCompactMates: the sample is in HBM in this very form -- its words are parked as they are (the
+            # buffer stays with the context whose pool it came from and goes back there)
+            self._words, tab.mates.words = words, None
+            self.ptr, self.nbytes = words.ptr, int(words.nbytes)
+        else:
+            ptr, nbytes = C.c_uint64(), C.c_int64()
+            check(lib().gk_mates_compact(self.dev.ctx, tab.mates.ptr, 2 * self.n_pairs, C.byref(ptr), C.byref(nbytes)))
+            self.ptr, self.nbytes = ptr.value, int(nbytes.value)
         # the records came from another context's pool (the copier's) and a pool orders reuse on its own stream only: the
-        # packing kernel on this stream must be through with them before the block can be handed out again
+        # kernels of this stream (the packing, the tabulation) must be through with them before a block can be handed out again
         self.dev.sync()
         tab.mates.free()
         tab.mates = None
@@ -280,9 +289,14 @@ class ParkedRecords:
         """The tabulated sample again (its compact records are released)."""
         if not self.ptr:
             raise ValueError("restored already")
-        mates = self.dev.alloc(2 * self.n_pairs, _lib.MATE_DTYPE)
-        check(lib().gk_mates_expand(self.dev.ctx, self.ptr, 2 * self.n_pairs, mates.ptr))
-        self.release()                      # stream-ordered: the expansion is queued before the block is reused
+        if self._words is not None:         # parked as they came: tabulated as such, and the sample's records again
+            from .packed import DeviceCompactMates
+            mates = DeviceCompactMates(self._words.dev, self._words, 2 * self.n_pairs)
+            self._words, self.ptr = None, 0
+        else:
+            mates = self.dev.alloc(2 * self.n_pairs, _lib.MATE_DTYPE)
+            check(lib().gk_mates_expand(self.dev.ctx, self.ptr, 2 * self.n_pairs, mates.ptr))
+            self.release()                  # stream-ordered: the expansion is queued before the block is reused
         tab = Tabulation(self.dindex, mates, novel_base=self.novel_base, dev=self.dev, spill=self.spill,
                          correction=self.correction)
         if (tab.n_valid, tab.n_ids, tab.n_novel) != self.expect:
@@ -291,7 +305,10 @@ class ParkedRecords:
         return SampleData(tab, self.index, None, ins_strings=self.ins_strings)
 
     def release(self) -> None:
-        if self.ptr:
+        if self._words is not None:
+            self._words.free()
+            self._words, self.ptr = None, 0
+        elif self.ptr:
             lib().gk_free(self.dev.ctx, self.ptr)
             self.ptr = 0
 

@@ -126,7 +126,7 @@ def _mapLoop(names, prepare, ahead, gk, gene_len, staging, dindex, index_ref, ex
         logger.info(f"[Graph] Filter mapping ({name})")
         handed_off = False
         if pack is not None:
-            # pinned records -> HBM on the copier's stream: compact words copied and expanded there, or the 128-byte records
+            # pinned records -> HBM on the copier's stream: the compact words as they are, or the 128-byte records
             compact = pack.pop("compact", None)
             mates = compact.toDevice(copier, wait=True) if compact is not None else copier.put(pack["records"])
             data = extractVariantFromPacked(pack, gk, dev=dev, dindex=dindex, mates=mates)

@@ -21,6 +21,7 @@ order.
 from __future__ import annotations
 
 import re
+import threading
 
 import numpy as np
 
@@ -539,10 +540,61 @@ def _rankWithin(group: np.ndarray, sel: np.ndarray) -> np.ndarray:
     return (before - before[first]).astype(np.int64)
 
 
+class DeviceCompactMates:
+    """The compact words of a sample in HBM (``CompactMates.toDevice``): what the tabulation (``gk_tabulate_compact``),
+    the depth (``gk_depth_compact``) and a parked sample (``hisat2.ParkedRecords``) read as they are.  ``size`` is the
+    number of mates, as for a buffer of records.  Whoever still wants the 128-byte records asks for ``ptr`` (their
+    device address) or ``download()``: they are written on first use (``gk_mates_expand`` on the words' own context,
+    waited for), once, whichever thread asks first -- several typing lanes may share one resident sample."""
+
+    def __init__(self, dev, words, n_mates: int):
+        from ._lib import MATE_DTYPE
+        self.dev, self.words, self.n_mates = dev, words, int(n_mates)
+        self.dtype, self.shape = MATE_DTYPE, (self.n_mates,)
+        self._records = None
+        self._lock = threading.Lock()
+
+    @property
+    def size(self) -> int:
+        return self.n_mates
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes held in HBM right now."""
+        return int(self.words.nbytes if self.words is not None else 0) + int(self._records.nbytes if self._records is not None else 0)
+
+    def records(self):
+        """The device buffer of the expanded records (``MATE_DTYPE``), made on first use."""
+        with self._lock:
+            if self._records is None:
+                from ._lib import check, lib
+                if self.words is None:
+                    raise ValueError("the compact records have been released already")
+                records = self.dev.alloc(self.n_mates, self.dtype)
+                check(lib().gk_mates_expand(self.dev.ctx, self.words.ptr, self.n_mates, records.ptr))
+                self.dev.sync()         # whoever reads them may be on another stream
+                self._records = records
+            return self._records
+
+    @property
+    def ptr(self) -> int:
+        return self.records().ptr
+
+    def download(self, count: int | None = None, offset: int = 0) -> np.ndarray:
+        return self.records().download(count, offset)
+
+    def free(self) -> None:
+        with self._lock:
+            for b in (self.words, self._records):
+                if b is not None:
+                    b.free()
+            self.words = self._records = None
+
+
 class CompactMates:
     """Packed records in compact form on the host (``gk_mates_compact_host``): uint32 word offsets ``[n_mates + 1]``
     followed by the words the mates use -- ~30 bytes per mate instead of 128.  This is what crosses PCIe for a sample;
-    ``toDevice`` queues the copy and the expansion into 128-byte records (``gk_mates_expand``) on a context's stream."""
+    ``toDevice`` queues the copy on a context's stream and hands out the words in HBM (``DeviceCompactMates``)."""
 
     def __init__(self, records: np.ndarray, threads: int = 4):
         import ctypes as C
@@ -559,16 +611,14 @@ class CompactMates:
     def nbytes(self) -> int:
         return int(self.words.nbytes)
 
-    def toDevice(self, dev, wait: bool = False):
-        """The 128-byte records in HBM (a device buffer of ``MATE_DTYPE``): compact words copied (queued on ``dev``'s
-        stream; ``wait``: synchronised) and expanded there."""
+    def toDevice(self, dev, wait: bool = False) -> DeviceCompactMates:
+        """The compact words in HBM: copied on ``dev``'s stream (queued; ``wait``: synchronised) and left as they are --
+        the tabulation and the depth read them directly.  A kernel of ANOTHER stream may read them only after the copy
+        is complete: ``wait``, or a ``dev.sync()`` of the caller's."""
         import ctypes as C
-        from ._lib import MATE_DTYPE, check, lib
-        compact = dev.alloc(len(self.words), np.uint32)
-        check(lib().gk_h2d_async(dev.ctx, compact.ptr, C.c_void_p(self.words.ctypes.data), self.words.nbytes))
-        mates = dev.alloc(self.n_mates, MATE_DTYPE)
-        check(lib().gk_mates_expand(dev.ctx, compact.ptr, self.n_mates, mates.ptr))
-        compact.free()          # the pool reuses the block in stream order: after the expansion
+        from ._lib import check, lib
+        words = dev.alloc(len(self.words), np.uint32)
+        check(lib().gk_h2d_async(dev.ctx, words.ptr, C.c_void_p(self.words.ctypes.data), self.words.nbytes))
         if wait:
             dev.sync()
-        return mates
+        return DeviceCompactMates(dev, words, self.n_mates)

@@ -92,9 +92,11 @@ def compatLaunch(n_rows: int, n_allele: int, n_ids: float, out_bytes: int = 8) -
     return 4.0 * n_ids + 16.0 * n_rows + float(out_bytes + 1) * n_rows * n_allele, 4.0 * n_ids * n_allele
 
 
-def tabLaunch(n_pairs: int, n_valid: int, n_ids: int) -> tuple[float, float]:
-    """reads 2 x 128-byte records per pair, writes the four id lists."""
-    return 256.0 * n_pairs + 4.0 * n_ids + 22.0 * n_valid, 0.0
+def tabLaunch(n_pairs: int, n_valid: int, n_ids: int, record_bytes: float | None = None) -> tuple[float, float]:
+    """reads the sample's records -- ``record_bytes``: the compact words and their offsets (``gk_tabulate_compact``,
+    ~60 bytes per pair on 150-base reads); None: 2 x 128-byte records per pair -- and writes the four id lists."""
+    read = 256.0 * n_pairs if record_bytes is None else float(record_bytes)
+    return read + 4.0 * n_ids + 22.0 * n_valid, 0.0
 
 
 def setsumLaunch(n_rows: int, n_sets: int, c: int, n_distinct: int) -> tuple[float, float]:
@@ -136,7 +138,7 @@ def _priced(kernel: str, calls: list[tuple]) -> tuple[float, float, str, float]:
         elif kernel == "compat_rows8":       # 8 rows per wave: the lists in, 9 bytes per entry out -- an HBM stream
             b, o = compatLaunch(*c[1:5])[0], 0.0
         elif kernel == "tab_count":
-            b, o = tabLaunch(*c[1:4])
+            b, o = tabLaunch(*c[1:5])
         elif kernel in ("fraction_chunks", "setsum_leaves"):
             b, o = setsumLaunch(*c[1:5])
         else:

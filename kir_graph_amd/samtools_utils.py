@@ -47,8 +47,13 @@ def depthOfSample(data, gene_len: dict[str, int], file_depth: str | None = None,
     off = np.zeros(len(genes) + 1, dtype=np.int64)
     np.cumsum(lens, out=off[1:])
     depth = np.empty(int(off[-1]), dtype=np.uint32)
-    check(lib().gk_depth(tab.dev.ctx, tab.handle, tab.mates.ptr, int(multiple), off.ctypes.data, len(genes),
-                         depth.ctypes.data))
+    words = getattr(tab.mates, "words", None) if hasattr(tab.mates, "records") else None
+    if words is not None:       # packed.DeviceCompactMates: the CIGARs are read out of the compact words
+        check(lib().gk_depth_compact(tab.dev.ctx, tab.handle, words.ptr, int(multiple), off.ctypes.data, len(genes),
+                                     depth.ctypes.data))
+    else:
+        check(lib().gk_depth(tab.dev.ctx, tab.handle, tab.mates.ptr, int(multiple), off.ctypes.data, len(genes),
+                             depth.ctypes.data))
     if file_depth:
         names = (C.c_char_p * len(genes))(*[g.encode() for g in genes])
         check(lib().gk_depth_write_tsv(file_depth.encode(), names, off.ctypes.data, len(genes), depth.ctypes.data))
