@@ -536,6 +536,25 @@ int gk_boot_row_counts(gk_ctx* ctx, int64_t n_rows, int32_t n_boot, int32_t boot
 int gk_weighted_sums(gk_ctx* ctx, gk_dptr d_V, int64_t ld, int64_t n_rows, int32_t n_sets, gk_dptr d_W, int64_t ldw,
                      int32_t n_boot, double* out);
 
+/* Fit report of a likelihood call (no reference counterpart; extends typing_mulit_allele.py:540-542, 569): how the called
+ * set explains the reads, in exact integers, from the u8 mismatch table the search left in HBM -- no search runs again.
+ * d_miss8 uint8 [n_table_cols][ldm], 16-byte aligned; rows r >= n_rows of a column may hold anything.
+ * gk_call_fit: cols = the n_cols distinct called columns (host, 1 .. 16, any order).  Per row r < n_rows, with
+ *   b_k = d_miss8[cols[k]][r]: m1 = min_k b_k, A = {k : b_k == m1}, second = the smallest b_j with j outside A.
+ *   hist_out[i], i < 16: rows with m1 == i; [16]: 16 <= m1 <= 254; [17]: m1 == 255 (a count >= 100 or a product out of
+ *   range).  m_out[0] = sum_r m1, bytes as stored.  col_out[3 k + 0 .. 2]: best = rows with k in A, unique = rows with
+ *   A == {k}, only = the sum over those rows of second - m1 (0 when n_cols == 1): M without column k minus M.
+ *   d_min, when not 0: uint8 [>= n_rows], 16-byte aligned, d_min[r] = m1; entries r >= n_rows are not written.
+ * gk_call_fit_extra: with_out[a] = sum_{r < n_rows} min(d_min[r], d_miss8[a][r]) for every column a of the table.
+ * Both wait for their result.  GK_ERR_ARG, and nothing launched: n_rows < 1 or >= 2^31, ldm < n_rows or ldm % 64 != 0,
+ * n_table_cols < 1, n_cols outside 1 .. 16, a column outside 0 .. n_table_cols - 1 or listed twice, a null output, a table
+ * or d_min that is not 16-byte aligned. */
+int gk_call_fit(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32_t n_table_cols, const int32_t* cols,
+                int32_t n_cols, uint64_t* hist_out /* [18] */, uint64_t* col_out /* [n_cols][3] */, uint64_t* m_out /* [1] */,
+                gk_dptr d_min);
+int gk_call_fit_extra(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32_t n_table_cols, gk_dptr d_min,
+                      uint64_t* with_out /* [n_table_cols] */);
+
 /* ---- host ingest (no GPU): name-collated SAM text -> gk_mate records.
  * Native form of readPair (hisat2.py:228-276), of the field reads of filterRead / getNH (551-569,
  * 95-100) and of the CIGAR / MD / Zs consistency checks of recordToRawVariant (279-515).  Text is fed

@@ -741,6 +741,29 @@ class DeviceModel:
             raise KeyError(f"alleles {missing} are not among the {len(cols)} columns of this model's table")
         return self._L, self.n_rows, _i32(at)
 
+    def missFor(self, ids: np.ndarray) -> tuple[DeviceBuffer, int, int, np.ndarray] | None:
+        """(the u8 mismatch table the search left in HBM, its leading dimension, its number of columns, ``ids`` as column
+        numbers of that table): ``tableFor``'s counterpart for ``miss8``.  A model whose tables hold a list of alleles hands
+        out THOSE and translates the ordinals -- never the all-allele tables ``_allColumns`` would write.  None for a model
+        without a mismatch table (``GK_SEARCH=exact``, 16 M rows or more)."""
+        ids = np.asarray(ids, dtype=np.int64)
+        self.finishLog()
+        if self.miss8 is None:
+            return None
+        cols = self._table_cols
+        if cols is None:
+            return self.miss8, self.ldm, self.n_allele, _i32(ids)
+        at = np.minimum(np.searchsorted(cols, ids), len(cols) - 1)
+        if not np.array_equal(cols[at], ids):
+            missing = np.unique(ids[cols[at] != ids])[:8].tolist()
+            raise KeyError(f"alleles {missing} are not among the {len(cols)} columns of this model's table")
+        return self.miss8, self.ldm, len(cols), _i32(at)
+
+    @property
+    def tableColumns(self) -> np.ndarray | None:
+        """The allele ordinals of the tables' columns when they hold a list of alleles (exon-first), else None."""
+        return self._table_cols
+
     def setmax(self, ids: np.ndarray) -> np.ndarray:
         """Host copy of allele_prob (R x T) for the given sets -- API parity only, not on the hot path."""
         ids = _i32(ids)

@@ -23,6 +23,7 @@ import numpy as np
 from . import _lib
 from ._lib import Device
 from .call_bootstrap import MAX_BOOT, MAX_TOP, CallBootstrap, bootstrapCall, homoFactor
+from .call_fit import MAX_EXTRA, CallFit, fitCall
 from .engine import PreparedGene, PreparedSample, searchMode
 from .hisat2 import SampleData, loadCompact, loadReadsAndVariantsData
 from .typing_em import (EmBootstrap, Hisat2AlleleResult, bootstrapEM, callsByAbundance, candidateSetsDistinct,
@@ -217,11 +218,17 @@ class TypingWithPosNegAllele(_OnLane):
     def __init__(self, filename_variant_json, top_n: int = 300, multiple: bool = False, exon_first: bool = False,
                  exon_only: bool = False, exon_candidate_threshold: float = .9, variant_correction: bool = False,
                  device: Device | None = None, call_bootstrap: int = 0, call_bootstrap_seed: int = 2022,
-                 call_bootstrap_top: int = 32):
+                 call_bootstrap_top: int = 32, call_fit: bool = False, call_fit_extra: int = 3):
         """``call_bootstrap`` > 0: every gene's adopted result is rescored in that many read-bootstrap replicates
         (``call_bootstrap.bootstrapCall`` on its first ``call_bootstrap_top`` candidate sets; ``self.call_bootstrap``:
-        gene -> ``CallBootstrap``); 0: nothing but the point result, and nothing more is launched."""
+        gene -> ``CallBootstrap``); 0: nothing but the point result, and nothing more is launched.
+        ``call_fit``: every gene's adopted result gets its fit report (``call_fit.fitCall`` with ``call_fit_extra`` extra
+        alleles listed; ``self.call_fit``: gene -> ``CallFit``); False: nothing more is launched."""
         super().__init__()
+        if not 0 <= int(call_fit_extra) <= MAX_EXTRA:
+            raise ValueError(f"call_fit_extra: the extra alleles listed must lie in 0 .. {MAX_EXTRA}")
+        self._call_fit = (bool(call_fit), int(call_fit_extra))
+        self.call_fit: dict[str, CallFit] = {}
         if not 0 <= int(call_bootstrap) <= MAX_BOOT:
             raise ValueError(f"call_bootstrap: the number of replicates must lie in 0 .. {MAX_BOOT}")
         if not 1 <= int(call_bootstrap_top) <= MAX_TOP:
@@ -375,6 +382,7 @@ class TypingWithPosNegAllele(_OnLane):
                 else:
                     self._result[gene], final = p["results"], p["final"]
                 self._bootstrapCall(gene, cn, final)
+                self._fitCall(gene, cn, final)
                 yield gene, _calls(gene, final), p["typ_e"].getReadsNum()
         calls = self._collect(entries(), min_reads_num)
         self._result = {gene: self._result[gene] for gene, _ in todo if gene in self._result}
@@ -428,6 +436,7 @@ class TypingWithPosNegAllele(_OnLane):
                 res = typ.result[-1] if job is not None else typ.typing(cn)     # no rows: the reference's empty results
                 self._result[gene] = typ.result
                 self._bootstrapCall(gene, cn, res)
+                self._fitCall(gene, cn, res)
                 yield gene, _calls(gene, res), typ.getReadsNum()
         return self._collect(calls(), min_reads_num)
 
@@ -491,7 +500,22 @@ class TypingWithPosNegAllele(_OnLane):
         res = typ.typing(cn)
         self._result[gene] = typ.result
         self._bootstrapCall(gene, cn, res)
+        self._fitCall(gene, cn, res)
         return _calls(gene, res), typ.getReadsNum()
+
+    def _fitCall(self, gene: str, cn: int, result) -> None:
+        """With ``call_fit``: the fit report of the result just adopted for ``gene`` (while the sample's tables are in
+        HBM).  A gene without rows, with a failed result or with ``cn == 0`` gets no entry."""
+        on, extra = self._call_fit
+        if not on:
+            return
+        self.call_fit.pop(gene, None)
+        g = self._data.index.gene_id.get(gene)
+        if cn <= 0 or g is None or result is None or result.isFail():
+            return
+        fit = fitCall(result, extra, names=self._data.index.tables[g].alleles)
+        if fit is not None:
+            self.call_fit[gene] = fit
 
     def _bootstrapCall(self, gene: str, cn: int, result) -> None:
         """With ``call_bootstrap`` > 0: the read bootstrap of the result just adopted for ``gene`` (while the sample's
@@ -642,6 +666,9 @@ def selectKirTypingModel(method: str, filename_variant_json, **kwargs: Any) -> T
         kwargs.pop("call_bootstrap_top", None)
         if kwargs.pop("call_bootstrap", 0):
             raise ValueError(f"call_bootstrap: only the likelihood strategies rescore candidate sets, not {method!r}")
+        kwargs.pop("call_fit_extra", None)
+        if kwargs.pop("call_fit", False):
+            raise ValueError(f"call_fit: only the likelihood strategies report the fit of a call, not {method!r}")
     if method in ("full", "pv"):
         return TypingWithPosNegAllele(filename_variant_json, **kwargs)
     if method.startswith("pv_exonfirst"):

@@ -256,6 +256,16 @@ def writeCallConfidence(name: str, bootstrap: dict) -> str:
     return name + ".call_confidence.tsv"
 
 
+def writeCallFit(name: str, fits: dict) -> str:
+    """``{name}.fit.tsv`` of one sample typed by a likelihood strategy with ``--call-fit``: per gene and distinct called
+    allele how the called set explains the reads, what the allele contributes, and the alleles that would explain the
+    most as one more copy (``call_fit.callFitText``)."""
+    from .call_fit import callFitText
+    with open(name + ".fit.tsv", "w") as f:
+        f.write(callFitText(fits))
+    return name + ".fit.tsv"
+
+
 def discoverAfterTyping(typer, called_alleles: list[str], name: str, result: str, index_ref: str) -> None:
     """Novel-variant discovery of one typed sample, on its tabulation in HBM (novel_discover.discoverSample):
     ``{result}.novel.variant.tsv / .tsv / .fa / .bam / .txt``, the reads piled up from ``{name}.no_multi.bam``."""
@@ -271,7 +281,7 @@ def discoverAfterTyping(typer, called_alleles: list[str], name: str, result: str
 
 def sampleTyper(method: str, release: bool = True, novel_index: str | None = None, bootstrap: int = 0,
                 bootstrap_seed: int = 2022, call_bootstrap: int = 0, call_bootstrap_seed: int = 2022,
-                call_bootstrap_top: int = 32) -> "cohort.SampleTyper":
+                call_bootstrap_top: int = 32, call_fit: bool = False, call_fit_extra: int = 3) -> "cohort.SampleTyper":
     """The typing stage of this process (``cohort.SampleTyper``: the sample lanes, search slots, urgent preamble and
     blocking waits that ``bench.py`` measures), finishing every sample the reference's way: its two files written, its
     tabulation released.  Submit ``(SampleData or hand-off file, copy numbers, (name, cn_file))``.
@@ -280,7 +290,9 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
     ``bootstrap`` > 0 (``--em-bootstrap``, EM strategy): the typer also runs that many read-bootstrap replicates and the
     finish step writes ``{result}.confidence.tsv``.
     ``call_bootstrap`` > 0 (``--call-bootstrap``, likelihood strategies): the typer rescores every gene's candidate sets
-    in that many read-bootstrap replicates and the finish step writes ``{result}.call_confidence.tsv``."""
+    in that many read-bootstrap replicates and the finish step writes ``{result}.call_confidence.tsv``.
+    ``call_fit`` (``--call-fit``, likelihood strategies): the typer reports the fit of every gene's called set, with
+    ``call_fit_extra`` extra alleles listed, and the finish step writes ``{result}.fit.tsv``."""
     def finish(typer, called_alleles, warning_genes, item):
         name, cn_file, source = item
         result = name + typingSuffix(name, cn_file, method)
@@ -301,12 +313,16 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
                 writeConfidence(result, typer.bootstrap)
             if call_bootstrap > 0:
                 writeCallConfidence(result, typer.call_bootstrap)
+            if call_fit:
+                writeCallFit(result, typer.call_fit)
         return written
 
     extra = {"bootstrap": bootstrap, "bootstrap_seed": bootstrap_seed} if bootstrap > 0 else {}
     if call_bootstrap > 0:
         extra.update(call_bootstrap=call_bootstrap, call_bootstrap_seed=call_bootstrap_seed,
                      call_bootstrap_top=call_bootstrap_top)
+    if call_fit:
+        extra.update(call_fit=True, call_fit_extra=call_fit_extra)
     return cohort.SampleTyper(method, finish=finish, **extra)
 
 
@@ -394,6 +410,12 @@ def createParser() -> argparse.ArgumentParser:
     p.add_argument("--call-bootstrap-seed", type=int, default=2022, help="Seed of the call bootstrap's draws")
     p.add_argument("--call-bootstrap-top", type=int, default=32,
                    help="Candidate sets of a gene the call bootstrap rescores (1 .. 256, in rank order)")
+    p.add_argument("--call-fit", action="store_true",
+                   help="Likelihood strategies (full / pv / exonfirst) only: report how the called set of every gene explains "
+                        "the reads; writes {result}.fit.tsv (reads without / with mismatches, per called allele the reads it "
+                        "explains best and alone, the alleles that would explain the most as one more copy)")
+    p.add_argument("--call-fit-extra", type=int, default=3,
+                   help="Extra alleles the fit report lists per gene (0 .. 64; 0: none are looked for)")
     p.add_argument("--ranks", type=int, default=1,
                    help="Start this many rank processes (samples are sharded over them; ranks map to GPUs round robin, "
                         "so 3 x the GPU count keeps every GPU busy).  Not needed under torchrun / any launcher that "
@@ -415,6 +437,18 @@ def _callBootstrapArgs(args: argparse.Namespace) -> dict:
             "call_bootstrap_top": top}
 
 
+def _callFitArgs(args: argparse.Namespace) -> dict:
+    """The ``sampleTyper`` keywords of ``--call-fit`` (none when the flag is not given); a ``--call-fit-extra`` outside
+    0 .. 64 or the EM strategy is an error."""
+    if not getattr(args, "call_fit", False):
+        return {}
+    extra = int(getattr(args, "call_fit_extra", 3))
+    if not 0 <= extra <= 64 or args.allele_strategy in ("em", "report"):
+        raise ValueError("--call-fit needs a --call-fit-extra in 0 .. 64 and a likelihood strategy (--allele-strategy full, "
+                         "pv or exonfirst)")
+    return {"call_fit": True, "call_fit_extra": extra}
+
+
 def main(args: argparse.Namespace) -> None:
     if getattr(args, "cn_cohort", False):
         os.environ.setdefault("GK_SAMPLE_LANES", "3")      # samples wait in HBM for the pooled fit: the lanes' working sets stay small
@@ -431,6 +465,7 @@ def main(args: argparse.Namespace) -> None:
     if n_boot < 0 or (n_boot > 0 and args.allele_strategy not in ("em", "report")):
         raise ValueError("--em-bootstrap needs a positive count and --allele-strategy em (or report)")
     _callBootstrapArgs(args)
+    _callFitArgs(args)
 
     if not args.input_csv:
         if not args.r1 and not args.alignment:
@@ -503,7 +538,8 @@ def _runCohort(args, names, reads, cn_files, index, index_ref, cohort_name, comm
     pooled_fit = args.cn_cohort and not all(cn_files)
     novel = getattr(args, "novel_discovery", False)
     lanes = sampleTyper(method, novel_index=index_ref if novel else None, bootstrap=int(getattr(args, "em_bootstrap", 0) or 0),
-                        bootstrap_seed=int(getattr(args, "em_bootstrap_seed", 2022)), **_callBootstrapArgs(args))
+                        bootstrap_seed=int(getattr(args, "em_bootstrap_seed", 2022)), **_callBootstrapArgs(args),
+                        **_callFitArgs(args))
     try:
         allele_files, my_cn = _typeShare(args, lanes, pick(names), pick(reads), my_cn, pick, index, index_ref, cohort_name,
                                          comm, kwargs, pooled_fit)

@@ -371,6 +371,11 @@ class LazyNames:
     def __init__(self, ids: np.ndarray, id_to_allele: dict[int, str]):
         self._ids, self._map = ids, id_to_allele
 
+    @property
+    def names(self) -> dict[int, str]:
+        """Ordinal -> name of every allele of the model the ids belong to (not only of those in the sets)."""
+        return self._map
+
     def __len__(self) -> int:
         return len(self._ids)
 
