@@ -555,6 +555,31 @@ int gk_call_fit(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32
 int gk_call_fit_extra(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32_t n_table_cols, gk_dptr d_min,
                       uint64_t* with_out /* [n_table_cols] */);
 
+/* Per-allele coverage of a likelihood call (no reference counterpart; serves what the reference's --plot would draw, "not
+ * supported in this build"): WHERE along backbone `gene` the reads lie that the called set explains, in exact integers,
+ * from the u8 mismatch table the search left in HBM joined with the sample's records -- no search runs again.
+ * tab: the sample's tabulation, made from packed records (its pair sources and wide records are read, as by gk_depth).
+ * d_mates / d_compact: the records the tabulation was made from, 2 * n_pairs gk_mate or the compact form (as for
+ *   gk_tabulate_compact); exactly one of the two is not 0.
+ * d_rows int32 [n_rows]: the model's rows = indices of valid pairs, as gk_select_gene / gk_select_nonempty leave them, in
+ *   any order; row r of the table belongs to pair d_rows[r].  An index outside the tabulation's valid pairs marks nothing.
+ * d_miss8 uint8 [n_table_cols][ldm], 16-byte aligned; rows r >= n_rows of a column may hold anything.
+ * cols = the n_cols = K distinct called columns (host, 1 .. 16, any order).  Per row r < n_rows, with
+ *   b_k = d_miss8[cols[k]][r]: m1 = min_k b_k, A = {k : b_k == m1} (gk_call_fit's rule: bytes as stored, 255 included).
+ * depth_out uint32 [2 + 2 K][gene_len] (host): per track the number of mates whose aligned (M) bases cover the position,
+ *   counted as gk_depth counts them (both mates independently, no overlap removal, D not counted, runs clipped to
+ *   [0, gene_len), a mate whose ref is not `gene` skipped), over the rows
+ *   [0] informative: every row; [1] mismatch: m1 > 0; [2 + k] best_k: k in A; [2 + K + k] unique_k: A == {k}.
+ * The marks go into one track's difference array in a workgroup's LDS when gene_len + 1 words fit 144 KB (callcov_mark_lds),
+ * else, or with GK_CALLCOV=direct in the environment, straight into HBM (callcov_mark); the result is the same integers.
+ * Waits for its result.  GK_ERR_ARG, and nothing launched: both or neither of d_mates / d_compact, n_rows < 1 or >= 2^31,
+ * ldm < n_rows or ldm % 64 != 0, n_table_cols < 1, n_cols outside 1 .. 16, a column outside 0 .. n_table_cols - 1 or listed
+ * twice, gene_len outside 1 .. 2^24, gene not a backbone of the tabulation's index, a null tab / d_rows / cols / depth_out, a
+ * table that is not 16-byte aligned, a tabulation without pair sources (gk_tab_from_csr). */
+int gk_call_coverage(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compact, gk_dptr d_rows, int64_t n_rows,
+                     gk_dptr d_miss8, int64_t ldm, int32_t n_table_cols, const int32_t* cols, int32_t n_cols, int32_t gene,
+                     int64_t gene_len, uint32_t* depth_out /* [2 + 2 n_cols][gene_len] */);
+
 /* ---- host ingest (no GPU): name-collated SAM text -> gk_mate records.
  * Native form of readPair (hisat2.py:228-276), of the field reads of filterRead / getNH (551-569,
  * 95-100) and of the CIGAR / MD / Zs consistency checks of recordToRawVariant (279-515).  Text is fed

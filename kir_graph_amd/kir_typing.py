@@ -23,6 +23,7 @@ import numpy as np
 from . import _lib
 from ._lib import Device
 from .call_bootstrap import MAX_BOOT, MAX_TOP, CallBootstrap, bootstrapCall, homoFactor
+from .call_coverage import CallCoverage, coverCall
 from .call_fit import MAX_EXTRA, CallFit, fitCall
 from .engine import PreparedGene, PreparedSample, searchMode
 from .hisat2 import SampleData, loadCompact, loadReadsAndVariantsData
@@ -218,13 +219,22 @@ class TypingWithPosNegAllele(_OnLane):
     def __init__(self, filename_variant_json, top_n: int = 300, multiple: bool = False, exon_first: bool = False,
                  exon_only: bool = False, exon_candidate_threshold: float = .9, variant_correction: bool = False,
                  device: Device | None = None, call_bootstrap: int = 0, call_bootstrap_seed: int = 2022,
-                 call_bootstrap_top: int = 32, call_fit: bool = False, call_fit_extra: int = 3):
+                 call_bootstrap_top: int = 32, call_fit: bool = False, call_fit_extra: int = 3,
+                 call_coverage: bool = False, call_coverage_len: dict[str, int] | None = None):
         """``call_bootstrap`` > 0: every gene's adopted result is rescored in that many read-bootstrap replicates
         (``call_bootstrap.bootstrapCall`` on its first ``call_bootstrap_top`` candidate sets; ``self.call_bootstrap``:
         gene -> ``CallBootstrap``); 0: nothing but the point result, and nothing more is launched.
         ``call_fit``: every gene's adopted result gets its fit report (``call_fit.fitCall`` with ``call_fit_extra`` extra
-        alleles listed; ``self.call_fit``: gene -> ``CallFit``); False: nothing more is launched."""
+        alleles listed; ``self.call_fit``: gene -> ``CallFit``); False: nothing more is launched.
+        ``call_coverage``: every gene's adopted result gets its per-allele coverage (``call_coverage.coverCall``;
+        ``self.call_coverage``: gene -> ``CallCoverage``, None for a gene whose report could not be made);
+        ``call_coverage_len``: gene -> backbone length, needed with it.  The sample's records must still be in HBM
+        (``tab.mates``).  False: nothing more is launched."""
         super().__init__()
+        if call_coverage and not call_coverage_len:
+            raise ValueError("call_coverage: needs call_coverage_len, the backbone length of every gene")
+        self._call_coverage = (bool(call_coverage), dict(call_coverage_len or {}))
+        self.call_coverage: dict[str, CallCoverage | None] = {}
         if not 0 <= int(call_fit_extra) <= MAX_EXTRA:
             raise ValueError(f"call_fit_extra: the extra alleles listed must lie in 0 .. {MAX_EXTRA}")
         self._call_fit = (bool(call_fit), int(call_fit_extra))
@@ -383,6 +393,7 @@ class TypingWithPosNegAllele(_OnLane):
                     self._result[gene], final = p["results"], p["final"]
                 self._bootstrapCall(gene, cn, final)
                 self._fitCall(gene, cn, final)
+                self._coverCall(gene, cn, final)
                 yield gene, _calls(gene, final), p["typ_e"].getReadsNum()
         calls = self._collect(entries(), min_reads_num)
         self._result = {gene: self._result[gene] for gene, _ in todo if gene in self._result}
@@ -437,6 +448,7 @@ class TypingWithPosNegAllele(_OnLane):
                 self._result[gene] = typ.result
                 self._bootstrapCall(gene, cn, res)
                 self._fitCall(gene, cn, res)
+                self._coverCall(gene, cn, res)
                 yield gene, _calls(gene, res), typ.getReadsNum()
         return self._collect(calls(), min_reads_num)
 
@@ -501,6 +513,7 @@ class TypingWithPosNegAllele(_OnLane):
         self._result[gene] = typ.result
         self._bootstrapCall(gene, cn, res)
         self._fitCall(gene, cn, res)
+        self._coverCall(gene, cn, res)
         return _calls(gene, res), typ.getReadsNum()
 
     def _fitCall(self, gene: str, cn: int, result) -> None:
@@ -516,6 +529,30 @@ class TypingWithPosNegAllele(_OnLane):
         fit = fitCall(result, extra, names=self._data.index.tables[g].alleles)
         if fit is not None:
             self.call_fit[gene] = fit
+
+    def _coverCall(self, gene: str, cn: int, result) -> None:
+        """With ``call_coverage``: the per-allele coverage of the result just adopted for ``gene`` (while the sample's
+        tables and records are in HBM).  A gene without rows, with a failed result or with ``cn == 0`` gets no entry; one
+        whose report could not be made (no records in HBM, ...) gets None."""
+        on, lengths = self._call_coverage
+        if not on:
+            return
+        self.call_coverage.pop(gene, None)
+        index = self._data.index
+        g = index.gene_id.get(gene)
+        if cn <= 0 or g is None or result is None or result.isFail():
+            return
+        if gene not in lengths:
+            raise ValueError(f"call_coverage: no backbone length for {gene}")
+        if getattr(self._data.tab, "mates", None) is None:      # a hand-off file, or released: said once per sample
+            if not getattr(self, "_coverage_warned", False):
+                self._coverage_warned = True
+                logger.warning("[Allele] call coverage: the sample's records are not in HBM (a hand-off file, or released); "
+                               "no gene of it is reported")
+            self.call_coverage[gene] = None
+            return
+        self.call_coverage[gene] = coverCall(result, lengths[gene], index.exons.get(gene, []), index.tables[g],
+                                             names=index.tables[g].alleles)
 
     def _bootstrapCall(self, gene: str, cn: int, result) -> None:
         """With ``call_bootstrap`` > 0: the read bootstrap of the result just adopted for ``gene`` (while the sample's
@@ -669,6 +706,9 @@ def selectKirTypingModel(method: str, filename_variant_json, **kwargs: Any) -> T
         kwargs.pop("call_fit_extra", None)
         if kwargs.pop("call_fit", False):
             raise ValueError(f"call_fit: only the likelihood strategies report the fit of a call, not {method!r}")
+        kwargs.pop("call_coverage_len", None)
+        if kwargs.pop("call_coverage", False):
+            raise ValueError(f"call_coverage: only the likelihood strategies report the coverage of a call, not {method!r}")
     if method in ("full", "pv"):
         return TypingWithPosNegAllele(filename_variant_json, **kwargs)
     if method.startswith("pv_exonfirst"):

@@ -165,7 +165,8 @@ def _mapLoop(names, prepare, ahead, gk, gene_len, staging, dindex, index_ref, ex
 
 def releaseInputs(data: SampleData, keep_records: bool = False, keep_text: bool = False) -> None:
     """Drop what only the by-products and the depth needed: the SAM text of the pairs (host; unless ``keep_text``) and
-    the packed records (HBM, 256 B per pair; unless ``keep_records``).  The tabulation's lists stay for typing."""
+    the packed records (HBM: the compact words, ~60 B per pair, or 256 B per pair where a sample arrived as 128-byte
+    records; unless ``keep_records``).  The tabulation's lists stay for typing."""
     if not keep_text:
         data.pairs_text = None
     data._reads = None
@@ -266,6 +267,23 @@ def writeCallFit(name: str, fits: dict) -> str:
     return name + ".fit.tsv"
 
 
+def writeCallCoverage(name: str, covers: dict, depth: bool = False) -> list[str]:
+    """``{name}.coverage.tsv`` of one sample typed by a likelihood strategy with ``--call-coverage``: per gene, region and
+    distinct called allele where the reads lie that the called set explains (``call_coverage.callCoverageText``), and with
+    ``depth`` (``--call-coverage-depth``) ``{name}.coverage.depth.tsv``: every track as runs of equal depth.  A gene
+    whose report could not be made (None) is left out: a sample without records in HBM gets the headers alone."""
+    from .call_coverage import callCoverageDepthText, callCoverageText
+    covers = {gene: c for gene, c in covers.items() if c is not None}
+    files = [name + ".coverage.tsv"]
+    with open(files[0], "w") as f:
+        f.write(callCoverageText(covers))
+    if depth:
+        files.append(name + ".coverage.depth.tsv")
+        with open(files[1], "w") as f:
+            f.write(callCoverageDepthText(covers))
+    return files
+
+
 def discoverAfterTyping(typer, called_alleles: list[str], name: str, result: str, index_ref: str) -> None:
     """Novel-variant discovery of one typed sample, on its tabulation in HBM (novel_discover.discoverSample):
     ``{result}.novel.variant.tsv / .tsv / .fa / .bam / .txt``, the reads piled up from ``{name}.no_multi.bam``."""
@@ -281,7 +299,9 @@ def discoverAfterTyping(typer, called_alleles: list[str], name: str, result: str
 
 def sampleTyper(method: str, release: bool = True, novel_index: str | None = None, bootstrap: int = 0,
                 bootstrap_seed: int = 2022, call_bootstrap: int = 0, call_bootstrap_seed: int = 2022,
-                call_bootstrap_top: int = 32, call_fit: bool = False, call_fit_extra: int = 3) -> "cohort.SampleTyper":
+                call_bootstrap_top: int = 32, call_fit: bool = False, call_fit_extra: int = 3,
+                call_coverage: bool = False, call_coverage_depth: bool = False,
+                gene_len: dict[str, int] | None = None) -> "cohort.SampleTyper":
     """The typing stage of this process (``cohort.SampleTyper``: the sample lanes, search slots, urgent preamble and
     blocking waits that ``bench.py`` measures), finishing every sample the reference's way: its two files written, its
     tabulation released.  Submit ``(SampleData or hand-off file, copy numbers, (name, cn_file))``.
@@ -292,7 +312,11 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
     ``call_bootstrap`` > 0 (``--call-bootstrap``, likelihood strategies): the typer rescores every gene's candidate sets
     in that many read-bootstrap replicates and the finish step writes ``{result}.call_confidence.tsv``.
     ``call_fit`` (``--call-fit``, likelihood strategies): the typer reports the fit of every gene's called set, with
-    ``call_fit_extra`` extra alleles listed, and the finish step writes ``{result}.fit.tsv``."""
+    ``call_fit_extra`` extra alleles listed, and the finish step writes ``{result}.fit.tsv``.
+    ``call_coverage`` (``--call-coverage``, likelihood strategies; ``gene_len``: backbone lengths, needed with it): the
+    typer reports the per-allele coverage of every gene's called set from the sample's records, which must still be in
+    HBM (``mapSamples(keep_records=True)``), and the finish step writes ``{result}.coverage.tsv`` -- with
+    ``call_coverage_depth`` (``--call-coverage-depth``) also ``{result}.coverage.depth.tsv``."""
     def finish(typer, called_alleles, warning_genes, item):
         name, cn_file, source = item
         result = name + typingSuffix(name, cn_file, method)
@@ -315,6 +339,8 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
                 writeCallConfidence(result, typer.call_bootstrap)
             if call_fit:
                 writeCallFit(result, typer.call_fit)
+            if call_coverage:
+                writeCallCoverage(result, typer.call_coverage, depth=call_coverage_depth)
         return written
 
     extra = {"bootstrap": bootstrap, "bootstrap_seed": bootstrap_seed} if bootstrap > 0 else {}
@@ -323,6 +349,8 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
                      call_bootstrap_top=call_bootstrap_top)
     if call_fit:
         extra.update(call_fit=True, call_fit_extra=call_fit_extra)
+    if call_coverage:
+        extra.update(call_coverage=True, call_coverage_len=gene_len)
     return cohort.SampleTyper(method, finish=finish, **extra)
 
 
@@ -416,6 +444,14 @@ def createParser() -> argparse.ArgumentParser:
                         "explains best and alone, the alleles that would explain the most as one more copy)")
     p.add_argument("--call-fit-extra", type=int, default=3,
                    help="Extra alleles the fit report lists per gene (0 .. 64; 0: none are looked for)")
+    p.add_argument("--call-coverage", action="store_true",
+                   help="Likelihood strategies (full / pv / exonfirst) only: report where along every gene the reads lie that "
+                        "its called set explains; writes {result}.coverage.tsv (per region -- upstream, exons, introns, "
+                        "downstream -- and called allele the bases of the reads it explains best and alone, and its private "
+                        "sites no read of its own covers).  The sample's records stay in HBM until it is typed")
+    p.add_argument("--call-coverage-depth", action="store_true",
+                   help="Also write {result}.coverage.depth.tsv: every coverage track as runs of equal depth (implies "
+                        "--call-coverage)")
     p.add_argument("--ranks", type=int, default=1,
                    help="Start this many rank processes (samples are sharded over them; ranks map to GPUs round robin, "
                         "so 3 x the GPU count keeps every GPU busy).  Not needed under torchrun / any launcher that "
@@ -449,6 +485,20 @@ def _callFitArgs(args: argparse.Namespace) -> dict:
     return {"call_fit": True, "call_fit_extra": extra}
 
 
+def _callCoverageArgs(args: argparse.Namespace, index_ref: str | None = None) -> dict:
+    """The ``sampleTyper`` keywords of ``--call-coverage`` / ``--call-coverage-depth`` (none when neither is given; the
+    backbone lengths are read when ``index_ref`` is); the EM strategy is an error."""
+    depth = bool(getattr(args, "call_coverage_depth", False))
+    if not (depth or getattr(args, "call_coverage", False)):
+        return {}
+    if args.allele_strategy in ("em", "report"):
+        raise ValueError("--call-coverage needs a likelihood strategy (--allele-strategy full, pv or exonfirst)")
+    out = {"call_coverage": True, "call_coverage_depth": depth}
+    if index_ref is not None:
+        out["gene_len"] = readLocusLengths(index_ref)
+    return out
+
+
 def main(args: argparse.Namespace) -> None:
     if getattr(args, "cn_cohort", False):
         os.environ.setdefault("GK_SAMPLE_LANES", "3")      # samples wait in HBM for the pooled fit: the lanes' working sets stay small
@@ -466,6 +516,7 @@ def main(args: argparse.Namespace) -> None:
         raise ValueError("--em-bootstrap needs a positive count and --allele-strategy em (or report)")
     _callBootstrapArgs(args)
     _callFitArgs(args)
+    _callCoverageArgs(args)
 
     if not args.input_csv:
         if not args.r1 and not args.alignment:
@@ -539,18 +590,20 @@ def _runCohort(args, names, reads, cn_files, index, index_ref, cohort_name, comm
     novel = getattr(args, "novel_discovery", False)
     lanes = sampleTyper(method, novel_index=index_ref if novel else None, bootstrap=int(getattr(args, "em_bootstrap", 0) or 0),
                         bootstrap_seed=int(getattr(args, "em_bootstrap_seed", 2022)), **_callBootstrapArgs(args),
-                        **_callFitArgs(args))
+                        **_callFitArgs(args), **_callCoverageArgs(args, index_ref))
     try:
         allele_files, my_cn = _typeShare(args, lanes, pick(names), pick(reads), my_cn, pick, index, index_ref, cohort_name,
-                                         comm, kwargs, pooled_fit)
+                                         comm, kwargs, pooled_fit, keep_records=bool(_callCoverageArgs(args)))
     finally:
         lanes.close()
     _mergeShare(my_cn, allele_files, cohort_name, comm)
 
 
-def _typeShare(args, lanes, names, reads, my_cn, pick, index, index_ref, cohort_name, comm, kwargs, pooled_fit):
+def _typeShare(args, lanes, names, reads, my_cn, pick, index, index_ref, cohort_name, comm, kwargs, pooled_fit,
+               keep_records=False):
     """Tabulation, depth, copy numbers of this rank's samples, each handed to the typing lanes as soon as its copy
-    numbers are known; returns (allele files, CN files) in the rank's sample order."""
+    numbers are known; returns (allele files, CN files) in the rank's sample order.  ``keep_records`` (``--call-coverage``):
+    a sample's records stay in HBM until the lane that typed it frees them."""
     allele_files: list[str] = []
     waiting: list[tuple[str, object]] = []      # samples that wait for the pooled copy-number fit
     depth_files: list[str] = []
@@ -558,7 +611,8 @@ def _typeShare(args, lanes, names, reads, my_cn, pick, index, index_ref, cohort_
     budget = int(float(os.environ.get("GK_RETAIN_GB", "64")) * 2**30)   # tabulations kept in HBM until the pooled fit
     samples = mapSamples(names, reads, index, index_ref, exon_region_only=args.cn_exon,
                          alignments=pick(args.alignment) if args.alignment else None,
-                         write_json=not args.no_variant_json, keep_records=pooled_fit and not args.step_skip_typing,
+                         write_json=not args.no_variant_json,
+                         keep_records=(pooled_fit or keep_records) and not args.step_skip_typing,
                          keep_text=getattr(args, "novel_discovery", False) and not args.step_skip_typing)
     for i, (_, name, data, depth_file) in enumerate(samples):
         depth_files.append(depth_file)
