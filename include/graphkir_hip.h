@@ -669,6 +669,32 @@ int gk_depth(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, int32_t multiple, const 
 int gk_depth_compact(gk_ctx* ctx, gk_tab* tab, gk_dptr d_compact, int32_t multiple, const int64_t* gene_off,
                      int32_t n_gene, uint32_t* depth_out);
 
+/* Read bootstrap of the copy-number stage (no reference counterpart; puts error bars on kir_cn.py:146-231, whose gene depths
+ * every typing call is conditioned on): gk_depth / gk_depth_compact for n_boot replicates at once, every mate of valid pair i
+ * counted d_W[b][i] times instead of once -- i the index of the tabulation's pair sources and NH, as in gk_depth -- and per
+ * (replicate, gene) the sum and two order statistics of the gene's selected positions, which is all that crosses PCIe.
+ * d_mates / d_compact: the records the tabulation was made from, as for gk_call_coverage; exactly one of the two is not 0.
+ * gene_off [n_gene + 1] (host): as for gk_depth, gene_off[0] == 0, every backbone 1 .. 2^24 positions, n_gene <= 256.
+ * d_W uint32 [n_boot][ldw], ldw >= n_valid (gk_boot_row_counts writes such a table); entries i >= n_valid are never read.
+ * The rules are gk_depth's: NH == 1 only unless `multiple`, M runs clipped to the mate's own backbone, D not counted, mates
+ *   counted independently, wide pairs from the tabulation's wide records; arithmetic mod 2^32.  With every weight 1
+ *   depth_out is gk_depth's / gk_depth_compact's integers.
+ * sel (host, nullable) uint8 [gene_off[n_gene]]: != 0 = the position counts in the statistics; NULL = every position.
+ * rank (host) int64 [n_gene][2]: two 0-based ranks among the gene's selected depths in ascending order.
+ * stat_out (host) uint32 [n_boot][n_gene][2]: the depths of those ranks (a radix select on the device: exact for any values,
+ *   ties included); sum_out (host) uint64 [n_boot][n_gene]: the sum of the selected depths.  A gene without a selected
+ *   position gives 0 / 0 / 0 and its ranks are ignored.
+ * depth_out (host, nullable) uint32 [n_boot][gene_off[n_gene]]: the tracks themselves (for the tests).
+ * The replicates are processed in slices of at most 1 GiB of difference arrays and scan copy; a replicate's result depends
+ *   on neither the slice nor n_boot.  Waits for its result.  n_valid == 0: zeros, nothing launched.
+ * GK_ERR_ARG, and nothing launched: both or neither of d_mates / d_compact, n_boot outside 1 .. 10000, ldw < n_valid, a rank
+ * < 0 or >= the gene's selected count when that count is > 0, a null tab / gene_off / d_W / rank / stat_out / sum_out, a
+ * backbone length outside 1 .. 2^24, a tabulation without pair sources (gk_tab_from_csr). */
+int gk_depth_weighted(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compact, int32_t multiple, const int64_t* gene_off,
+                      int32_t n_gene, gk_dptr d_W, int64_t ldw, int32_t n_boot, const uint8_t* sel, const int64_t* rank,
+                      uint32_t* stat_out /* [n_boot][n_gene][2] */, uint64_t* sum_out /* [n_boot][n_gene] */,
+                      uint32_t* depth_out /* nullable: [n_boot][gene_off[n_gene]] */);
+
 /* the `samtools depth -aa` text of that table ("gene\tpos\tdepth", positions 1-based, no header), as
  * samtools_utils.readSamtoolsDepth / kir_cn.predictSamplesCN read it (samtools_utils.py:17-22) */
 int gk_depth_write_tsv(const char* path, const char* const* genes, const int64_t* gene_off, int32_t n_genes,

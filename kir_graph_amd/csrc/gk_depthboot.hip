@@ -1,0 +1,372 @@
+// Read bootstrap of the copy-number stage (gk_depth_weighted): the depth of the sample with every valid pair counted
+// W[b][i] times instead of once, for a slice of replicates b at a time, and per (replicate, gene) the exact sum and two
+// order statistics of the gene's selected positions -- what p75 / mean / median of a replicate's depth track are made of.
+// Only those numbers cross PCIe; the tracks stay in HBM (depth_out exists for the tests).
+//
+// A mate counts as in depth_mark (gk_depth.hip, restated here: that file's digest pins committed profiles): pairs with
+// NH != 1 are skipped unless `multiple`; every M run [cur, cur + n) of the CIGAR, clipped to [0, gene_len) of the mate's own
+// backbone, adds +w at its start and -w at its end into the replicate's difference array; M and D advance cur, every other
+// operation does not; a pair in the wide format takes its CIGAR from the tabulation's wide records and is skipped when
+// there are none.  With every weight 1 the result is gk_depth's integers.  All adds are integer atomics mod 2^32: exact
+// whatever the schedule.
+//
+//   depthw_mark    one thread per mate (a workgroup holds 128 pairs) and per group of kBootPerThread replicates of the
+//                  slice (blockIdx.y).  The header is read once and the CIGAR of a 128-byte / compact record is held in 7
+//                  registers; per replicate the thread loads W[b][i] (the lanes of a wave read consecutive pairs), skips
+//                  on 0 and marks replicate b's array of total + 1 slots.  A wide pair's CIGAR (up to 128 operations) is
+//                  walked from its record per replicate: such pairs are rare.
+//   gk_scan_u32    ONE exclusive scan over the slice: a replicate's +w / -w cancel inside its own total + 1 slots, so
+//                  nothing carries over into the next replicate (as in gk_callcov.hip).
+//   depthw_finish  depth = excl + diff, in place; a replicate keeps its total + 1 slots, the last one holds 0.
+//   depthw_select  one workgroup per (replicate, gene): over the gene's selected positions the sum in 64 bits and the values
+//                  of two 0-based ranks by a radix select -- three passes over the track with LDS histograms of 11 / 11 /
+//                  10 bits, most significant first, both ranks carried through each pass (a histogram each from the second
+//                  pass on).  Nothing is sorted.  Exact for any uint32 values, ties included.
+//
+// The replicates are processed in slices so that the difference arrays and their scan copy stay within kDepthwBudget
+// (GK_TEST_HOOKS=depthw_budget=BYTES lowers it: the tests force several slices); a replicate's result does not depend on
+// the slice it falls in.  tests/test_gpu_cn_bootstrap.py takes its pair counts from the workgroup's 128 pairs and its depth
+// values from the digit boundaries 2^10 and 2^21: move them together.
+#include <algorithm>
+#include <cstddef>
+#include <vector>
+
+#include "gk_common.h"
+
+namespace {
+
+constexpr int kDwThreads = 256;
+constexpr int kMaxBoot = 10000;
+constexpr int kBootPerThread = 8;                           // replicates a thread of depthw_mark takes
+constexpr size_t kDepthwBudget = (size_t)1 << 30;           // bytes of a slice's difference arrays + their scan copy
+constexpr int64_t kDwMaxLen = 1ll << 24;                    // a backbone position has 24 bits in a variant key
+constexpr int kCigWords = GK_MAX_CIG / 2;                   // uint16 operations, two to a word
+constexpr int kDwInsWord = offsetof(gk_mate, ins) / 4;      // ins[0] of a record whose pair is in the wide array: its place there
+constexpr int kSelBins = 2048;                              // 11 bits; the last pass uses the first 1024
+static_assert(offsetof(gk_mate, cig) == 12 && offsetof(gk_mate, pos0) == 0 && sizeof(gk_mate) == 128, "gk_mate layout");
+static_assert(GK_MAX_CIG % 2 == 0, "the CIGAR of a record is held as whole words");
+
+struct DwSample {
+  const gk_mate* mates;              // the 128-byte records, or
+  const uint32_t* c_off;             // the compact form: word offsets [2 * n_pairs + 1] ...
+  const uint32_t* c_words;           // ... and the words
+  const gk_mate_wide* wide;
+  const int32_t* pair_src;
+  const uint8_t* pair_nh;
+  int64_t n_valid, n_pairs, n_spill;
+};
+
+template <bool kCompact>
+__global__ __launch_bounds__(kDwThreads) void depthw_mark(DwSample s, int multiple, const int64_t* __restrict__ gene_off,
+                                                          int n_gene, const uint32_t* __restrict__ W, int64_t ldw, int n_boot,
+                                                          int64_t slots, uint32_t* __restrict__ diff) {
+  const int64_t t = (int64_t)blockIdx.x * kDwThreads + threadIdx.x;
+  if (t >= 2 * s.n_valid) return;
+  const int64_t i = t >> 1;
+  const int side = (int)(t & 1);
+  if (!multiple && s.pair_nh[i] != 1) return;
+  const int64_t src = s.pair_src[i];
+  if (src < 0 || src >= s.n_pairs) return;
+  const int64_t at = 2 * src + side;
+  // header words 0 - 2 (pos0, flag | ref | nh, nm | n_cig | n_mm | n_ins), then the words that hold the CIGAR / the wide index
+  const uint32_t* w = kCompact ? s.c_words + s.c_off[at] : reinterpret_cast<const uint32_t*>(s.mates + at);
+  const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+  const uint32_t ref = (w1 >> 16) & 0xFFu, n_ops = (w2 >> 8) & 0xFFu;
+  if ((int)ref >= n_gene) return;
+  const int64_t base = gene_off[ref], len = gene_off[ref + 1] - base;
+  const gk_mate_wide* far = nullptr;
+  int n_cig = 0;
+  uint32_t cw[kCigWords];
+  if (n_ops == GK_SPILLED) {      // the pair is in the wide array (gk_mate_wide): its CIGAR is there
+    if (!s.wide) return;
+    const int64_t slot = kCompact ? w[3] : w[kDwInsWord];
+    if (slot >= s.n_spill) return;
+    far = s.wide + 2 * slot + side;
+    n_cig = far->n_cig < GK_WIDE_CIG ? far->n_cig : GK_WIDE_CIG;
+  } else {
+    n_cig = n_ops < GK_MAX_CIG ? (int)n_ops : GK_MAX_CIG;
+#pragma unroll
+    for (int k = 0; k < kCigWords; ++k) cw[k] = 2 * k < n_cig ? w[3 + k] : 0u;      // a compact mate ends with its last word
+  }
+  const int b0 = blockIdx.y * kBootPerThread;
+  const int b1 = min(b0 + kBootPerThread, n_boot);
+  for (int b = b0; b < b1; ++b) {
+    const uint32_t wt = W[(int64_t)b * ldw + i];
+    if (wt == 0) continue;
+    uint32_t* d = diff + (int64_t)b * slots + base;
+    int64_t cur = w0;
+    auto run = [&](uint32_t op, uint32_t n) {
+      if (op == GK_CIG_M) {
+        const int64_t a = cur < 0 ? 0 : cur, e = cur + n > len ? len : cur + n;
+        if (e > a) {
+          atomicAdd(&d[a], wt);
+          atomicAdd(&d[e], 0u - wt);      // -w (mod 2^32); a replicate's array has one slot past the end
+        }
+        cur += n;
+      } else if (op == GK_CIG_D) {
+        cur += n;
+      }
+    };
+    if (far) {
+      for (int c = 0; c < n_cig; ++c) run(far->cig[c] & 15u, far->cig[c] >> 4);
+    } else {
+#pragma unroll
+      for (int c = 0; c < GK_MAX_CIG; ++c) {
+        if (c < n_cig) {
+          const uint32_t cg = (c & 1) ? (cw[c >> 1] >> 16) : (cw[c >> 1] & 0xFFFFu);
+          run(cg & 15u, cg >> 4);
+        }
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kDwThreads) void depthw_finish(const uint32_t* __restrict__ excl, uint32_t* __restrict__ diff,
+                                                            int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * kDwThreads + threadIdx.x;
+  if (i < n) diff[i] += excl[i];
+}
+
+// The bin of `hist` (bins = per * kDwThreads) that holds 0-based rank k, and k's rank inside that bin -- by every thread
+// of the workgroup: a thread sums its `per` bins, adds up the sums before it, and the one whose bins hold k walks them.
+// k must be below the histogram's total.  Ends with a barrier.
+__device__ inline void sel_find(const uint32_t* hist, int per, uint32_t k, uint32_t* part, uint32_t* digit_out, uint32_t* rank_out) {
+  const int tid = threadIdx.x;
+  uint32_t mine = 0;
+  for (int j = 0; j < per; ++j) mine += hist[tid * per + j];
+  __syncthreads();      // part may still be read by a previous call
+  part[tid] = mine;
+  __syncthreads();
+  uint32_t before = 0;
+  for (int x = 0; x < tid; ++x) before += part[x];
+  if (k >= before && k - before < mine) {
+    uint32_t left = k - before;
+    for (int j = 0; j < per; ++j) {
+      const uint32_t c = hist[tid * per + j];
+      if (left < c) {
+        *digit_out = (uint32_t)(tid * per + j);
+        *rank_out = left;
+        break;
+      }
+      left -= c;
+    }
+  }
+  __syncthreads();
+}
+
+// Workgroup (g, b): gene g of replicate b.  depth: the slice's tracks, `slots` words per replicate; sel: nullable mask over
+// the concatenated positions; rank [n_gene][2]; stat [n_boot][n_gene][2], sum [n_boot][n_gene] of the slice.
+__global__ __launch_bounds__(kDwThreads) void depthw_select(const uint32_t* __restrict__ depth, int64_t slots,
+                                                            const int64_t* __restrict__ gene_off, const uint8_t* __restrict__ sel,
+                                                            const int64_t* __restrict__ rank, uint32_t* __restrict__ stat,
+                                                            unsigned long long* __restrict__ sum) {
+  __shared__ uint32_t hists[2 * kSelBins];      // one histogram per rank; the first pass shares the first
+  uint32_t* const hist[2] = {hists, hists + kSelBins};
+  __shared__ uint32_t part[kDwThreads];
+  __shared__ uint32_t digit[2], left[2], count;
+  __shared__ unsigned long long total;
+  const int tid = threadIdx.x, g = blockIdx.x, n_gene = gridDim.x;
+  const int64_t base = gene_off[g], len = gene_off[g + 1] - base;
+  const uint32_t* d = depth + (int64_t)blockIdx.y * slots + base;
+  const uint8_t* m = sel ? sel + base : nullptr;
+  const int64_t cell = (int64_t)blockIdx.y * n_gene + g;
+
+  // pass 1: bits 31 .. 21 of every selected value, their number and their sum
+  for (int x = tid; x < kSelBins; x += kDwThreads) hist[0][x] = 0;
+  if (tid == 0) {
+    count = 0;
+    total = 0;
+  }
+  __syncthreads();
+  uint32_t n_mine = 0;
+  unsigned long long s_mine = 0;
+  for (int64_t p = tid; p < len; p += kDwThreads) {
+    if (m && !m[p]) continue;
+    const uint32_t v = d[p];
+    atomicAdd(&hist[0][v >> 21], 1u);
+    s_mine += v;
+    ++n_mine;
+  }
+  if (n_mine) {
+    atomicAdd(&count, n_mine);
+    atomicAdd(&total, s_mine);
+  }
+  __syncthreads();
+  const uint32_t n = count;      // <= 2^24
+  if (n == 0) {      // no selected position: 0 / 0, the ranks are not looked at
+    if (tid == 0) {
+      stat[2 * cell] = stat[2 * cell + 1] = 0;
+      sum[cell] = 0;
+    }
+    return;
+  }
+  uint32_t k[2], prefix[2];
+  for (int j = 0; j < 2; ++j) {
+    const int64_t r = rank[2 * g + j];
+    k[j] = (uint32_t)(r < 0 ? 0 : r >= n ? n - 1 : r);      // checked on the host; clamped all the same
+    sel_find(hist[0], kSelBins / kDwThreads, k[j], part, &digit[j], &left[j]);
+    prefix[j] = digit[j];
+    k[j] = left[j];
+  }
+
+  // pass 2: bits 20 .. 10 of the values under each rank's first digit
+  for (int x = tid; x < 2 * kSelBins; x += kDwThreads) hists[x] = 0;
+  __syncthreads();
+  for (int64_t p = tid; p < len; p += kDwThreads) {
+    if (m && !m[p]) continue;
+    const uint32_t v = d[p], hi = v >> 21, mid = (v >> 10) & 0x7FFu;
+    if (hi == prefix[0]) atomicAdd(&hist[0][mid], 1u);
+    if (hi == prefix[1]) atomicAdd(&hist[1][mid], 1u);
+  }
+  __syncthreads();
+  for (int j = 0; j < 2; ++j) {
+    sel_find(hist[j], kSelBins / kDwThreads, k[j], part, &digit[j], &left[j]);
+    prefix[j] = (prefix[j] << 11) | digit[j];
+    k[j] = left[j];
+  }
+
+  // pass 3: bits 9 .. 0 of the values under each rank's first two digits
+  for (int x = tid; x < 2 * kSelBins; x += kDwThreads) hists[x] = 0;
+  __syncthreads();
+  for (int64_t p = tid; p < len; p += kDwThreads) {
+    if (m && !m[p]) continue;
+    const uint32_t v = d[p], hi = v >> 10, low = v & 0x3FFu;
+    if (hi == prefix[0]) atomicAdd(&hist[0][low], 1u);
+    if (hi == prefix[1]) atomicAdd(&hist[1][low], 1u);
+  }
+  __syncthreads();
+  for (int j = 0; j < 2; ++j) {
+    sel_find(hist[j], 1024 / kDwThreads, k[j], part, &digit[j], &left[j]);
+    prefix[j] = (prefix[j] << 10) | digit[j];
+  }
+  if (tid == 0) {
+    stat[2 * cell] = prefix[0];
+    stat[2 * cell + 1] = prefix[1];
+    sum[cell] = total;
+  }
+}
+
+size_t depthw_budget() {
+  const long v = gk_test_hook_value("depthw_budget", 0);
+  return v > 0 ? (size_t)v : kDepthwBudget;
+}
+
+}  // namespace
+
+extern "C" {
+
+/* The weighted depth of a slice of bootstrap replicates and its per-gene statistics; waits for the result.  See
+ * include/graphkir_hip.h. */
+int gk_depth_weighted(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compact, int32_t multiple, const int64_t* gene_off,
+                      int32_t n_gene, gk_dptr d_W, int64_t ldw, int32_t n_boot, const uint8_t* sel, const int64_t* rank,
+                      uint32_t* stat_out, uint64_t* sum_out, uint32_t* depth_out) {
+  gk_bind(ctx);
+  GK_REQUIRE(ctx && tab && gene_off && rank && stat_out && sum_out, "null pointer");
+  GK_REQUIRE(tab->d_pair_src, "weighted depth needs a tabulation made from packed records");
+  GK_REQUIRE((d_mates != 0) != (d_compact != 0), "weighted depth needs the sample's records in exactly one form");
+  GK_REQUIRE(n_gene >= 1 && n_gene <= 256, "weighted depth: the number of backbones must lie in 1 .. 256");
+  GK_REQUIRE(n_boot >= 1 && n_boot <= kMaxBoot, "the number of bootstrap replicates must lie in 1 .. 10000");
+  GK_REQUIRE(d_W && ldw >= tab->n_valid, "weighted depth: a row of the weights is shorter than the valid pairs");
+  GK_REQUIRE(gene_off[0] == 0, "weighted depth: the first backbone must start at 0");
+  for (int g = 0; g < n_gene; ++g) {
+    const int64_t len = gene_off[g + 1] - gene_off[g];
+    GK_REQUIRE(len >= 1 && len <= kDwMaxLen, "weighted depth: a backbone's length must lie in 1 .. 2^24");
+    int64_t n_sel = len;
+    if (sel) {
+      n_sel = 0;
+      for (int64_t p = gene_off[g]; p < gene_off[g + 1]; ++p) n_sel += sel[p] != 0;
+    }
+    for (int j = 0; j < 2; ++j)
+      GK_REQUIRE(n_sel == 0 || (rank[2 * g + j] >= 0 && rank[2 * g + j] < n_sel),
+                 "weighted depth: a rank lies outside the gene's selected positions");
+  }
+  const int64_t total = gene_off[n_gene], slots = total + 1;
+  const size_t n_cells = (size_t)n_boot * n_gene;
+  if (tab->n_valid == 0) {      // nothing to mark: zeros, nothing launched
+    std::fill(stat_out, stat_out + 2 * n_cells, 0u);
+    std::fill(sum_out, sum_out + n_cells, (uint64_t)0);
+    if (depth_out) std::fill(depth_out, depth_out + (size_t)n_boot * total, 0u);
+    return GK_OK;
+  }
+  // replicates of one slice: their difference arrays and the scan copy stay within the budget
+  const int64_t slice = std::max<int64_t>(1, std::min<int64_t>(n_boot, (int64_t)(depthw_budget() / (2 * sizeof(uint32_t) * (size_t)slots))));
+  hipStream_t st = ctx->stream;
+  std::vector<void*> blocks;
+  auto take = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (gk_pool_malloc(ctx, &p, bytes) != hipSuccess) return nullptr;
+    blocks.push_back(p);
+    return p;
+  };
+  uint32_t* diff = (uint32_t*)take((size_t)slice * slots * sizeof(uint32_t));
+  uint32_t* scan = (uint32_t*)take((size_t)slice * slots * sizeof(uint32_t));
+  int64_t* d_off = (int64_t*)take((size_t)(n_gene + 1) * sizeof(int64_t));
+  int64_t* d_rank = (int64_t*)take((size_t)2 * n_gene * sizeof(int64_t));
+  uint32_t* d_stat = (uint32_t*)take(2 * n_cells * sizeof(uint32_t));
+  unsigned long long* d_sum = (unsigned long long*)take(n_cells * sizeof(unsigned long long));
+  uint8_t* d_sel = sel ? (uint8_t*)take((size_t)total) : nullptr;
+  int rc = GK_OK;
+  hipError_t e = hipSuccess;
+  if (!diff || !scan || !d_off || !d_rank || !d_stat || !d_sum || (sel && !d_sel)) {
+    gk_set_error("out of device memory for the replicates of a weighted depth");
+    rc = GK_ERR_HIP;
+  }
+  if (rc == GK_OK) {
+    e = gk_send(ctx, d_off, gene_off, (size_t)(n_gene + 1) * sizeof(int64_t));
+    if (e == hipSuccess) e = gk_send(ctx, d_rank, rank, (size_t)2 * n_gene * sizeof(int64_t));
+    if (e == hipSuccess && sel) e = gk_send(ctx, d_sel, sel, (size_t)total);      // once, for every slice
+  }
+  DwSample s;
+  const uint32_t* c_off = gk_ptr<const uint32_t>(d_compact);
+  s.mates = gk_ptr<const gk_mate>(d_mates);
+  s.c_off = c_off;
+  s.c_words = c_off ? c_off + 2 * tab->n_pairs + 1 : nullptr;
+  s.wide = tab->d_wide;
+  s.pair_src = tab->d_pair_src;
+  s.pair_nh = tab->d_pair_nh;
+  s.n_valid = tab->n_valid;
+  s.n_pairs = tab->n_pairs;
+  s.n_spill = tab->n_spill;
+  const uint32_t* W = gk_ptr<const uint32_t>(d_W);
+  const unsigned mate_groups = (unsigned)((2 * tab->n_valid + kDwThreads - 1) / kDwThreads);
+  for (int64_t b0 = 0; b0 < n_boot && rc == GK_OK && e == hipSuccess; b0 += slice) {
+    const int nb = (int)std::min<int64_t>(slice, n_boot - b0);
+    const int64_t n = (int64_t)nb * slots;
+    e = hipMemsetAsync(diff, 0, (size_t)n * sizeof(uint32_t), st);
+    if (e != hipSuccess) break;
+    const dim3 grid(mate_groups, (unsigned)((nb + kBootPerThread - 1) / kBootPerThread));
+    if (c_off)
+      GK_PROF(ctx, "depthw_mark", GK_KERNEL(depthw_mark<true>, grid, dim3(kDwThreads), 0, st, s, (int)multiple, d_off, (int)n_gene,
+                                            W + b0 * ldw, ldw, nb, slots, diff));
+    else
+      GK_PROF(ctx, "depthw_mark", GK_KERNEL(depthw_mark<false>, grid, dim3(kDwThreads), 0, st, s, (int)multiple, d_off, (int)n_gene,
+                                            W + b0 * ldw, ldw, nb, slots, diff));
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(scan, diff, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) break;
+    rc = gk_scan_u32(ctx, scan, n, nullptr);
+    if (rc != GK_OK) break;
+    GK_PROF(ctx, "depthw_finish", GK_KERNEL(depthw_finish, dim3((unsigned)((n + kDwThreads - 1) / kDwThreads)), dim3(kDwThreads), 0,
+                                            st, scan, diff, n));
+    GK_PROF(ctx, "depthw_select", GK_KERNEL(depthw_select, dim3((unsigned)n_gene, (unsigned)nb), dim3(kDwThreads), 0, st, diff, slots,
+                                            d_off, d_sel, d_rank, d_stat + 2 * b0 * n_gene, d_sum + b0 * n_gene));
+    e = hipGetLastError();
+    if (e == hipSuccess && depth_out)      // the tracks without their extra slots (the tests ask for them)
+      e = hipMemcpy2DAsync(depth_out + b0 * total, (size_t)total * sizeof(uint32_t), diff, (size_t)slots * sizeof(uint32_t),
+                           (size_t)total * sizeof(uint32_t), (size_t)nb, hipMemcpyDeviceToHost, st);
+  }
+  if (rc == GK_OK && e == hipSuccess) e = gk_fetch_queue(ctx, stat_out, d_stat, 2 * n_cells * sizeof(uint32_t));
+  if (rc == GK_OK && e == hipSuccess) e = gk_fetch_queue(ctx, sum_out, d_sum, n_cells * sizeof(uint64_t));
+  if (rc == GK_OK && e == hipSuccess) e = gk_fetch_wait(ctx);
+  if (e != hipSuccess || rc != GK_OK) {
+    gk_fetch_cancel(ctx);      // drains the stream: sel / rank / gene_off may be the caller's again
+    if (e != hipSuccess) {
+      gk_set_error("weighted depth: %s", hipGetErrorString(e));
+      rc = GK_ERR_HIP;
+    }
+  }
+  for (void* p : blocks) gk_pool_free(ctx, p);
+  return rc;
+}
+
+}  // extern "C"

@@ -6,7 +6,9 @@
 //                  two_walks (tabulation: second walk instead of the saved words), novel_log2cap=N (size of the first
 //                  novel-variant table), bam_segments=N (segments of the BAM record index), setsum=tiles|leaves,
 //                  no_libdeflate (zlib for BGZF), wide_compat (column lists of at most 8 alleles through compat_kernel
-//                  instead of compat_rows8); read by the Python side only: bam_reader=samtools, ingest_ahead=N
+//                  instead of compat_rows8), depthw_budget=BYTES (gk_depth_weighted: the bytes a slice of replicates may take,
+//                  so that a few replicates already make several slices); read by the Python side only:
+//                  bam_reader=samtools, ingest_ahead=N
 #pragma once
 #include <cstdlib>
 #include <cstring>

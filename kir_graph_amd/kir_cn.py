@@ -108,12 +108,15 @@ def filterDepth(depth_file: str, filtered_depth_file: str,
 def predictSamplesCN(samples_depth_tsv: list[str], samples_cn: list[str], diploid_depth: str = "",
                      save_cn_model_path: str | None = None, assume_3DL3_diploid: bool = False,
                      select_mode: str = "p75", per_gene: bool = False, cluster_method: str = "CNgroup",
-                     cluster_method_kwargs: dict[str, Any] = {}, comm=None) -> None:
+                     cluster_method_kwargs: dict[str, Any] = {}, comm=None, return_model: bool = False) -> Dist | None:
     """Depth TSVs -> per-sample CN TSVs (``gene, cn, depth``), one pooled fit (kir_cn.py:146-231).
 
     ``comm``: optional collective (``cohort.Comm``) when the listed samples are this rank's shard
-    of a cohort; the depths of all ranks are all-gathered before the fit."""
+    of a cohort; the depths of all ranks are all-gathered before the fit.
+    ``return_model``: hand back the fitted model (``--cn-bootstrap`` assigns replicate depths with it); None otherwise, and
+    with ``per_gene``, which has no single model."""
     assert len(samples_depth_tsv) == len(samples_cn)
+    model = None
     tables = []
     for depth_file in samples_depth_tsv:
         logger.info(f"[CN] Select {select_mode} of depths per gene ({depth_file})")
@@ -138,6 +141,7 @@ def predictSamplesCN(samples_depth_tsv: list[str], samples_cn: list[str], diploi
         df1 = pd.DataFrame(list(cn.items()), columns=["gene", "cn"])
         df2 = pd.DataFrame(list(depths.items()), columns=["gene", "depth"])
         df1.merge(df2, on="gene").to_csv(filename, index=False, sep="\t")
+    return model if return_model else None
 
 
 def _predictPerGene(tables: list[pd.DataFrame], samples_depth_tsv: list[str], cluster_method: str,

@@ -66,7 +66,7 @@ def hisatMap(index: str, f1: str, f2: str, output_file: str, threads: int = 1) -
 
 
 def mapSamples(names, reads, index, index_ref, exon_region_only=False, alignments=None, write_json=True,
-               keep_records=False, keep_text=False):
+               keep_records=False, keep_text=False, cn_bootstrap=None):
     """Graph mapping (external) -> tabulation (GPU) -> depth (GPU), one sample at a time (main.py:124-168).
 
     Yields ``(alignment file, "{name}.variant", SampleData, depth file)`` per sample, in order.  When a sample
@@ -74,7 +74,10 @@ def mapSamples(names, reads, index, index_ref, exon_region_only=False, alignment
     text of the pairs and the packed records in HBM -- has been released: the consumer holds the CSR of the
     tabulation only (and closes it after typing), whatever the size of the cohort.  ``keep_records``: the packed
     records stay in HBM with the sample (``--cn-cohort`` parks a sample as its compact records, ``ParkedRecords``).
-    ``keep_text``: the SAM lines of the pairs stay with the sample (``--novel-discovery`` writes them grouped)."""
+    ``keep_text``: the SAM lines of the pairs stay with the sample (``--novel-discovery`` writes them grouped).
+    ``cn_bootstrap`` (``--cn-bootstrap``): ``{"n_boot", "seed", "select_mode"}`` and optionally ``"samples"``, one flag per
+    sample -- right after a flagged sample's depth, while its records are still in HBM, the read bootstrap of its gene
+    depths is written next to the depth file (``{depth_name}.boot.tsv``, ``cn_bootstrap.bootstrapGeneDepths``)."""
     gk = GkIndex.load(index_ref)
     gene_len = readLocusLengths(index_ref)
     dev = defaultDevice()
@@ -111,7 +114,7 @@ def mapSamples(names, reads, index, index_ref, exon_region_only=False, alignment
     writes = []
     try:
         yield from _mapLoop(names, prepare, ahead, gk, gene_len, (copier, ingest), dindex, index_ref, exon_region_only,
-                            write_json, writer, writes, keep_records, keep_text)
+                            write_json, writer, writes, keep_records, keep_text, cn_bootstrap)
     finally:
         for w in writes:
             w.result()          # every hand-off file is complete (and any write error surfaces) before we return
@@ -119,10 +122,12 @@ def mapSamples(names, reads, index, index_ref, exon_region_only=False, alignment
 
 
 def _mapLoop(names, prepare, ahead, gk, gene_len, staging, dindex, index_ref, exon_region_only, write_json, writer, writes,
-             keep_records=False, keep_text=False):
+             keep_records=False, keep_text=False, cn_bootstrap=None):
     copier, dev = staging
-    for name, source, pack in cohort.prefetched(range(len(names)), prepare, depth=ahead, workers=ahead):
+    warned = False
+    for k, (name, source, pack) in enumerate(cohort.prefetched(range(len(names)), prepare, depth=ahead, workers=ahead)):
         name += ".variant"
+        packed_records = pack is not None
         logger.info(f"[Graph] Filter mapping ({name})")
         handed_off = False
         if pack is not None:
@@ -159,6 +164,18 @@ def _mapLoop(names, prepare, ahead, gk, gene_len, staging, dindex, index_ref, ex
             logger.info(f"[Graph] Filter exon read to {depth_name}.exon.tsv")
             filterDepth(depth_name + ".tsv", depth_name + ".exon.tsv", readExons(index_ref))
             depth_name += ".exon"
+        if cn_bootstrap and (cn_bootstrap.get("samples") is None or cn_bootstrap["samples"][k]):
+            from .cn_bootstrap import bootstrapGeneDepths, hasRecords, writeDepthBootstrap
+            if packed_records and hasRecords(data):
+                logger.info(f"[CN] Read bootstrap of the gene depths to {depth_name}.boot.tsv")
+                boot = bootstrapGeneDepths(data, gene_len, cn_bootstrap["n_boot"], seed=cn_bootstrap["seed"],
+                                           select_mode=cn_bootstrap["select_mode"],
+                                           regions=readExons(index_ref) if exon_region_only else None)
+                writeDepthBootstrap(boot, depth_name + ".boot.tsv")
+            elif not warned:
+                logger.warning("[CN] cn bootstrap: a sample arrived without packed records (alignments read as text pairs); "
+                               "no .boot.tsv for it")
+                warned = True
         releaseInputs(data, keep_records, keep_text)
         yield source, name, data, depth_name + ".tsv"
 
@@ -386,6 +403,17 @@ class _Parser(argparse.ArgumentParser):
         return ns, rest
 
 
+def _cnBootstrapCount(text: str) -> int:
+    """``--cn-bootstrap N``: a count outside 1 .. 10000 is a parser error."""
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not 1 <= n <= 10000:
+        raise argparse.ArgumentTypeError(f"the number of replicates must lie in 1 .. 10000, got {n}")
+    return n
+
+
 def createParser() -> argparse.ArgumentParser:
     p = _Parser(description="Run Graph-KIR (MI355X typing path)",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -452,6 +480,11 @@ def createParser() -> argparse.ArgumentParser:
     p.add_argument("--call-coverage-depth", action="store_true",
                    help="Also write {result}.coverage.depth.tsv: every coverage track as runs of equal depth (implies "
                         "--call-coverage)")
+    p.add_argument("--cn-bootstrap", type=_cnBootstrapCount, default=None, metavar="N",
+                   help="Read bootstrap of the copy-number stage, N replicates (1 .. 10000): every replicate draws the sample's "
+                        "pairs again, recomputes every gene's depth statistic and is assigned a copy number by the fitted "
+                        "model; writes {depth}.boot.tsv, {cn}.confidence.tsv per sample and {cohort}.cn.confidence.tsv")
+    p.add_argument("--cn-bootstrap-seed", type=int, default=2022, help="Seed of the copy-number bootstrap's draws")
     p.add_argument("--ranks", type=int, default=1,
                    help="Start this many rank processes (samples are sharded over them; ranks map to GPUs round robin, "
                         "so 3 x the GPU count keeps every GPU busy).  Not needed under torchrun / any launcher that "
@@ -499,6 +532,16 @@ def _callCoverageArgs(args: argparse.Namespace, index_ref: str | None = None) ->
     return out
 
 
+def _cnBootstrapArgs(args: argparse.Namespace) -> dict | None:
+    """The ``mapSamples`` keyword of ``--cn-bootstrap`` (None when the flag is not given)."""
+    n = getattr(args, "cn_bootstrap", None)
+    if n is None:
+        return None
+    if not 1 <= int(n) <= 10000:
+        raise ValueError("--cn-bootstrap needs a count in 1 .. 10000")
+    return {"n_boot": int(n), "seed": int(getattr(args, "cn_bootstrap_seed", 2022)), "select_mode": args.cn_select}
+
+
 def main(args: argparse.Namespace) -> None:
     if getattr(args, "cn_cohort", False):
         os.environ.setdefault("GK_SAMPLE_LANES", "3")      # samples wait in HBM for the pooled fit: the lanes' working sets stay small
@@ -517,6 +560,7 @@ def main(args: argparse.Namespace) -> None:
     _callBootstrapArgs(args)
     _callFitArgs(args)
     _callCoverageArgs(args)
+    _cnBootstrapArgs(args)
 
     if not args.input_csv:
         if not args.r1 and not args.alignment:
@@ -592,18 +636,39 @@ def _runCohort(args, names, reads, cn_files, index, index_ref, cohort_name, comm
                         bootstrap_seed=int(getattr(args, "em_bootstrap_seed", 2022)), **_callBootstrapArgs(args),
                         **_callFitArgs(args), **_callCoverageArgs(args, index_ref))
     try:
+        confidence: list | None = [] if _cnBootstrapArgs(args) else None
         allele_files, my_cn = _typeShare(args, lanes, pick(names), pick(reads), my_cn, pick, index, index_ref, cohort_name,
-                                         comm, kwargs, pooled_fit, keep_records=bool(_callCoverageArgs(args)))
+                                         comm, kwargs, pooled_fit, keep_records=bool(_callCoverageArgs(args)),
+                                         confidence=confidence)
     finally:
         lanes.close()
-    _mergeShare(my_cn, allele_files, cohort_name, comm)
+    _mergeShare(my_cn, allele_files, cohort_name, comm, confidence)
 
 
 def _typeShare(args, lanes, names, reads, my_cn, pick, index, index_ref, cohort_name, comm, kwargs, pooled_fit,
-               keep_records=False):
+               keep_records=False, confidence=None):
     """Tabulation, depth, copy numbers of this rank's samples, each handed to the typing lanes as soon as its copy
     numbers are known; returns (allele files, CN files) in the rank's sample order.  ``keep_records`` (``--call-coverage``):
-    a sample's records stay in HBM until the lane that typed it frees them."""
+    a sample's records stay in HBM until the lane that typed it frees them.  ``confidence`` (``--cn-bootstrap``): a list that
+    gets, per sample in the rank's order, its ``{cn_name}.confidence.tsv`` -- written as soon as the model that assigned its
+    copy numbers is fitted -- or None for a sample without one (its copy numbers were provided, or it has no ``.boot.tsv``)."""
+    cn_boot = _cnBootstrapArgs(args) if confidence is not None else None
+    if cn_boot is not None:
+        cn_boot["samples"] = [pooled_fit or not c for c in my_cn]
+        for c in my_cn:
+            if c and not pooled_fit:
+                logger.info(f"[CN] cn bootstrap: the copy numbers of {c} are provided; nothing to bootstrap")
+
+    def confide(depth_file: str, cn_file: str, model) -> None:
+        if confidence is None:
+            return
+        boot_file = depth_file[:-len(".tsv")] + ".boot.tsv"
+        if model is None or not Path(boot_file).exists():
+            confidence.append(None)
+            return
+        from .cn_bootstrap import writeCnConfidence
+        confidence.append(writeCnConfidence(boot_file, model, cn_file, cn_file[:-len(".tsv")] + ".confidence.tsv"))
+
     allele_files: list[str] = []
     waiting: list[tuple[str, object]] = []      # samples that wait for the pooled copy-number fit
     depth_files: list[str] = []
@@ -613,7 +678,8 @@ def _typeShare(args, lanes, names, reads, my_cn, pick, index, index_ref, cohort_
                          alignments=pick(args.alignment) if args.alignment else None,
                          write_json=not args.no_variant_json,
                          keep_records=(pooled_fit or keep_records) and not args.step_skip_typing,
-                         keep_text=getattr(args, "novel_discovery", False) and not args.step_skip_typing)
+                         keep_text=getattr(args, "novel_discovery", False) and not args.step_skip_typing,
+                         cn_bootstrap=cn_boot)
     for i, (_, name, data, depth_file) in enumerate(samples):
         depth_files.append(depth_file)
         if pooled_fit:
@@ -646,10 +712,14 @@ def _typeShare(args, lanes, names, reads, my_cn, pick, index, index_ref, cohort_
         if not my_cn[i]:
             cn_name = str(Path(depth_file).with_suffix(f".{args.cn_select}.{args.cn_algorithm}"))
             logger.info(f"[CN] Copy number estimation per sample ({cn_name})")
-            predictSamplesCN([depth_file], [cn_name + ".tsv"], "", cluster_method=args.cn_algorithm,
-                             cluster_method_kwargs=kwargs, assume_3DL3_diploid=not args.cn_3dl3_not_diploid,
-                             save_cn_model_path=cn_name + ".json", select_mode=args.cn_select)
+            model = predictSamplesCN([depth_file], [cn_name + ".tsv"], "", cluster_method=args.cn_algorithm,
+                                     cluster_method_kwargs=kwargs, assume_3DL3_diploid=not args.cn_3dl3_not_diploid,
+                                     save_cn_model_path=cn_name + ".json", select_mode=args.cn_select,
+                                     return_model=confidence is not None)
             my_cn[i] = cn_name + ".tsv"
+            confide(depth_file, my_cn[i], model)
+        else:
+            confide(depth_file, my_cn[i], None)
         # copy numbers known: hand the sample to the typing lanes and go on with the next one's tabulation; a lane
         # releases the sample when it is typed (at most GK_SAMPLE_LANES tabulations wait in HBM)
         if not args.step_skip_typing:
@@ -662,8 +732,11 @@ def _typeShare(args, lanes, names, reads, my_cn, pick, index, index_ref, cohort_
         suffix = f".{args.cn_select}.cohort.{args.cn_algorithm}"
         my_cn = [str(Path(p).with_suffix(suffix + ".tsv")) for p in depth_files]
         logger.info(f"[CN] Copy number estimation by cohort ({cohort_name + suffix})")
-        predictSamplesCN(depth_files, my_cn, cluster_method=args.cn_algorithm, cluster_method_kwargs=kwargs,
-                         save_cn_model_path=cohort_name + suffix + ".json", select_mode=args.cn_select, comm=comm)
+        model = predictSamplesCN(depth_files, my_cn, cluster_method=args.cn_algorithm, cluster_method_kwargs=kwargs,
+                                 save_cn_model_path=cohort_name + suffix + ".json", select_mode=args.cn_select, comm=comm,
+                                 return_model=confidence is not None)
+        for depth_file, cn_file in zip(depth_files, my_cn):      # every rank ran the identical fit: its own samples' tables
+            confide(depth_file, cn_file, model)
         for (name, source), cn_file in zip(waiting, my_cn):
             if args.step_skip_typing:
                 continue
@@ -676,19 +749,26 @@ def _typeShare(args, lanes, names, reads, my_cn, pick, index, index_ref, cohort_
     return allele_files, my_cn
 
 
-def _mergeShare(my_cn, allele_files, cohort_name, comm) -> None:
+def _mergeShare(my_cn, allele_files, cohort_name, comm, confidence=None) -> None:
     # merge on rank 0, in cohort order
+    if confidence is not None:      # --cn-bootstrap: (CN file, confidence table) of every sample that has one
+        confidence = [(cn, c) for cn, c in zip(my_cn, confidence)]
     if comm is not None:
         cn_sorted = comm.gatherInCohortOrder(my_cn)
         al_sorted = comm.gatherInCohortOrder(allele_files)
+        conf_sorted = comm.gatherInCohortOrder(confidence) if confidence is not None else None
         if comm.rank == 0:
-            my_cn, allele_files = cn_sorted, [a for a in al_sorted if a]
+            my_cn, allele_files, confidence = cn_sorted, [a for a in al_sorted if a], conf_sorted
     if comm is None or comm.rank == 0:
         logger.info(f"[CN] Saved copy number in {cohort_name}.cn.tsv")
         mergeCN(my_cn, cohort_name + ".cn.tsv")
         if allele_files:
             logger.info(f"[Allele] Saved in {cohort_name}.allele.tsv")
             mergeAllele(allele_files, cohort_name + ".allele.tsv")
+        if confidence is not None:
+            from .cn_bootstrap import mergeCnConfidence
+            logger.info(f"[CN] Saved the copy numbers' bootstrap confidence in {cohort_name}.cn.confidence.tsv")
+            mergeCnConfidence([(cn, c) for cn, c in confidence if c], cohort_name + ".cn.confidence.tsv")
     if comm is not None:
         comm.barrier()
         comm.close()
