@@ -37,6 +37,7 @@ constexpr int kLocalProbes = 8;
 constexpr uint32_t kTableProbes = 1u << 12;
 constexpr size_t kLocalBytes = (size_t)kLocalSlots * (8 + 4 + 4);
 constexpr size_t kMaskLdsMax = 100 * 1024;    // bit rows of a gene staged in LDS up to this size, read from HBM / L2 beyond
+constexpr size_t kLdsPerCu = 160 * 1024;      // what one workgroup can ask of a CU (gfx950)
 
 struct EmSetsJob {     // one gene of a launch (blockIdx.y)
   const int32_t* rows;
@@ -359,6 +360,21 @@ void by_group(int G, Launch&& go) {
   else go(std::integral_constant<int, 16>());
 }
 
+// What em_sets_groups keeps in LDS behind the workgroup's table when it stages a gene's bit rows: the rows at an even
+// number of words each, the row of zeros and the row of ones behind them, room for the lanes that read past a row's end.
+size_t staged_mask_bytes(int64_t n_span, int words) {
+  return ((size_t)(n_span + 2) * (size_t)((words + 1) & ~1) + 2 * kMaxWords) * sizeof(uint32_t);
+}
+
+// The bit rows of a gene go to LDS when they are small enough to be worth a copy per workgroup (kMaskLdsMax) AND what the
+// kernel then really requests -- the padded form above next to the local table -- is there on a CU: rows of 1 or 3 words
+// grow by a half or a third on the way in (16 367 .. 25 600 rows of one word, 8 183 .. 8 533 of three passed the first
+// test alone and asked for more LDS than a CU has).  A gene that does not fit is read from global memory.
+bool mask_fits_lds(int64_t n_span, int words) {
+  return (size_t)n_span * (size_t)words * sizeof(uint32_t) <= kMaskLdsMax &&
+         staged_mask_bytes(n_span, words) <= kLdsPerCu - kLocalBytes;
+}
+
 struct Geometry { int G = 4; uint32_t blocks = 1, slots = 0; size_t lds = kLocalBytes; };
 
 Geometry geometry_of(const std::vector<EmSetsJob>& jobs) {
@@ -368,8 +384,7 @@ Geometry geometry_of(const std::vector<EmSetsJob>& jobs) {
     words = std::max(words, j.words);
     g.blocks = std::max(g.blocks, j.n_blocks);
     g.slots = std::max(g.slots, j.slot_mask);
-    if (j.mask_in_lds)      // the gene's rows, the two rows behind them, room for the lanes that read past a row's end
-      g.lds = std::max(g.lds, kLocalBytes + ((size_t)(j.n_span + 2) * (size_t)((j.words + 1) & ~1) + 2 * kMaxWords) * sizeof(uint32_t));
+    if (j.mask_in_lds) g.lds = std::max(g.lds, kLocalBytes + staged_mask_bytes(j.n_span, j.words));
   }
   g.G = lanes_per_pair(words);
   return g;
@@ -499,12 +514,11 @@ int gk_em_sets(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, int32_t
   GK_REQUIRE(words >= 1 && words <= kMaxWords, "more than 512 alleles per gene are not supported by the EM kernel");
   GK_REQUIRE(n_rows >= 0 && n_rows < (1ll << 31) && vend >= vbeg, "bad candidate-set geometry");
   if (!n_rows) return GK_OK;
-  const size_t mask_bytes = (size_t)(vend - vbeg) * words * sizeof(uint32_t);
   std::vector<EmSetsJob> jobs(1);
   EmSetsJob& j = jobs[0];
   memset(&j, 0, sizeof(j));
   j.rows = gk_ptr<int32_t>(d_rows); j.n_rows = n_rows; j.mask = gk_ptr<uint32_t>(d_mask);
-  j.vbeg = vbeg; j.n_span = vend - vbeg; j.words = words; j.mask_in_lds = mask_bytes <= kMaskLdsMax ? 1 : 0;
+  j.vbeg = vbeg; j.n_span = vend - vbeg; j.words = words; j.mask_in_lds = mask_fits_lds(vend - vbeg, words) ? 1 : 0;
   j.sets = gk_ptr<uint32_t>(d_sets_out);
   j.n_blocks = blocks_for(n_rows, lanes_per_pair(words));
   EmSetsJob* d_jobs = nullptr;
@@ -666,9 +680,8 @@ int gk_sample_em(gk_ctx* ctx, gk_tab* tab, gk_em_job* jobs, int32_t n_jobs, int3
       Work& w = work[i];
       EmSetsJob& s = sj[q];
       memset(&s, 0, sizeof(s));
-      const size_t mask_bytes = (size_t)(j.vend - j.vbeg) * j.words * sizeof(uint32_t);
       s.rows = gk_ptr<int32_t>(j.d_rows); s.n_rows = j.n_rows; s.mask = gk_ptr<uint32_t>(j.d_mask);
-      s.vbeg = j.vbeg; s.n_span = j.vend - j.vbeg; s.words = j.words; s.mask_in_lds = mask_bytes <= kMaskLdsMax ? 1 : 0;
+      s.vbeg = j.vbeg; s.n_span = j.vend - j.vbeg; s.words = j.words; s.mask_in_lds = mask_fits_lds(j.vend - j.vbeg, j.words) ? 1 : 0;
       s.sets = w.d_sets;
       s.tag = (unsigned long long*)(table + at_tag); s.cnt = (uint32_t*)(table + at_tag + (size_t)w.n_slots * 8);
       s.row = (uint32_t*)(table + at_row);
