@@ -204,7 +204,11 @@ __global__ __launch_bounds__(kThreads) void minsum_finish(const uint32_t* __rest
     for (int s = 0; s < n_slices; ++s) sad += partial[(int64_t)s * n_out + o];
     const int t = (int)(o / n_cols), a = (int)(o % n_cols);
     const uint32_t sp = pcol ? msum[pcol[t]] : psum[t];
-    v = (sp + msum[cols[a]] - sad) >> 1;
+    // sp + msum - sad = 2 M: with bytes up to 255 it passes 2^32 from 8.4 M reads on, while M itself (<= 255 n_rows)
+    // and each of the three sums fit 32 bits up to the 16 M reads the entry point admits -- so the difference is
+    // formed in 64 bits and halved before it is narrowed (tightening the row limit instead would have refused
+    // tables that were typed correctly so far)
+    v = (uint32_t)(((uint64_t)sp + msum[cols[a]] - sad) >> 1);
   }
   if (o < n_out) M[o] = v;
   // count / min / max of the candidates for the select passes below (one atomic triple per workgroup)

@@ -83,7 +83,8 @@ def test_second_allele_table_is_mirrored_exactly(device, n_allele):
 
 @pytest.mark.parametrize("n_rows,n_allele,n_sets,c_prev,top_n", [(5, 9, 3, 1, 4), (1000, 33, 40, 1, 25), (8200, 70, 100, 2, 60),
                                                                  (20011, 130, 129, 3, 600), (129, 17, 16, 1, 1000),
-                                                                 (70001, 200, 200, 1, 600)])
+                                                                 (70001, 200, 200, 1, 600),
+                                                                 (3, 400, 400, 1, 600)])     # a flood of ties: more than cap
 def test_bound_step_selects_what_numpy_selects(device, n_rows, n_allele, n_sets, c_prev, top_n):
     """gk_miss_colsum / gk_bound_step straight through the C ABI on a random u8 mismatch table:
     M = sum_r min(miss) for every candidate, the top_n-th smallest among the masked candidates, and the
@@ -121,6 +122,10 @@ def test_bound_step_selects_what_numpy_selects(device, n_rows, n_allele, n_sets,
         order = np.argsort(idx[:len(want)])
         assert np.array_equal(idx[:len(want)][order], want)
         assert np.array_equal(mm[:len(want)][order], flat[want])
+    else:       # more selected than there is room for: the first cap entries are different members with their own totals
+        got = idx[:cap]
+        assert len(np.unique(got)) == cap and np.isin(got, want).all()
+        assert np.array_equal(mm[:cap], flat[got])
     d_miss.free()
     d_msum.free()
 
