@@ -373,6 +373,11 @@ int gk_bound_step(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, gk_
                   int32_t top_n, int32_t cap, uint32_t* hdr_out, int32_t* idx_out, uint32_t* m_out);
 int gk_setsum(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t ld, const int32_t* ids, int32_t n_sets, int32_t c,
               double* value_out, double* frac_out);
+/* gk_setsum for a FEW sets (at most 4096) of c = 1 .. 4 alleles by workgroups that own a chunk of 8192 rows and read only
+ * the columns their set names (csrc/gk_setsum_few.hip; the search takes this form for at most 8 sets, and for the column
+ * sums of a table of at most 8 columns): the same bits.  c = 1: value_out = the column's sum, every share 1. */
+int gk_setsum_few(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t ld, const int32_t* ids, int32_t n_sets, int32_t c,
+                  double* value_out, double* frac_out);
 
 /* ---- the whole greedy search of one gene, host half included: AlleleTyping.addCandidate called n_steps times
  * (typing_mulit_allele.py:478-598 with 156-214, 456-476), in the calling thread, without the host language's
@@ -447,7 +452,7 @@ int gk_search_export(gk_search* const* s, int32_t n, int64_t* totals, int64_t* m
  * filled and every other entry is NaN */
 int gk_search_colsum(gk_search* s, double* out);
 /* launch geometries of the run, 7 int64 per device call: kind (0 gk_maxsum, 1 gk_bound_step, 2 gk_setsum /
- * gk_fraction) and the arguments of the roofline model (kir_graph_amd/roofmodel.py) */
+ * gk_fraction by tiles, 3 gk_setsum leaf by leaf, 4 gk_setsum_few) and the arguments of the roofline model (kir_graph_amd/roofmodel.py) */
 int gk_search_log(gk_search* s, int64_t* out, int64_t capacity, int64_t* n_out);
 int gk_search_destroy(gk_search* s);
 /* isHomozygous (typing_mulit_allele.py:835-857) on flat observations (position, label code, negative?, count):

@@ -187,7 +187,8 @@ struct gk_search {
   std::vector<double> colsum;
   std::vector<Step> steps;
   // launch geometries for the roofline accounting (kir_graph_amd/roofmodel.py): 7 numbers per device call --
-  // kind (0 maxsum / column sums, 1 minsum, 2 set sums by tiles, 3 set sums leaf by leaf), then the model's arguments
+  // kind (0 maxsum / column sums, 1 minsum, 2 set sums by tiles, 3 set sums leaf by leaf, 4 sums of a few sets or columns
+  // by chunk-owning workgroups), then the model's arguments
   std::vector<int64_t> log;
   int64_t distinct(const int32_t* ids, size_t n) const {
     std::vector<char> seen((size_t)n_allele, 0);
@@ -242,7 +243,36 @@ int gk_compat_index(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk
 
 }  // extern "C"
 
+// gk_setsum_few.hip: value + shares of a few sets, and the sums of a few columns, by workgroups that own a chunk.  Weak
+// like the two above: the host-only builds have no stand-in, and the calls then keep the forms of gk_search.hip
+__attribute__((weak)) int gk_shares_few_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32_t* ids, int32_t n_sets,
+                                                int32_t c, GkSumCall& call);
+__attribute__((weak)) int gk_colsum_few_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32_t* cols, int32_t n_cols,
+                                                GkSumCall& call);
+
 namespace {
+
+constexpr int kFewSets = 8;     // sets of a call, or columns of a table, the chunk-owning form takes
+
+// float64 tables only; GK_TEST_HOOKS=setsum=leaves|tiles keeps the forms of gk_search.hip (read on every call: the tests
+// compare both sides on one library, in one process)
+bool few_form(const GkTable& table) {
+  if (!gk_shares_few_enqueue || !gk_colsum_few_enqueue || table.indexed()) return false;
+  char form[16];
+  return !(gk_test_hook("setsum", form, sizeof(form)) && (!strcmp(form, "leaves") || !strcmp(form, "tiles")));
+}
+
+// value + shares of the given sets; *kind: what S->note records for the launch
+int shares_enqueue(gk_ctx* ctx, const GkTable& table, int64_t n_rows, const int32_t* ids, int32_t n_sets, int32_t c,
+                   GkSumCall& call, int* kind) {
+  if (n_sets <= kFewSets && c >= 2 && c <= 4 && few_form(table)) {
+    *kind = 4;
+    return gk_shares_few_enqueue(ctx, table, n_rows, ids, n_sets, c, call);
+  }
+  const int rc = gk_shares_enqueue(ctx, table, n_rows, ids, n_sets, c, true, call);
+  *kind = call.leafwise ? 3 : 2;
+  return rc;
+}
 
 // The search of ONE gene as a sequence of phases, each cut where the host needs something from the device:
 //   colsums   -> (wait) -> first step
@@ -314,6 +344,12 @@ struct GeneSearch {
   int colsum_enqueue() {
     std::vector<int32_t> every((size_t)n_allele);
     std::iota(every.begin(), every.end(), 0);
+    if (n_allele <= kFewSets && few_form(table)) {
+      int rc = gk_colsum_few_enqueue(ctx, table, n_rows, every.data(), n_allele, scall);
+      if (rc) return rc;
+      S->note(4, n_rows, n_allele, 1, n_allele, 0, 0);
+      return GK_OK;
+    }
     int rc = gk_colsum_enqueue(ctx, table, n_rows, every.data(), n_allele, scall);
     if (rc) return rc;
     S->note(0, n_rows, 1, 0, n_allele, 0, 0);
@@ -403,9 +439,10 @@ struct GeneSearch {
       std::copy(prev.ids.begin() + (size_t)t * k, prev.ids.begin() + (size_t)(t + 1) * k, sel.ids.begin() + (size_t)i * c);
       sel.ids[(size_t)i * c + k] = cols[a];
     }
-    int rc = gk_shares_enqueue(ctx, table, n_rows, sel.ids.data(), (int32_t)n_sel, c, true, scall);
+    int kind = 0;
+    int rc = shares_enqueue(ctx, table, n_rows, sel.ids.data(), (int32_t)n_sel, c, scall, &kind);
     if (rc) return rc;
-    S->note(scall.leafwise ? 3 : 2, n_rows, n_sel, c, S->distinct(sel.ids.data(), sel.ids.size()), 0, 0);
+    S->note(kind, n_rows, n_sel, c, S->distinct(sel.ids.data(), sel.ids.size()), 0, 0);
     sums_in_flight = true;
     return GK_OK;
   }
@@ -1069,10 +1106,11 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
             b->deps.push_back(d);
           }
           if (rc || b->deps.empty()) break;
-          rc = gk_shares_enqueue(ctx, GkTable{j.d_L, j.n_rows, nullptr}, j.n_rows, b->ids.data(), (int32_t)b->deps.size(), k, true,
-                                 b->call);
+          int kind = 0;
+          rc = shares_enqueue(ctx, GkTable{j.d_L, j.n_rows, nullptr}, j.n_rows, b->ids.data(), (int32_t)b->deps.size(), k, b->call,
+                              &kind);
           if (rc) break;
-          gs[b->deps[0]]->S->note(b->call.leafwise ? 3 : 2, j.n_rows, (int64_t)b->deps.size(), k, gs[b->deps[0]]->S->distinct(b->ids.data(), b->ids.size()), 0, 0);
+          gs[b->deps[0]]->S->note(kind, j.n_rows, (int64_t)b->deps.size(), k, gs[b->deps[0]]->S->distinct(b->ids.data(), b->ids.size()), 0, 0);
           batches.push_back(std::move(b));
           rc = push((int)batches.size() - 1, kOneSet);
         }

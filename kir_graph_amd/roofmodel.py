@@ -139,7 +139,7 @@ def _priced(kernel: str, calls: list[tuple]) -> tuple[float, float, str, float]:
             b, o = compatLaunch(*c[1:5])[0], 0.0
         elif kernel == "tab_count":
             b, o = tabLaunch(*c[1:5])
-        elif kernel in ("fraction_chunks", "setsum_leaves"):
+        elif kernel in ("fraction_chunks", "setsum_leaves", "setsum_few"):
             b, o = setsumLaunch(*c[1:5])
         else:
             return 0.0, 0.0, "hbm", 0.0

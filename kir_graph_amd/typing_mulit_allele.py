@@ -694,7 +694,7 @@ class AlleleTyping:
             elif kind == 1:
                 m.dev.call_log.append(("minsum_sad", a, b, c_, d, False))
             else:
-                m.dev.call_log.append(("setsum_leaves" if kind == 3 else "fraction_chunks", a, b, c_, d))
+                m.dev.call_log.append(({3: "setsum_leaves", 4: "setsum_few"}.get(kind, "fraction_chunks"), a, b, c_, d))
 
     def geneJob(self, cn: int, verdict: bool | None = None):
         """(``_lib.GeneJob`` for ``gk_sample_search``, homozygous?) of a model built with ``_defer_launch``: the
