@@ -367,13 +367,11 @@ int gk_bound_step(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, gk_
   gk_bind(ctx);
   GK_REQUIRE(hdr_out && idx_out && m_out, "null pointer");
   GkBoundCall call;
-  int rc = gk_bound_enqueue(ctx, d_miss8, ldm, n_rows, d_msum, ids, n_sets, c_prev, cols, n_cols, first, top_n, cap, call);
-  if (rc == GK_OK && gk_fetch_wait(ctx) != hipSuccess) {
-    gk_set_error("bound step: waiting for the stream failed");
-    rc = GK_ERR_HIP;
-  }
+  const int rc = gk_call_wait(ctx, call,
+                              gk_bound_enqueue(ctx, d_miss8, ldm, n_rows, d_msum, ids, n_sets, c_prev, cols, n_cols, first,
+                                               top_n, cap, call),
+                              "bound step");
   if (rc == GK_OK) gk_bound_collect(ctx, call, hdr_out, idx_out, m_out);
-  else gk_release(ctx, call.temps);
   return rc;
 }
 
@@ -389,23 +387,18 @@ int gk_bound_enqueue(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, 
   GK_REQUIRE(n_rows < (int64_t)16000000, "too many reads for 32-bit mismatch totals");
   hipStream_t st = ctx->stream;
   const int64_t n_out = (int64_t)n_sets * n_cols;
-  auto take = [&](void** p, size_t bytes) -> hipError_t {
-    hipError_t e = gk_pool_malloc(ctx, p, bytes);
-    if (e == hipSuccess) call.temps.push_back(*p);
-    return e;
-  };
+  call.begin(ctx);
   // parameters through the context's pinned ring: [ids | cols | first mask]
   const size_t n_ids = (size_t)n_sets * c_prev;
   const size_t par_bytes = (n_ids + (size_t)n_cols) * sizeof(int32_t) + (size_t)n_out;
   char* d_par = nullptr;
-  GK_HIP(take((void**)&d_par, par_bytes));
+  GK_HIP(call.take((void**)&d_par, par_bytes));
   {
     std::vector<char> packed(par_bytes);   // one copy instead of three (every runtime call is contended by the host threads)
     memcpy(packed.data(), ids, n_ids * sizeof(int32_t));
     memcpy(packed.data() + n_ids * sizeof(int32_t), cols, (size_t)n_cols * sizeof(int32_t));
     memcpy(packed.data() + (n_ids + n_cols) * sizeof(int32_t), first, (size_t)n_out);
-    GK_HIP(gk_send(ctx, d_par, packed.data(), par_bytes));
-    if (par_bytes > gk_stage_direct()) GK_HIP(hipStreamSynchronize(st));   // sent straight from `packed`
+    GK_HIP(call.send(d_par, packed.data(), par_bytes));
   }
   const int32_t* d_ids = (const int32_t*)d_par;
   const int32_t* d_cols = d_ids + n_ids;
@@ -415,8 +408,8 @@ int gk_bound_enqueue(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, 
   uint8_t* d_P = nullptr;
   uint32_t* d_psum = nullptr;
   if (c_prev >= 2) {   // previous sets of two or more alleles become one column each
-    GK_HIP(take((void**)&d_P, (size_t)n_sets * (size_t)ldm));
-    GK_HIP(take((void**)&d_psum, (size_t)n_sets * sizeof(uint32_t)));
+    GK_HIP(call.take((void**)&d_P, (size_t)n_sets * (size_t)ldm));
+    GK_HIP(call.take((void**)&d_psum, (size_t)n_sets * sizeof(uint32_t)));
     GK_PROF(ctx, "setmin_u8", GK_KERNEL(setmin_u8, dim3((unsigned)n_sets), dim3(kThreads), 0, st, miss, ldm, d_ids,
                                         c_prev, d_P, d_psum));
   }
@@ -429,12 +422,13 @@ int gk_bound_enqueue(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, 
   const int blocks_per_slice = (int)((n_blk + want - 1) / want);
   const int n_slices = (int)((n_blk + blocks_per_slice - 1) / blocks_per_slice);
   uint32_t *d_partial = nullptr, *d_M = nullptr;
-  // selection state, indices and totals in ONE block, so that one copy brings the result back
+  // selection state, indices and totals in ONE block, so that one copy brings the result back (the kernels update the
+  // state with atomics: it stays in device memory, no slot of the result ring)
   char* d_sel = nullptr;
   const size_t sel_bytes = sizeof(SelState) + (size_t)cap * (sizeof(int32_t) + sizeof(uint32_t));
-  GK_HIP(take((void**)&d_partial, (size_t)n_out * n_slices * sizeof(uint32_t)));
-  GK_HIP(take((void**)&d_M, (size_t)n_out * sizeof(uint32_t)));
-  GK_HIP(take((void**)&d_sel, sel_bytes));
+  GK_HIP(call.take((void**)&d_partial, (size_t)n_out * n_slices * sizeof(uint32_t)));
+  GK_HIP(call.take((void**)&d_M, (size_t)n_out * sizeof(uint32_t)));
+  GK_HIP(call.result(sel_bytes, (void**)&d_sel, false));
   SelState* d_state = (SelState*)d_sel;
   int32_t* d_idx = (int32_t*)(d_sel + sizeof(SelState));
   uint32_t* d_mout = (uint32_t*)(d_idx + cap);
@@ -457,12 +451,11 @@ int gk_bound_enqueue(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, 
   // one copy: the header first, then the entries (the three parts are adjacent)
   call.cap = cap;
   call.state_bytes = sizeof(SelState);
-  call.back.resize(sel_bytes);
-  GK_HIP(gk_fetch_queue(ctx, call.back.data(), d_sel, sel_bytes));
+  GK_HIP(call.finish());
   return GK_OK;
 }
 
-void gk_bound_collect(gk_ctx* ctx, GkBoundCall& call, uint32_t* hdr_out, int32_t* idx_out, uint32_t* m_out) {
+void gk_bound_collect(gk_ctx*, GkBoundCall& call, uint32_t* hdr_out, int32_t* idx_out, uint32_t* m_out) {
   const uint32_t* head = (const uint32_t*)call.back.data();
   hdr_out[0] = head[0];   // candidates
   hdr_out[1] = head[4];   // the cut: the top_n-th smallest M (rounded up to 2^sh0 - 1 when the band is wider than 2^22)
@@ -473,5 +466,5 @@ void gk_bound_collect(gk_ctx* ctx, GkBoundCall& call, uint32_t* hdr_out, int32_t
     memcpy(idx_out, call.back.data() + call.state_bytes, (size_t)n_sel * sizeof(int32_t));
     memcpy(m_out, call.back.data() + call.state_bytes + (size_t)call.cap * sizeof(int32_t), (size_t)n_sel * sizeof(uint32_t));
   }
-  gk_release(ctx, call.temps);
+  call.done();
 }

@@ -5,7 +5,7 @@
 //   GK_TEST_HOOKS  switches the TESTS use to force rarely taken paths, comma-separated `name` or `name=value`:
 //                  two_walks (tabulation: second walk instead of the saved words), novel_log2cap=N (size of the first
 //                  novel-variant table), bam_segments=N (segments of the BAM record index), setsum=tiles|leaves (either one also
-//                  keeps the search's sums of at most 8 sets / 8 columns off setsum_few: gk_hostsearch.cpp),
+//                  keeps sums of at most 8 sets / 8 columns off setsum_few: gk_shares_enqueue, gk_colsum_enqueue),
 //                  no_libdeflate (zlib for BGZF), wide_compat (column lists of at most 8 alleles through compat_kernel
 //                  instead of compat_rows8), depthw_budget=BYTES (gk_depth_weighted: the bytes a slice of replicates may take,
 //                  so that a few replicates already make several slices); read by the Python side only:

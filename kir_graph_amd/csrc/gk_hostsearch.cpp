@@ -243,36 +243,7 @@ int gk_compat_index(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk
 
 }  // extern "C"
 
-// gk_setsum_few.hip: value + shares of a few sets, and the sums of a few columns, by workgroups that own a chunk.  Weak
-// like the two above: the host-only builds have no stand-in, and the calls then keep the forms of gk_search.hip
-__attribute__((weak)) int gk_shares_few_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32_t* ids, int32_t n_sets,
-                                                int32_t c, GkSumCall& call);
-__attribute__((weak)) int gk_colsum_few_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32_t* cols, int32_t n_cols,
-                                                GkSumCall& call);
-
 namespace {
-
-constexpr int kFewSets = 8;     // sets of a call, or columns of a table, the chunk-owning form takes
-
-// float64 tables only; GK_TEST_HOOKS=setsum=leaves|tiles keeps the forms of gk_search.hip (read on every call: the tests
-// compare both sides on one library, in one process)
-bool few_form(const GkTable& table) {
-  if (!gk_shares_few_enqueue || !gk_colsum_few_enqueue || table.indexed()) return false;
-  char form[16];
-  return !(gk_test_hook("setsum", form, sizeof(form)) && (!strcmp(form, "leaves") || !strcmp(form, "tiles")));
-}
-
-// value + shares of the given sets; *kind: what S->note records for the launch
-int shares_enqueue(gk_ctx* ctx, const GkTable& table, int64_t n_rows, const int32_t* ids, int32_t n_sets, int32_t c,
-                   GkSumCall& call, int* kind) {
-  if (n_sets <= kFewSets && c >= 2 && c <= 4 && few_form(table)) {
-    *kind = 4;
-    return gk_shares_few_enqueue(ctx, table, n_rows, ids, n_sets, c, call);
-  }
-  const int rc = gk_shares_enqueue(ctx, table, n_rows, ids, n_sets, c, true, call);
-  *kind = call.leafwise ? 3 : 2;
-  return rc;
-}
 
 // The search of ONE gene as a sequence of phases, each cut where the host needs something from the device:
 //   colsums   -> (wait) -> first step
@@ -344,15 +315,10 @@ struct GeneSearch {
   int colsum_enqueue() {
     std::vector<int32_t> every((size_t)n_allele);
     std::iota(every.begin(), every.end(), 0);
-    if (n_allele <= kFewSets && few_form(table)) {
-      int rc = gk_colsum_few_enqueue(ctx, table, n_rows, every.data(), n_allele, scall);
-      if (rc) return rc;
-      S->note(4, n_rows, n_allele, 1, n_allele, 0, 0);
-      return GK_OK;
-    }
     int rc = gk_colsum_enqueue(ctx, table, n_rows, every.data(), n_allele, scall);
     if (rc) return rc;
-    S->note(0, n_rows, 1, 0, n_allele, 0, 0);
+    if (scall.form == kSumFew) S->note(scall.form, n_rows, n_allele, 1, n_allele, 0, 0);   // n_allele "sets" of one column
+    else S->note(kSumColumns, n_rows, 1, 0, n_allele, 0, 0);
     return GK_OK;
   }
   void colsum_collect() { gk_colsum_collect(ctx, scall, S->colsum.data()); }
@@ -439,10 +405,9 @@ struct GeneSearch {
       std::copy(prev.ids.begin() + (size_t)t * k, prev.ids.begin() + (size_t)(t + 1) * k, sel.ids.begin() + (size_t)i * c);
       sel.ids[(size_t)i * c + k] = cols[a];
     }
-    int kind = 0;
-    int rc = shares_enqueue(ctx, table, n_rows, sel.ids.data(), (int32_t)n_sel, c, scall, &kind);
+    int rc = gk_shares_enqueue(ctx, table, n_rows, sel.ids.data(), (int32_t)n_sel, c, true, scall);
     if (rc) return rc;
-    S->note(kind, n_rows, n_sel, c, S->distinct(sel.ids.data(), sel.ids.size()), 0, 0);
+    S->note(scall.form, n_rows, n_sel, c, S->distinct(sel.ids.data(), sel.ids.size()), 0, 0);
     sums_in_flight = true;
     return GK_OK;
   }
@@ -594,10 +559,11 @@ struct GeneSearch {
 
   void step_end() { S->steps.push_back(std::move(st)); }
 
-  // calls still queued when an error ends the run: their temporaries go back to the pool
-  void abandon() {
-    gk_release(ctx, bcall.temps);
-    gk_release(ctx, scall.temps);
+  // an error ends the run; calls still queued drop themselves when the search goes away (GkCall)
+  void abandon() { finish(); }
+  // a table that is written again: the column sums of the pass before have been waited for and are void
+  void discard() {
+    scall.done();
     finish();
   }
   // the float64 copy this search made for itself (every kernel that reads it has been waited for)
@@ -733,7 +699,7 @@ int sample_search_lockstep(gk_ctx* ctx, const std::vector<gk_ctx*>& cx, gk_tab* 
     gk_gene_job& j = jobs[i];
     std::vector<int32_t> cols((size_t)j.n_allele);
     std::iota(cols.begin(), cols.end(), 0);
-    if (gs[i]) gs[i]->abandon();                                    // a pass that is being repeated: its sums are void
+    if (gs[i]) gs[i]->discard();                                    // a pass that is being repeated: its sums are void
     gs[i].reset(new GeneSearch());
     const GkTable tbl = indexed ? GkTable{j.d_lidx, j.ldm, lut->d_vals} : GkTable{d_L, j.n_rows, nullptr};
     int r = gs[i]->init(ctx_of[i], tbl, indexed ? 0 : d_L, j.n_rows, j.n_rows, j.n_allele, j.d_miss8, j.ldm, j.d_msum,
@@ -911,7 +877,6 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
   auto fail = [&](int code) {
     gk_fetch_cancel(ctx);                        // copies still queued point into the searches that go away now
     for (auto& g : gs) if (g) g->abandon();
-    for (auto& b : batches) if (b) gk_release(ctx, b->call.temps);
     return code;
   };
   auto push = [&](int gene, int stage) {
@@ -972,7 +937,7 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
     if (rc) return rc;
     std::vector<int32_t> cols((size_t)nc);
     std::iota(cols.begin(), cols.end(), 0);
-    if (gs[i]) gs[i]->abandon();                 // the pass before this one: its column sums are void
+    if (gs[i]) gs[i]->discard();                 // the pass before this one: its column sums are void
     gs[i].reset(new GeneSearch());
     rc = gs[i]->init(ctx, GkTable{j.d_L, j.n_rows, nullptr}, j.d_L, j.n_rows, j.n_rows, nc, j.d_miss8, j.ldm, j.d_msum,
                      cols.data(), nc, j.n_steps, j.top_n, argsort);
@@ -1106,11 +1071,10 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
             b->deps.push_back(d);
           }
           if (rc || b->deps.empty()) break;
-          int kind = 0;
-          rc = shares_enqueue(ctx, GkTable{j.d_L, j.n_rows, nullptr}, j.n_rows, b->ids.data(), (int32_t)b->deps.size(), k, b->call,
-                              &kind);
+          rc = gk_shares_enqueue(ctx, GkTable{j.d_L, j.n_rows, nullptr}, j.n_rows, b->ids.data(), (int32_t)b->deps.size(), k, true,
+                                 b->call);
           if (rc) break;
-          gs[b->deps[0]]->S->note(kind, j.n_rows, (int64_t)b->deps.size(), k, gs[b->deps[0]]->S->distinct(b->ids.data(), b->ids.size()), 0, 0);
+          gs[b->deps[0]]->S->note(b->call.form, j.n_rows, (int64_t)b->deps.size(), k, gs[b->deps[0]]->S->distinct(b->ids.data(), b->ids.size()), 0, 0);
           batches.push_back(std::move(b));
           rc = push((int)batches.size() - 1, kOneSet);
         }

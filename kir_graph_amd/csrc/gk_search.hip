@@ -28,6 +28,7 @@
 
 #include "gk_calls.h"
 #include "gk_lut.h"
+#include "gk_tree.h"
 
 namespace {
 
@@ -794,61 +795,51 @@ struct Program {
   std::vector<int32_t> unit0, zero0;      // combine_chunks over one sum per chunk: [0, 1, 2, ...] and all zeros
 };
 
-// returns the (chunk-relative) leaf that holds the node's sum
-int fold_nodes(Program& p, int chunk, int64_t chunk_row0, int start, int n, int first_leaf) {
-  if (n <= kBlockRows) {
-    p.flat.push_back(LeafAbs{chunk_row0 + start, n, chunk});
-    return (int)p.flat.size() - 1 - first_leaf;
-  }
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  const int a = fold_nodes(p, chunk, chunk_row0, start, n2, first_leaf);
-  const int b = fold_nodes(p, chunk, chunk_row0, start + n2, n - n2, first_leaf);
-  p.lops.push_back(TopOp{a, b});
-  return a;
+// the leaves of a chunk and the additions that fold them (setsum_leaves / fold_leaves)
+void fold_nodes(Program& p, int chunk, int64_t chunk_row0, int n) {
+  const int first_leaf = (int)p.flat.size();
+  gk_pairwise_walk(0, n, kBlockRows, 0,
+                   [&](int start, int len, int) {
+                     p.flat.push_back(LeafAbs{chunk_row0 + start, len, chunk});
+                     return (int)p.flat.size() - 1 - first_leaf;
+                   },
+                   [&](int a, int b) { p.lops.push_back(TopOp{a, b}); });
 }
 
 // leaves of a span in post-order; a leaf that completes right sub-trees folds them immediately
-void span_leaves(int start, int n, int slot, std::vector<Leaf>& out) {
-  if (n <= kBlockRows) {
-    out.push_back(Leaf{start, n, slot, 0});
-    return;
-  }
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  span_leaves(start, n2, slot, out);
-  span_leaves(start + n2, n - n2, slot + 1, out);
-  out.back().n_add += 1;   // after the right child finished: slot += slot + 1
+void span_leaves(int start, int n, std::vector<Leaf>& out) {
+  gk_pairwise_walk(start, n, kBlockRows, 0,
+                   [&](int s, int len, int slot) {
+                     out.push_back(Leaf{s, len, slot, 0});
+                     return 0;
+                   },
+                   [&](int, int) { out.back().n_add += 1; });   // after the right child finished: slot += slot + 1
 }
 
-// returns the (chunk-relative) span index that holds the node's sum
-int chunk_nodes(Program& p, int chunk, int64_t chunk_row0, int start, int n, int first_span) {
-  if (n <= kSpanRows) {
-    Span s;
-    s.row0 = chunk_row0 + start;
-    s.leaf_begin = (int32_t)p.leaves.size();
-    if (n <= kHalfRows) {
-      span_leaves(0, n, 0, p.leaves);
-    } else {   // two children on the same slots: park the left sum, add it to the right one
-      int n2 = n / 2;
-      n2 -= n2 % 8;
-      span_leaves(0, n2, 0, p.leaves);
-      p.leaves.back().n_add |= kLeafHold;
-      span_leaves(n2, n - n2, 0, p.leaves);
-      p.leaves.back().n_add |= kLeafAddHold;
-    }
-    s.leaf_end = (int32_t)p.leaves.size();
-    s.chunk = chunk;
-    s.pad = 0;
-    p.spans.push_back(s);
-    return (int)p.spans.size() - 1 - first_span;
-  }
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  const int a = chunk_nodes(p, chunk, chunk_row0, start, n2, first_span);
-  const int b = chunk_nodes(p, chunk, chunk_row0, start + n2, n - n2, first_span);
-  p.top.push_back(TopOp{a, b});
-  return a;
+// the spans of a chunk, each with its leaf program, and the additions that fold them (combine_chunks)
+void chunk_nodes(Program& p, int chunk, int64_t chunk_row0, int n) {
+  const int first_span = (int)p.spans.size();
+  gk_pairwise_walk(0, n, kSpanRows, 0,
+                   [&](int start, int len, int) {
+                     Span s;
+                     s.row0 = chunk_row0 + start;
+                     s.leaf_begin = (int32_t)p.leaves.size();
+                     if (len <= kHalfRows) {
+                       span_leaves(0, len, p.leaves);
+                     } else {   // two children on the same slots: park the left sum, add it to the right one
+                       const int n2 = gk_pairwise_split(len);
+                       span_leaves(0, n2, p.leaves);
+                       p.leaves.back().n_add |= kLeafHold;
+                       span_leaves(n2, len - n2, p.leaves);
+                       p.leaves.back().n_add |= kLeafAddHold;
+                     }
+                     s.leaf_end = (int32_t)p.leaves.size();
+                     s.chunk = chunk;
+                     s.pad = 0;
+                     p.spans.push_back(s);
+                     return (int)p.spans.size() - 1 - first_span;
+                   },
+                   [&](int a, int b) { p.top.push_back(TopOp{a, b}); });
 }
 
 void build_program(int64_t n_rows, Program& p) {
@@ -858,10 +849,10 @@ void build_program(int64_t n_rows, Program& p) {
     const int n = (int)std::min<int64_t>(kChunkRows, n_rows - row0);
     p.chunk_span0.push_back((int32_t)p.spans.size());
     p.chunk_op0.push_back((int32_t)p.top.size());
-    chunk_nodes(p, q, row0, 0, n, (int)p.spans.size());
+    chunk_nodes(p, q, row0, n);
     p.chunk_leaf0.push_back((int32_t)p.flat.size());
     p.chunk_lop0.push_back((int32_t)p.lops.size());
-    fold_nodes(p, q, row0, 0, n, (int)p.flat.size());
+    fold_nodes(p, q, row0, n);
     p.unit0.push_back(q);
     p.zero0.push_back(0);
   }
@@ -873,18 +864,21 @@ void build_program(int64_t n_rows, Program& p) {
   p.zero0.push_back(0);
 }
 
+// a tree program on the device (one block, cached per row count) and the parameter block of the call in hand
 struct DeviceProgram {
-  char* base = nullptr;
-  Leaf* leaves = nullptr;
-  Span* spans = nullptr;
-  int32_t *chunk_span0 = nullptr, *chunk_op0 = nullptr;
-  TopOp* top = nullptr;
+  const char* prog = nullptr;
+  gk_ctx::TreeHead head{};
   int32_t *ids = nullptr, *cols = nullptr;
-  int n_spans = 0, n_chunks = 0;
-  LeafAbs* flat = nullptr;
-  int32_t *chunk_leaf0 = nullptr, *chunk_lop0 = nullptr, *unit0 = nullptr, *zero0 = nullptr;
-  TopOp* lops = nullptr;
-  int n_leaves = 0, max_chunk_leaves = 0;
+  template <typename T> const T* at(size_t off) const { return reinterpret_cast<const T*>(prog + off); }
+  const Leaf* leaves() const { return at<Leaf>(head.o_leaf); }
+  const Span* spans() const { return at<Span>(head.o_span); }
+  const int32_t* chunk_span0() const { return at<int32_t>(head.o_cs); }
+  const int32_t* chunk_op0() const { return at<int32_t>(head.o_co); }
+  const TopOp* top() const { return at<TopOp>(head.o_top); }
+  const LeafAbs* flat() const { return at<LeafAbs>(head.o_flat); }
+  const int32_t* chunk_leaf0() const { return at<int32_t>(head.o_cl); }
+  const int32_t* chunk_lop0() const { return at<int32_t>(head.o_clo); }
+  const TopOp* lops() const { return at<TopOp>(head.o_lops); }
 };
 
 template <typename T>
@@ -899,23 +893,20 @@ size_t put(std::vector<char>& buf, const T* src, size_t n) {
 // (context, row count) and kept (a search makes dozens of calls on the same table).  The per-call
 // id / column arrays go through the context's pinned staging buffer, so a call costs one truly
 // asynchronous copy and no synchronisation before its kernels.
-using CachedProgram = gk_ctx::TreeHead;
 constexpr size_t kMaxCachedPrograms = 64;
 
-int upload_program(gk_ctx* ctx, int64_t n_rows, const int32_t* ids, size_t n_ids, const int32_t* cols, size_t n_cols,
-                   DeviceProgram& d) {
-  char* prog = nullptr;
+// the program of `n_rows` rows, and ids | cols in a block of `call`
+int upload_program(gk_ctx* ctx, GkCall& call, int64_t n_rows, const int32_t* ids, size_t n_ids, const int32_t* cols,
+                   size_t n_cols, DeviceProgram& d) {
   auto hit = ctx->tree_programs.find(n_rows);
-  if (hit != ctx->tree_programs.end()) {
-    prog = (char*)hit->second;
-  } else {
+  if (hit == ctx->tree_programs.end()) {
     Program p;
     build_program(n_rows, p);
     for (size_t q = 0; q + 1 < p.chunk_span0.size(); ++q)
       GK_REQUIRE(p.chunk_span0[q + 1] - p.chunk_span0[q] <= kMaxSpans, "too many spans in a chunk");
     for (const Leaf& lf : p.leaves) GK_REQUIRE(lf.slot <= kMaxSlot, "leaf program deeper than the lane stack");
     std::vector<char> buf;
-    CachedProgram head;
+    gk_ctx::TreeHead head;
     head.o_leaf = put(buf, p.leaves.data(), p.leaves.size());
     head.o_span = put(buf, p.spans.data(), p.spans.size());
     head.o_cs = put(buf, p.chunk_span0.data(), p.chunk_span0.size());
@@ -939,40 +930,23 @@ int upload_program(gk_ctx* ctx, int64_t n_rows, const int32_t* ids, size_t n_ids
       ctx->tree_programs.clear();
       ctx->tree_heads.clear();
     }
-    GK_HIP(gk_pool_malloc(ctx, (void**)&prog, buf.size()));
-    GK_HIP(gk_send(ctx, prog, buf.data(), buf.size()));
-    if (buf.size() > gk_stage_direct())          // a large program goes straight from buf, which goes out of scope
-      GK_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->tree_programs[n_rows] = prog;
+    void* prog = nullptr;
+    GK_HIP(call.take(&prog, buf.size()));
+    GK_HIP(call.send(prog, buf.data(), buf.size()));
+    call.keep(prog);                       // the cache owns it from here
+    hit = ctx->tree_programs.emplace(n_rows, prog).first;
     ctx->tree_heads[n_rows] = head;
   }
-  const CachedProgram& head = ctx->tree_heads[n_rows];
-  d.leaves = (Leaf*)(prog + head.o_leaf);
-  d.spans = (Span*)(prog + head.o_span);
-  d.chunk_span0 = (int32_t*)(prog + head.o_cs);
-  d.chunk_op0 = (int32_t*)(prog + head.o_co);
-  d.top = (TopOp*)(prog + head.o_top);
-  d.flat = (LeafAbs*)(prog + head.o_flat);
-  d.chunk_leaf0 = (int32_t*)(prog + head.o_cl);
-  d.chunk_lop0 = (int32_t*)(prog + head.o_clo);
-  d.lops = (TopOp*)(prog + head.o_lops);
-  d.unit0 = (int32_t*)(prog + head.o_unit);
-  d.zero0 = (int32_t*)(prog + head.o_zero);
-  d.n_leaves = head.n_leaves;
-  d.max_chunk_leaves = head.max_chunk_leaves;
-  d.n_spans = head.n_spans;
-  d.n_chunks = head.n_chunks;
+  d.prog = (const char*)hit->second;
+  d.head = ctx->tree_heads[n_rows];
   // per-call parameters
   const size_t n_par = std::max<size_t>(n_ids + n_cols, 1);
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d.base, n_par * sizeof(int32_t)));
-  {
-    std::vector<int32_t> packed(n_par);   // ids then columns, one copy
-    if (n_ids) memcpy(packed.data(), ids, n_ids * sizeof(int32_t));
-    if (n_cols) memcpy(packed.data() + n_ids, cols, n_cols * sizeof(int32_t));
-    GK_HIP(gk_send(ctx, d.base, packed.data(), n_par * sizeof(int32_t)));
-  }
-  d.ids = (int32_t*)d.base;
-  d.cols = (int32_t*)d.base + n_ids;
+  std::vector<int32_t> packed(n_par);      // ids then columns, one copy
+  if (n_ids) memcpy(packed.data(), ids, n_ids * sizeof(int32_t));
+  if (n_cols) memcpy(packed.data() + n_ids, cols, n_cols * sizeof(int32_t));
+  GK_HIP(call.take((void**)&d.ids, n_par * sizeof(int32_t)));
+  GK_HIP(call.send(d.ids, packed.data(), n_par * sizeof(int32_t)));
+  d.cols = d.ids + n_ids;
   return GK_OK;
 }
 
@@ -994,6 +968,8 @@ int gk_maxsum(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t ld, const int32_
   hipStream_t st = ctx->stream;
   std::vector<int32_t> pcol_host((size_t)n_sets);
   double* d_P = nullptr;
+  GkCall call;                             // the blocks of the call: an early return gives them back
+  call.begin(ctx);
   // second allele of the search: the sets are the single alleles themselves, so the table is
   // symmetric; run the sets in column order and compute the upper triangle only
   std::vector<int32_t> row_of_set;
@@ -1021,38 +997,38 @@ int gk_maxsum(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t ld, const int32_
     for (int t = 0; t < n_sets; ++t) pcol_host[t] = ids[t];
   } else if (c_prev >= 2) {
     for (int t = 0; t < n_sets; ++t) pcol_host[t] = t;
-    GK_HIP(gk_pool_malloc(ctx, (void**)&d_P, (size_t)n_sets * ld * sizeof(double)));
+    GK_HIP(call.take((void**)&d_P, (size_t)n_sets * ld * sizeof(double)));
     int rc0 = gk_setmax(ctx, d_L, n_rows, ld, ids, n_sets, c_prev, gk_addr(d_P));
     if (rc0) return rc0;
   }
   DeviceProgram dp;
-  int rc = upload_program(ctx, n_rows, pcol_host.data(), c_prev ? (size_t)n_sets : 0, cols, (size_t)n_cols, dp);
+  int rc = upload_program(ctx, call, n_rows, pcol_host.data(), c_prev ? (size_t)n_sets : 0, cols, (size_t)n_cols, dp);
   if (rc) return rc;
   double *d_partial = nullptr, *d_out = nullptr;
   const int64_t n_out = (int64_t)n_sets * n_cols;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_partial, (size_t)n_out * dp.n_spans * sizeof(double)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_out, (size_t)n_out * sizeof(double)));
+  GK_HIP(call.take((void**)&d_partial, (size_t)n_out * dp.head.n_spans * sizeof(double)));
+  GK_HIP(call.take((void**)&d_out, (size_t)n_out * sizeof(double)));
   const int tiles_t = (n_sets + kTileT - 1) / kTileT, tiles_a = (n_cols + kTileA - 1) / kTileA;
-  const dim3 grid((unsigned)(tiles_t * tiles_a * dp.n_spans));
+  const dim3 grid((unsigned)(tiles_t * tiles_a * dp.head.n_spans));
   if (c_prev) {
     GK_PROF_EXACT(ctx, "maxsum_chunks",
             GK_KERNEL(maxsum_chunks<true>, grid, dim3(kThreads), 0, st, gk_ptr<double>(d_L), ld,
-                               c_prev >= 2 ? d_P : gk_ptr<double>(d_L), ld, dp.ids, n_sets, dp.cols, n_cols, dp.spans,
-                               dp.leaves, tiles_t * tiles_a, symmetric ? 1 : 0, d_partial));
+                               c_prev >= 2 ? d_P : gk_ptr<double>(d_L), ld, dp.ids, n_sets, dp.cols, n_cols, dp.spans(),
+                               dp.leaves(), tiles_t * tiles_a, symmetric ? 1 : 0, d_partial));
   } else if (n_sets == 1) {
     GK_PROF_EXACT(ctx, "colsum_chunks",
-            GK_KERNEL(colsum_chunks<double>, dim3((unsigned)((n_cols + kColsPerGroup - 1) / kColsPerGroup), (unsigned)dp.n_spans),
-                      dim3(kThreads), 0, st, TableView<double>{gk_ptr<double>(d_L), nullptr}, ld, dp.cols, n_cols, dp.spans,
-                      dp.leaves, d_partial));
+            GK_KERNEL(colsum_chunks<double>, dim3((unsigned)((n_cols + kColsPerGroup - 1) / kColsPerGroup), (unsigned)dp.head.n_spans),
+                      dim3(kThreads), 0, st, TableView<double>{gk_ptr<double>(d_L), nullptr}, ld, dp.cols, n_cols, dp.spans(),
+                      dp.leaves(), d_partial));
   } else {
     GK_PROF_EXACT(ctx, "maxsum_chunks",
             GK_KERNEL(maxsum_chunks<false>, grid, dim3(kThreads), 0, st, gk_ptr<double>(d_L), ld,
-                               gk_ptr<double>(d_L), ld, (const int32_t*)nullptr, n_sets, dp.cols, n_cols, dp.spans,
-                               dp.leaves, tiles_t * tiles_a, 0, d_partial));
+                               gk_ptr<double>(d_L), ld, (const int32_t*)nullptr, n_sets, dp.cols, n_cols, dp.spans(),
+                               dp.leaves(), tiles_t * tiles_a, 0, d_partial));
   }
   GK_PROF(ctx, "combine_chunks",
           GK_KERNEL(combine_chunks, dim3((unsigned)((n_out + kCombOut - 1) / kCombOut)), dim3(kThreads), 0, st,
-                             d_partial, n_out, dp.n_chunks, dp.chunk_span0, dp.chunk_op0, dp.top, 0.0, d_out));
+                             d_partial, n_out, dp.head.n_chunks, dp.chunk_span0(), dp.chunk_op0(), dp.top(), 0.0, d_out));
   GK_HIP(hipGetLastError());
   if (symmetric) {
     std::vector<double> sq((size_t)n_out);
@@ -1065,10 +1041,6 @@ int gk_maxsum(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t ld, const int32_
   } else {
     GK_HIP(gk_fetch(ctx, out, d_out, (size_t)n_out * sizeof(double)));
   }
-  gk_pool_free(ctx, d_partial);
-  gk_pool_free(ctx, d_out);
-  gk_pool_free(ctx, dp.base);
-  gk_pool_free(ctx, d_P);
   return GK_OK;
 }
 
@@ -1077,10 +1049,9 @@ int gk_fraction(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t ld, const int3
   gk_bind(ctx);
   GK_REQUIRE(frac_out, "null output");
   GkSumCall call;
-  int rc = gk_shares_enqueue(ctx, GkTable{d_L, ld, nullptr}, n_rows, ids, n_sets, c, false, call);
-  if (rc == GK_OK && gk_fetch_wait(ctx) != hipSuccess) { gk_set_error("set shares: waiting for the stream failed"); rc = GK_ERR_HIP; }
+  const int rc = gk_call_wait(ctx, call, gk_shares_enqueue(ctx, GkTable{d_L, ld, nullptr}, n_rows, ids, n_sets, c, false, call),
+                              "set shares");
   if (rc == GK_OK) gk_shares_collect(ctx, call, nullptr, frac_out);
-  else gk_release(ctx, call.temps);
   return rc;
 }
 
@@ -1089,10 +1060,9 @@ int gk_setsum(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t ld, const int32_
   gk_bind(ctx);
   GK_REQUIRE(value_out && frac_out, "null output");
   GkSumCall call;
-  int rc = gk_shares_enqueue(ctx, GkTable{d_L, ld, nullptr}, n_rows, ids, n_sets, c, true, call);
-  if (rc == GK_OK && gk_fetch_wait(ctx) != hipSuccess) { gk_set_error("set sums: waiting for the stream failed"); rc = GK_ERR_HIP; }
+  const int rc = gk_call_wait(ctx, call, gk_shares_enqueue(ctx, GkTable{d_L, ld, nullptr}, n_rows, ids, n_sets, c, true, call),
+                              "set sums");
   if (rc == GK_OK) gk_shares_collect(ctx, call, value_out, frac_out);
-  else gk_release(ctx, call.temps);
   return rc;
 }
 
@@ -1102,8 +1072,10 @@ int gk_setmax(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t ld, const int32_
   GK_REQUIRE(ctx && ids && n_rows > 0 && ld >= n_rows && n_sets > 0 && c >= 1 && c <= kMaxC, "bad setmax arguments");
   hipStream_t st = ctx->stream;
   int32_t* d_ids = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_ids, (size_t)n_sets * c * sizeof(int32_t)));
-  GK_HIP(gk_send(ctx, d_ids, ids, (size_t)n_sets * c * sizeof(int32_t)));
+  GkCall call;                             // gives d_ids back, also on an early return
+  call.begin(ctx);
+  GK_HIP(call.take((void**)&d_ids, (size_t)n_sets * c * sizeof(int32_t)));
+  GK_HIP(call.send(d_ids, ids, (size_t)n_sets * c * sizeof(int32_t)));
   int64_t want = (n_rows + kThreads - 1) / kThreads;
   unsigned bx = (unsigned)(want < 1024 ? want : 1024);
   GK_PROF(ctx, "setmax_kernel",
@@ -1111,7 +1083,6 @@ int gk_setmax(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t ld, const int32_
                              ld, d_ids, n_sets, c, gk_ptr<double>(d_P)));
   GK_HIP(hipGetLastError());
   GK_HIP(hipStreamSynchronize(st));
-  gk_pool_free(ctx, d_ids);
   return GK_OK;
 }
 
@@ -1122,24 +1093,20 @@ int gk_setmax(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t ld, const int32_
 static int shares_leafwise(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32_t* ids, int32_t n_sets, int32_t c,
                            int n_cols, size_t lds, GkSumCall& call) {
   DeviceProgram dp;
-  int rc = upload_program(ctx, n_rows, ids, (size_t)n_sets * c, nullptr, 0, dp);
+  int rc = upload_program(ctx, call, n_rows, ids, (size_t)n_sets * c, nullptr, 0, dp);
   if (rc) return rc;
-  call.temps.push_back(dp.base);
   hipStream_t st = ctx->stream;
   const int per_set = c + 1;
   const int64_t n_out = (int64_t)n_sets * per_set;
   double *d_partial = nullptr, *d_chunk = nullptr, *d_out = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_partial, (size_t)n_out * dp.n_leaves * sizeof(double)));
-  call.temps.push_back(d_partial);
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_chunk, (size_t)n_out * dp.n_chunks * sizeof(double)));
-  call.temps.push_back(d_chunk);
+  GK_HIP(call.take((void**)&d_partial, (size_t)n_out * dp.head.n_leaves * sizeof(double)));
+  GK_HIP(call.take((void**)&d_chunk, (size_t)n_out * dp.head.n_chunks * sizeof(double)));
   // the sums go straight into the pinned result ring (fold_leaves' last workgroups store them there): no copy to queue
-  call.back.resize((size_t)n_out);
-  GK_HIP(gk_fetch_direct(ctx, call.back.data(), (size_t)n_out * sizeof(double), (void**)&d_out));
+  GK_HIP(call.result((size_t)n_out * sizeof(double), (void**)&d_out));
   // accumulators per lane group: (c + 1) float64 per set within 128 VGPRs -- 6 sets of 2 alleles, 4 of 3, 3 of 4; a
   // selection beyond 128 x that many sets goes in batches (each batch streams the table once more)
   const int max_slots = c == 2 ? 6 : c == 3 ? 4 : 3;
-  const dim3 grid((unsigned)dp.n_leaves);
+  const dim3 grid((unsigned)dp.head.n_leaves);
   for (int set0 = 0; set0 < n_sets; set0 += kLeafGroups * max_slots) {
     const int n_here = std::min(n_sets - set0, kLeafGroups * max_slots);
     const int slots = (n_here + kLeafGroups - 1) / kLeafGroups;
@@ -1149,7 +1116,7 @@ static int shares_leafwise(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const 
       GK_HIP(hipFuncSetAttribute((const void*)setsum_leaves<C, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
     GK_PROF(ctx, "setsum_leaves",                                                                                           \
             GK_KERNEL((setsum_leaves<C, S>), grid, dim3(kLeafThreads), lds, st, gk_ptr<double>(L.d), L.ld, n_cols,         \
-                      dp.ids + (size_t)set0 * C, n_here, n_sets, dp.flat, d_partial + (size_t)set0 * (C + 1)));           \
+                      dp.ids + (size_t)set0 * C, n_here, n_sets, dp.flat(), d_partial + (size_t)set0 * (C + 1)));           \
   }
     if (c == 2) {
       switch (slots) {
@@ -1176,7 +1143,7 @@ static int shares_leafwise(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const 
     }
 #undef GK_LEAF_GO
   }
-  const size_t fold_lds = (size_t)dp.max_chunk_leaves * kFoldOut * sizeof(double);
+  const size_t fold_lds = (size_t)dp.head.max_chunk_leaves * kFoldOut * sizeof(double);
   if (fold_lds > 48 * 1024)
     GK_HIP(hipFuncSetAttribute((const void*)fold_leaves, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fold_lds));
   uint32_t* tickets = nullptr;
@@ -1185,16 +1152,22 @@ static int shares_leafwise(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const 
   // the leaves of every chunk in the order of the pairwise recursion, then -- in the workgroup that comes last -- the
   // chunk sums in sequence (numpy's outer reduce loop); the shares are handed back undivided (collect divides)
   GK_PROF(ctx, "fold_leaves",
-          GK_KERNEL(fold_leaves, dim3(fold_groups, (unsigned)dp.n_chunks), dim3(kFoldOut), fold_lds, st, d_partial, n_out,
-                    dp.chunk_leaf0, dp.chunk_lop0, dp.lops, d_chunk, dp.n_chunks, tickets, d_out));
+          GK_KERNEL(fold_leaves, dim3(fold_groups, (unsigned)dp.head.n_chunks), dim3(kFoldOut), fold_lds, st, d_partial, n_out,
+                    dp.chunk_leaf0(), dp.chunk_lop0(), dp.lops(), d_chunk, dp.head.n_chunks, tickets, d_out));
   GK_HIP(hipGetLastError());
-  call.n_rows = n_rows;
-  call.n_sets = n_sets;
-  call.c = c;
-  call.with_value = true;
-  call.leafwise = true;
+  GK_HIP(call.finish());
+  call.form = kSumLeaves;
   return GK_OK;
 }
+
+// GK_TEST_HOOKS=setsum=leaves|tiles: the tests compare the forms on one library, in one process, so it is read per call
+enum class SumHook { none, leaves, tiles };
+static SumHook sum_hook() {
+  char form[16];
+  if (!gk_test_hook("setsum", form, sizeof(form))) return SumHook::none;
+  return !strcmp(form, "leaves") ? SumHook::leaves : !strcmp(form, "tiles") ? SumHook::tiles : SumHook::none;
+}
+constexpr int kFewSets = 8;     // sets of a call, or columns of a table, the chunk-owning form takes (gk_setsum_few.hip)
 
 int gk_shares_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32_t* ids, int32_t n_sets, int32_t c,
                       bool with_value, GkSumCall& call) {
@@ -1207,10 +1180,18 @@ int gk_shares_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32
     GK_REQUIRE(ids[i] >= 0, "negative allele id");
     max_id = std::max(max_id, ids[i]);
   }
-  // value + shares of a step's selection, leaf by leaf: every column of the table through LDS once (setsum_leaves)
-  {
-    char form_buf[16];
-    const char* const form = gk_test_hook("setsum", form_buf, sizeof(form_buf)) ? form_buf : nullptr;      // tests compare both forms
+  // the route: few, leaves, tiles.  Value + shares of sets of 2 .. 4 alleles on a float64 table have all three
+  const bool every_form = with_value && !L.indexed() && c >= 2 && c <= 4;
+  const SumHook hook = every_form ? sum_hook() : SumHook::none;
+  if (every_form && n_sets <= kFewSets && hook == SumHook::none)
+    return gk_few_enqueue(ctx, L, n_rows, ids, n_sets, c, call);      // begins and fills the record itself
+  call.begin(ctx);
+  call.n_rows = n_rows;
+  call.n_sets = n_sets;
+  call.c = c;
+  call.with_value = with_value;
+  if (every_form) {
+    // leaf by leaf: every column of the table through LDS once (setsum_leaves)
     const int n_cols = max_id + 1;
     const size_t lds = (size_t)n_cols * kStageLd * sizeof(double);
     // the leaf kernel stages EVERY column below the largest id of the selection: right for a step's few hundred sets,
@@ -1221,10 +1202,11 @@ int gk_shares_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32
     for (int64_t i = 0; i < (int64_t)n_sets * c; ++i)
       if (!named[ids[i]]) { named[ids[i]] = 1; ++distinct; }
     const bool dense = n_sets >= 64 || distinct * 4 >= n_cols;
-    if (with_value && !L.indexed() && c >= 2 && c <= 4 && n_sets <= 4 * kLeafGroups * kLeafSlots && lds <= 158 * 1024 &&
-        ((dense && !(form && !strcmp(form, "tiles"))) || (form && !strcmp(form, "leaves"))))
+    if (n_sets <= 4 * kLeafGroups * kLeafSlots && lds <= 158 * 1024 &&
+        ((dense && hook != SumHook::tiles) || hook == SumHook::leaves))
       return shares_leafwise(ctx, L, n_rows, ids, n_sets, c, n_cols, lds, call);
   }
+  call.form = kSumTiles;
   // Order the sets so that tiles of 32 share columns: the best sets pair a few strong alleles with
   // many partners, so sort by each set's ids taken rarest-first (partners adjacent, hubs shared).
   std::vector<int32_t> freq((size_t)max_id + 1, 0);
@@ -1271,18 +1253,15 @@ int gk_shares_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32
   plan.insert(plan.end(), perm.begin(), perm.end());
 
   DeviceProgram dp;
-  int rc = upload_program(ctx, n_rows, plan.data(), plan.size(), nullptr, 0, dp);
+  int rc = upload_program(ctx, call, n_rows, plan.data(), plan.size(), nullptr, 0, dp);
   if (rc) return rc;
-  call.temps.push_back(dp.base);
   hipStream_t st = ctx->stream;
   double *d_partial = nullptr, *d_out = nullptr;
   const int per_set = c + (with_value ? 1 : 0);
   const int64_t n_out = (int64_t)n_sets * per_set;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_partial, (size_t)n_out * dp.n_spans * sizeof(double)));
-  call.temps.push_back(d_partial);
-  call.back.resize((size_t)n_out);
-  GK_HIP(gk_fetch_direct(ctx, call.back.data(), (size_t)n_out * sizeof(double), (void**)&d_out));      // combine_chunks stores into the result ring
-  const dim3 grid((unsigned)n_tiles, (unsigned)dp.n_spans);
+  GK_HIP(call.take((void**)&d_partial, (size_t)n_out * dp.head.n_spans * sizeof(double)));
+  GK_HIP(call.result((size_t)n_out * sizeof(double), (void**)&d_out));      // combine_chunks stores into the result ring
+  const dim3 grid((unsigned)n_tiles, (unsigned)dp.head.n_spans);
   const size_t lds = (size_t)max_dist * kFracLd * sizeof(double);   // <= 256 columns * 41 * 8 = 84 KB
 #define GK_FRAC_GO(C, V, TL, VIEW)                                                                                   \
   {                                                                                                                  \
@@ -1291,7 +1270,7 @@ int gk_shares_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32
                                  (int)lds));                                                                         \
     GK_PROF(ctx, "fraction_chunks",                                                                                      \
             GK_KERNEL((fraction_chunks<C, V, TL>), grid, dim3(kThreads), lds, st, VIEW, ld, dp.ids, dp.ids + o_cols, \
-                      dp.ids + o_local, dp.ids + o_perm, n_sets, dp.spans, dp.leaves, d_partial));                   \
+                      dp.ids + o_local, dp.ids + o_perm, n_sets, dp.spans(), dp.leaves(), d_partial));                   \
   }
 #define GK_FRAC_LAUNCH_V(C, V)                                                                          \
   if (L.indexed()) GK_FRAC_GO(C, V, uint16_t, (TableView<uint16_t>{gk_ptr<uint16_t>(L.d), L.vals}))     \
@@ -1315,17 +1294,14 @@ int gk_shares_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32
   // with the value riding along the sums are handed back undivided (collect divides the shares by n_rows)
   GK_PROF(ctx, "combine_chunks",
           GK_KERNEL(combine_chunks, dim3((unsigned)((n_out + kCombOut - 1) / kCombOut)), dim3(kThreads), 0, st,
-                             d_partial, n_out, dp.n_chunks, dp.chunk_span0, dp.chunk_op0, dp.top,
+                             d_partial, n_out, dp.head.n_chunks, dp.chunk_span0(), dp.chunk_op0(), dp.top(),
                              with_value ? 0.0 : (double)n_rows, d_out));
   GK_HIP(hipGetLastError());
-  call.n_rows = n_rows;
-  call.n_sets = n_sets;
-  call.c = c;
-  call.with_value = with_value;
+  GK_HIP(call.finish());
   return GK_OK;
 }
 
-void gk_shares_collect(gk_ctx* ctx, GkSumCall& call, double* value_out, double* frac_out) {
+void gk_shares_collect(gk_ctx*, GkSumCall& call, double* value_out, double* frac_out) {
   const int c = call.c;
   if (!call.with_value) {
     if (frac_out) std::copy(call.back.begin(), call.back.end(), frac_out);
@@ -1339,7 +1315,7 @@ void gk_shares_collect(gk_ctx* ctx, GkSumCall& call, double* value_out, double* 
       if (value_out) value_out[k] = src[c];
     }
   }
-  gk_release(ctx, call.temps);
+  call.done();
 }
 
 int gk_colsum_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32_t* cols, int32_t n_cols,
@@ -1347,39 +1323,41 @@ int gk_colsum_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32
   gk_bind(ctx);
   const int64_t ld = L.ld;
   GK_REQUIRE(ctx && L.d && cols && n_rows > 0 && ld >= n_rows && n_cols > 0, "bad column-sum arguments");
+  if (n_cols <= kFewSets && !L.indexed() && sum_hook() == SumHook::none)
+    return gk_few_enqueue(ctx, L, n_rows, cols, n_cols, 1, call);
+  call.begin(ctx);
+  call.n_rows = n_rows;
+  call.n_sets = n_cols;
+  call.form = kSumColumns;
   DeviceProgram dp;
-  int rc = upload_program(ctx, n_rows, nullptr, 0, cols, (size_t)n_cols, dp);
+  int rc = upload_program(ctx, call, n_rows, nullptr, 0, cols, (size_t)n_cols, dp);
   if (rc) return rc;
-  call.temps.push_back(dp.base);
   hipStream_t st = ctx->stream;
   double *d_partial = nullptr, *d_out = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_partial, (size_t)n_cols * dp.n_spans * sizeof(double)));
-  call.temps.push_back(d_partial);
-  call.back.resize((size_t)n_cols);
-  GK_HIP(gk_fetch_direct(ctx, call.back.data(), (size_t)n_cols * sizeof(double), (void**)&d_out));      // combine_chunks stores into the result ring
-  const dim3 cgrid((unsigned)((n_cols + kColsPerGroup - 1) / kColsPerGroup), (unsigned)dp.n_spans);
+  GK_HIP(call.take((void**)&d_partial, (size_t)n_cols * dp.head.n_spans * sizeof(double)));
+  GK_HIP(call.result((size_t)n_cols * sizeof(double), (void**)&d_out));      // combine_chunks stores into the result ring
+  const dim3 cgrid((unsigned)((n_cols + kColsPerGroup - 1) / kColsPerGroup), (unsigned)dp.head.n_spans);
   if (L.indexed())
     GK_PROF_EXACT(ctx, "colsum_chunks",
                   GK_KERNEL(colsum_chunks<uint16_t>, cgrid, dim3(kThreads), 0, st,
-                            TableView<uint16_t>{gk_ptr<uint16_t>(L.d), L.vals}, ld, dp.cols, n_cols, dp.spans, dp.leaves,
+                            TableView<uint16_t>{gk_ptr<uint16_t>(L.d), L.vals}, ld, dp.cols, n_cols, dp.spans(), dp.leaves(),
                             d_partial));
   else
     GK_PROF_EXACT(ctx, "colsum_chunks",
                   GK_KERNEL(colsum_chunks<double>, cgrid, dim3(kThreads), 0, st,
-                            TableView<double>{gk_ptr<double>(L.d), nullptr}, ld, dp.cols, n_cols, dp.spans, dp.leaves,
+                            TableView<double>{gk_ptr<double>(L.d), nullptr}, ld, dp.cols, n_cols, dp.spans(), dp.leaves(),
                             d_partial));
   GK_PROF(ctx, "combine_chunks",
           GK_KERNEL(combine_chunks, dim3((unsigned)((n_cols + kCombOut - 1) / kCombOut)), dim3(kThreads), 0, st,
-                             d_partial, (int64_t)n_cols, dp.n_chunks, dp.chunk_span0, dp.chunk_op0, dp.top, 0.0, d_out));
+                             d_partial, (int64_t)n_cols, dp.head.n_chunks, dp.chunk_span0(), dp.chunk_op0(), dp.top(), 0.0, d_out));
   GK_HIP(hipGetLastError());
-  call.n_rows = n_rows;
-  call.n_sets = n_cols;
+  GK_HIP(call.finish());
   return GK_OK;
 }
 
-void gk_colsum_collect(gk_ctx* ctx, GkSumCall& call, double* out) {
+void gk_colsum_collect(gk_ctx*, GkSumCall& call, double* out) {
   if (out) std::copy(call.back.begin(), call.back.end(), out);
-  gk_release(ctx, call.temps);
+  call.done();
 }
 
 int gk_expand_table(gk_ctx* ctx, const GkTable& L, int64_t n_rows, int32_t n_allele, gk_dptr d_L, int64_t ld) {

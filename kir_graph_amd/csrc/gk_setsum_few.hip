@@ -1,7 +1,7 @@
 // Exact value + shares of a FEW allele sets, and the column sums of a narrow table: one workgroup owns one chunk.
 //
-//   gk_shares_few_enqueue   typing_mulit_allele.py:540-542 for one set + 575-580 (value and undivided shares per set)
-//   gk_colsum_few_enqueue   typing_mulit_allele.py:514 (log_probs[:, cols].sum(axis=0))
+//   gk_few_enqueue, c >= 2  typing_mulit_allele.py:540-542 for one set + 575-580 (value and undivided shares per set)
+//   gk_few_enqueue, c == 1  typing_mulit_allele.py:514 (log_probs[:, cols].sum(axis=0))
 //
 // The one-set steps of exon-first ask for ONE set of 2 .. 4 alleles over a table of ~750 k rows, a dozen times per
 // sample.  setsum_leaves (gk_search.hip) gives such a call a 1024-thread workgroup per 128-row leaf, of which 8 lanes
@@ -10,14 +10,18 @@
 // global memory into registers, folds the leaves in LDS and leaves one sum per output; the workgroup that finishes last
 // for its set adds the chunk sums.  One launch, the named columns read once, nothing staged.
 //
-// The summation tree is numpy's add.reduce, restated from gk_search.hip (which this file must not share code with: the
-// committed traffic measurements are tied to that file's digest): chunks of 8192 rows added in sequence; a chunk halved
+// The summation tree is numpy's add.reduce, as in gk_search.hip.  The DEVICE side is restated here and shares no code with
+// that file: the committed traffic measurements of a kernel are tied to the digest of its own file + gk_common.h
+// (build.KERNEL_SOURCES), so an edit to one file leaves the other's profiles valid.  The host's walk of the tree is
+// gk_tree.h for both; it is host code only, no kernel is compiled from it, and it is in neither digest -- an edit to it
+// invalidates no profile.  Chunks of 8192 rows are added in sequence; a chunk is halved
 // (n2 = n/2, n2 -= n2 % 8) down to leaves of <= 128 rows; a leaf summed by 8 strided accumulators combined as
 // ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then its `len & 7` tail rows in sequence (a leaf shorter than 8 is all tail).
 // The per-row terms are setsum_leaves': the row's maximum, and 1 / (number of alleles that reach it) for each that does.
 #include <algorithm>
 
 #include "gk_calls.h"
+#include "gk_tree.h"
 
 namespace {
 
@@ -212,22 +216,21 @@ __global__ __launch_bounds__(kFewThreads) void setsum_few(const double* __restri
 
 // ---------------------------------------------------------------------------------------------
 // host: the leaves of a chunk of n rows and the additions that fold them (they depend on n only)
-int few_nodes(std::vector<FewLeaf>& leaves, std::vector<FewOp>& ops, int first_leaf, int start, int n) {
-  if (n <= kFewLeafRows) {
-    leaves.push_back(FewLeaf{start, n});
-    return (int)leaves.size() - 1 - first_leaf;
-  }
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  const int a = few_nodes(leaves, ops, first_leaf, start, n2);
-  const int b = few_nodes(leaves, ops, first_leaf, start + n2, n - n2);
-  ops.push_back(FewOp{a, b});
-  return a;
+void few_nodes(std::vector<FewLeaf>& leaves, std::vector<FewOp>& ops, int n) {
+  const int first_leaf = (int)leaves.size();
+  gk_pairwise_walk(0, n, kFewLeafRows, 0,
+                   [&](int start, int len, int) {
+                     leaves.push_back(FewLeaf{start, len});
+                     return (int)leaves.size() - 1 - first_leaf;
+                   },
+                   [&](int a, int b) { ops.push_back(FewOp{a, b}); });
 }
+
+}  // namespace
 
 // `ids`: n_sets x c column ids; c == 1: the sums of n_sets columns.  Results: per set c shares then the value (c >= 2),
 // one sum (c == 1), written by the kernel into call.back's slot of the result ring
-int few_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32_t* ids, int32_t n_sets, int32_t c, GkSumCall& call) {
+int gk_few_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32_t* ids, int32_t n_sets, int32_t c, GkSumCall& call) {
   gk_bind(ctx);
   GK_REQUIRE(ctx && L.d && !L.indexed() && ids && n_rows > 0 && L.ld >= n_rows, "bad arguments of the sums of a few sets");
   GK_REQUIRE(n_sets > 0 && n_sets <= kFewMaxSets, "too many sets for the chunk-owning form");
@@ -244,7 +247,7 @@ int few_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32_t* id
   for (int k = 0; k < 2; ++k) {
     plan.leaf0[k] = (int32_t)leaves.size();
     plan.op0[k] = (int32_t)ops.size();
-    few_nodes(leaves, ops, plan.leaf0[k], 0, lens[k]);
+    few_nodes(leaves, ops, lens[k]);
     plan.n_leaf[k] = (int32_t)leaves.size() - plan.leaf0[k];
     plan.n_op[k] = (int32_t)ops.size() - plan.op0[k];
     GK_REQUIRE(plan.n_leaf[k] <= kFewMaxLeaves && plan.n_op[k] < kFewMaxLeaves && plan.n_op[k] <= kFewThreads,
@@ -257,16 +260,14 @@ int few_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32_t* id
   memcpy(par.data(), ids, n_id * sizeof(int32_t));
   memcpy(par.data() + o_leaf, leaves.data(), leaves.size() * sizeof(FewLeaf));
   if (!ops.empty()) memcpy(par.data() + o_op, ops.data(), ops.size() * sizeof(FewOp));
+  call.begin(ctx);
   int32_t* d_par = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_par, par.size() * sizeof(int32_t)));
-  call.temps.push_back(d_par);
-  GK_HIP(gk_send(ctx, d_par, par.data(), par.size() * sizeof(int32_t)));
+  GK_HIP(call.take((void**)&d_par, par.size() * sizeof(int32_t)));
+  GK_HIP(call.send(d_par, par.data(), par.size() * sizeof(int32_t)));
   double *d_chunk = nullptr, *d_out = nullptr;
   const int64_t n_out = (int64_t)n_sets * kO;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_chunk, (size_t)n_out * n_chunks * sizeof(double)));
-  call.temps.push_back(d_chunk);
-  call.back.resize((size_t)n_out);
-  GK_HIP(gk_fetch_direct(ctx, call.back.data(), (size_t)n_out * sizeof(double), (void**)&d_out));
+  GK_HIP(call.take((void**)&d_chunk, (size_t)n_out * n_chunks * sizeof(double)));
+  GK_HIP(call.result((size_t)n_out * sizeof(double), (void**)&d_out));
   uint32_t* tickets = nullptr;
   { const int trc = gk_ctx_tickets(ctx, (size_t)n_sets, &tickets); if (trc) return trc; }
   const dim3 grid((unsigned)n_chunks, (unsigned)n_sets);
@@ -282,26 +283,13 @@ int few_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32_t* id
   }
 #undef GK_FEW_GO
   GK_HIP(hipGetLastError());
+  GK_HIP(call.finish());
   call.n_rows = n_rows;
   call.n_sets = n_sets;
   call.c = c;
   call.with_value = c >= 2;
-  call.leafwise = false;
+  call.form = kSumFew;
   return GK_OK;
-}
-
-}  // namespace
-
-// value + shares of n_sets <= 4096 sets of 2 .. 4 alleles; unpacked by gk_shares_collect
-int gk_shares_few_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32_t* ids, int32_t n_sets, int32_t c,
-                          GkSumCall& call) {
-  GK_REQUIRE(c >= 2, "a set of one allele is a column sum");
-  return few_enqueue(ctx, L, n_rows, ids, n_sets, c, call);
-}
-
-// the sums of n_cols <= 4096 columns; unpacked by gk_colsum_collect
-int gk_colsum_few_enqueue(gk_ctx* ctx, const GkTable& L, int64_t n_rows, const int32_t* cols, int32_t n_cols, GkSumCall& call) {
-  return few_enqueue(ctx, L, n_rows, cols, n_cols, 1, call);
 }
 
 extern "C" int gk_setsum_few(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t ld, const int32_t* ids, int32_t n_sets,
@@ -309,12 +297,9 @@ extern "C" int gk_setsum_few(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t l
   gk_bind(ctx);
   GK_REQUIRE(value_out && frac_out, "null output");
   GkSumCall call;
-  int rc = few_enqueue(ctx, GkTable{d_L, ld, nullptr}, n_rows, ids, n_sets, c, call);
-  if (rc == GK_OK && gk_fetch_wait(ctx) != hipSuccess) { gk_set_error("sums of a few sets: waiting for the stream failed"); rc = GK_ERR_HIP; }
-  if (rc != GK_OK) {
-    gk_release(ctx, call.temps);
-    return rc;
-  }
+  const int rc = gk_call_wait(ctx, call, gk_few_enqueue(ctx, GkTable{d_L, ld, nullptr}, n_rows, ids, n_sets, c, call),
+                              "sums of a few sets");
+  if (rc != GK_OK) return rc;
   if (c == 1) {                          // one allele owns every row: its share is rows / rows
     gk_colsum_collect(ctx, call, value_out);
     std::fill(frac_out, frac_out + n_sets, 1.0);

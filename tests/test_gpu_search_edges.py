@@ -354,3 +354,56 @@ def test_sets_that_repeat_an_allele(device, monkeypatch, n_rows):
         assert np.array_equal(T.maxsum(homo, a), T.maxsum(a[:, None], a))
     finally:
         T.free()
+
+
+@pytest.mark.parametrize("n_rows", [1, 129, 8193])
+@pytest.mark.parametrize("c", [2, 3, 4])
+def test_setsum_routes_at_most_8_sets_to_the_few_form(device, monkeypatch, n_rows, c):
+    """gk_setsum without a hook: 8 sets run setsum_few and nothing else, 9 sets do not run it; numpy's bits either way."""
+    n_allele = 30
+    L = sr.table(np.random.default_rng(n_rows * 10 + c), n_rows, n_allele)
+    ids = np.random.default_rng(n_rows + c).integers(0, n_allele, (9, c)).astype(np.int32)
+    ids[0, :] = n_allele - 1                   # a homozygous set on the last column
+    T = Table(device, L, pad=3)
+    try:
+        use_form(monkeypatch, None)
+        for n_sets in (8, 9):
+            (value, frac), ran = launches(device, lambda: T.setsum(ids[:n_sets]))
+            if n_sets <= 8:
+                assert ran.get("setsum_few") == 1 and {k for k, n in ran.items() if n} == {"setsum_few"}, ran
+            else:
+                assert "setsum_few" not in ran and ("setsum_leaves" in ran) != ("fraction_chunks" in ran), ran
+            assert np.array_equal(value, sr.setvalue_numpy(L, ids[:n_sets])), n_sets
+            assert np.array_equal(frac, sr.shares_numpy(L, ids[:n_sets]) / n_rows), n_sets
+    finally:
+        T.free()
+
+
+RING_DOUBLES = (4 << 20) // 8                  # a result of more float64 than this does not fit a slot of the result ring
+
+
+@pytest.mark.parametrize("n_sets", [174762, 174763])
+def test_setsum_result_on_both_sides_of_the_result_ring(device, monkeypatch, n_sets):
+    """Sets of 2 alleles bring back 3 float64 each: 174 762 sets are 524 286 values, the last count that fits a slot of the
+    result ring; 174 763 are 524 289, one value past 4 MB, which the ring refuses.  Asserted here: both calls succeed,
+    ran the tiles once and give numpy's bits.  WHICH way a result comes back (ring slot, or pool block + queued copy) is
+    not visible through the C ABI; tests/test_call_record.py asserts it on both sides of the limit.  The plan of the
+    tiles stays under 4 MB on both sides (at most 879 278 int32 for 174 763 sets: tile offsets, two columns, two local
+    indices and the position per set), so only the result crosses the limit."""
+    n_rows, n_allele, c = 9, 40, 2
+    assert (n_sets * (c + 1) > RING_DOUBLES) == (n_sets == 174763)
+    n_tiles = (n_sets + 31) // 32
+    plan_ints = (n_tiles + 1) + n_sets * c + n_sets * c + n_sets
+    assert plan_ints * 4 < (4 << 20) and (n_sets != 174763 or plan_ints == 879278)
+    L = sr.table(np.random.default_rng(n_sets), n_rows, n_allele)
+    ids = np.random.default_rng(n_sets + 1).integers(0, n_allele, (n_sets, c)).astype(np.int32)
+    ids[-1, :] = n_allele - 1
+    T = Table(device, L, pad=3)
+    try:
+        use_form(monkeypatch, None)
+        (value, frac), ran = launches(device, lambda: T.setsum(ids))
+        assert ran.get("fraction_chunks") == 1 and "setsum_leaves" not in ran and "setsum_few" not in ran, ran
+        assert np.array_equal(value, sr.setvalue_numpy(L, ids))
+        assert np.array_equal(frac, sr.shares_numpy(L, ids) / n_rows)
+    finally:
+        T.free()
