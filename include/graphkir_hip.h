@@ -359,6 +359,12 @@ int gk_compat_log_miss_narrow(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t 
  * comes back when some value is still undefined, bit 0 as above (typing_mulit_allele.py:263, 340-381). */
 int gk_compat_patch(gk_ctx* ctx, gk_lut* lut, gk_dptr d_log, int64_t n_rows, int32_t n_allele, gk_dptr d_miss8,
                     int64_t ldm, gk_dptr d_flags);
+/* The row classes gk_compat_log_miss(_cols) works on for a gene of many rows (csrc/gk_rowclass.hip): rows whose KEPT
+ * (id, sign) sequences are equal -- kept as the compatibility kernel keeps them under d_vflag, sign = negative list -- form
+ * one class.  *n_classes = their number; d_class_of (uint32 [n_rows], may be 0) = the class of every row, classes numbered
+ * by their lowest row.  For the tools and the tests; waits for the stream. */
+int gk_row_classes(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag, gk_dptr d_class_of,
+                   int64_t* n_classes);
 /* The index form of gk_compat_log_miss (typing_mulit_allele.py:263, 340-381): d_lidx uint16 [n_allele][ldm] = dense index
  * of every log-likelihood in the value table (0xFFFF while a product's log10 is undefined: resolve and call again);
  * *d_flags bit 1 = the table holds more than 65535 values (use gk_compat_log_miss).  gk_expand_index writes the float64

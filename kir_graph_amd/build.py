@@ -11,7 +11,7 @@ ROOT = PKG.parent
 SOURCES = ["gk_runtime.hip", "gk_scan.hip", "gk_tabulate.hip", "gk_typing.hip", "gk_lut.hip",
            "gk_search.hip", "gk_bound.hip", "gk_em.hip", "gk_cn.hip", "gk_depth.hip", "gk_sampack.cpp", "gk_bamread.cpp", "gk_textout.cpp",
            "gk_comm.cpp", "gk_hostsearch.cpp", "gk_novel.hip", "gk_boot.hip", "gk_callboot.hip", "gk_compat_narrow.hip",
-           "gk_callfit.hip", "gk_callcov.hip", "gk_depthboot.hip", "gk_setsum_few.hip"]
+           "gk_callfit.hip", "gk_callcov.hip", "gk_depthboot.hip", "gk_setsum_few.hip", "gk_rowclass.hip"]
 
 
 def hipcc() -> str:
@@ -75,6 +75,10 @@ KERNEL_SOURCES = {
     "depthw_finish": ["gk_depthboot.hip", "gk_common.h"],
     "depthw_select": ["gk_depthboot.hip", "gk_common.h"],
     "setsum_few": ["gk_setsum_few.hip", "gk_common.h"],
+    "rowclass_keys": ["gk_rowclass.hip", "gk_rowclass.h", "gk_common.h"],
+    "rowclass_verify": ["gk_rowclass.hip", "gk_rowclass.h", "gk_common.h"],
+    "rowclass_rank": ["gk_rowclass.hip", "gk_rowclass.h", "gk_common.h"],
+    "rowclass_expand": ["gk_rowclass.hip", "gk_rowclass.h", "gk_common.h"],
 }
 
 

@@ -8,7 +8,9 @@
 //                  keeps sums of at most 8 sets / 8 columns off setsum_few: gk_shares_enqueue, gk_colsum_enqueue),
 //                  no_libdeflate (zlib for BGZF), wide_compat (column lists of at most 8 alleles through compat_kernel
 //                  instead of compat_rows8), depthw_budget=BYTES (gk_depth_weighted: the bytes a slice of replicates may take,
-//                  so that a few replicates already make several slices); read by the Python side only:
+//                  so that a few replicates already make several slices), row_classes=on|off (gk_compat_log_miss(_cols):
+//                  the table through the row classes of gk_rowclass.hip, or never), rowclass_hashbits=N (their hash cut to
+//                  N bits: rows of different sequences meet in one slot); read by the Python side only:
 //                  bam_reader=samtools, ingest_ahead=N
 #pragma once
 #include <cstdlib>

@@ -18,6 +18,7 @@
 
 #include "gk_common.h"
 #include "gk_lut.h"
+#include "gk_rowclass.h"
 
 namespace {
 
@@ -355,7 +356,13 @@ __global__ __launch_bounds__(kCompatThreads) void compat_kernel(const int32_t* r
                                                                 const uint32_t* mask_t, int words, int n_allele, int a_base,
                                                                 double* probs, uint8_t* miss_out, uint16_t* nvar_out,
                                                                 LutView lut, double empty_p, uint8_t* miss8, int64_t ldm,
-                                                                uint32_t* bound_flags, uint16_t* lidx) {
+                                                                uint32_t* bound_flags, uint16_t* lidx,
+                                                                const uint32_t* n_rows_dev, int64_t ld) {
+  // n_rows_dev: the row count is on the device (the representatives of the row classes, gk_rowclass.hip: n_rows is then its
+  // upper bound, which sized the grid -- workgroups beyond the count fall through the tile loop), and the log-likelihoods
+  // go out ROW by row, probs[row][ld] (the expansion gathers a row's entries of neighbouring columns from one line).
+  // ld: rows per column of probs / miss_out otherwise, apart from the count
+  if (n_rows_dev) n_rows = (int64_t)*n_rows_dev;
   const int n_span = vend - vbeg;   // mask_t: [words][n_span], see transpose_mask
   constexpr int kPassAlleles = 64 * kSlots;
   constexpr int kPassWords = 2 * kSlots;   // bit-row words covering one pass
@@ -490,7 +497,7 @@ __global__ __launch_bounds__(kCompatThreads) void compat_kernel(const int32_t* r
           // a read without any kept variant: 1.0, or 0.999 for every allele when such reads stay in the
           // model (no_empty=False, typing_mulit_allele.py:372-374)
           tile[(lane + 64 * s) * kTileLd + rt] = nvar ? p[s] : empty_p;
-          if (kMiss && miss_out) miss_out[(int64_t)a[s] * n_rows + i] = (uint8_t)min(miss[s], 255u);
+          if (kMiss && miss_out) miss_out[(int64_t)a[s] * ld + i] = (uint8_t)min(miss[s], 255u);
         }
       }
       if (kMiss && nvar_out && lane == 0 && a_base == 0) nvar_out[i] = (uint16_t)min(nvar, 65535u);
@@ -603,14 +610,25 @@ __global__ __launch_bounds__(kCompatThreads) void compat_kernel(const int32_t* r
       // |a - b| sum).  A count >= 100 (the product is about to leave the normal range / underflow, L = -inf) raises the
       // flag that sends the gene to the exact search; NaN (log10 not defined yet) is rewritten by the next pass.
       constexpr int kQuads = kTileRows / 4;
+      if (n_rows_dev) {      // the compact table of the row classes: four consecutive alleles of one read per thread
+        const int n_q = (n_pass + 3) / 4;
+        for (int it = tid; it < n_q * kTileRows; it += kCompatThreads) {
+          const int r = it % kTileRows, al0 = 4 * (it / kTileRows);
+          if (r >= n_r) continue;
+          double* const dst = probs + (row0 + r) * ld + a_base + al0;
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (al0 + j < n_pass) dst[j] = tile[(al0 + j) * kTileLd + r];
+        }
+      }
       for (int it = tid; it < n_pass * kQuads; it += kCompatThreads) {
         const int al = it / kQuads, r0 = 4 * (it % kQuads);
         const double* const cell = &tile[al * kTileLd + r0];
         double v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = cell[j];
-        if (r0 < n_r) {
-          double* const dst = probs + (int64_t)(a_base + al) * n_rows + row0 + r0;
+        if (r0 < n_r && !n_rows_dev) {
+          double* const dst = probs + (int64_t)(a_base + al) * ld + row0 + r0;
           if (r0 + 4 <= n_r) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) dst[j] = v[j];
@@ -636,9 +654,9 @@ __global__ __launch_bounds__(kCompatThreads) void compat_kernel(const int32_t* r
         }
       }
     }
-    if (kLog && miss8 && tile_i == n_tiles - 1) {
+    if (kLog && miss8 && tile_i == n_tiles - 1 && !n_rows_dev) {
       // rows of the mismatch table past the last tile, up to its stride (a multiple of 64 rows): zero, they add nothing
-      // to any |a - b| sum of the bound
+      // to any |a - b| sum of the bound (the compact table of the row classes has no such rows: the expansion zeroes them)
       const int64_t pad0 = n_tiles * kTileRows;
       const int n_pad = (int)((ldm - pad0) / 4);
       for (int it = tid; it < n_pass * n_pad; it += kCompatThreads) {
@@ -679,6 +697,20 @@ __global__ __launch_bounds__(kThreads) void patch_pending(double* __restrict__ L
   }
 }
 
+// Does a log-likelihood table with mismatch bytes go through the row classes?  They pay where most rows share their kept
+// sequence with another row, which comes with depth: the threshold is on the rows of the gene (measurements: DESIGN.md
+// section 8, profiles/r20_row_classes.txt).  GK_TEST_HOOKS=row_classes=on|off, read on every call, forces either route.
+constexpr int64_t kRowClassMinRows = 150000;
+bool use_row_classes(int64_t n_rows, int n_cols) {
+  if (n_cols > 65535) return false;      // a column of the expansion is one blockIdx.y
+  char form[8];
+  if (gk_test_hook("row_classes", form, sizeof(form))) {
+    if (!strcmp(form, "on")) return true;
+    if (!strcmp(form, "off")) return false;
+  }
+  return n_rows >= kRowClassMinRows;
+}
+
 // table_cols (host, n_table_cols > 0): the tables hold these alleles of the gene only, column c = allele table_cols[c]
 template <bool kLog>
 int launch_compat(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag, int vbeg, int vend,
@@ -716,12 +748,42 @@ int launch_compat(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_d
               gk_ptr<uint32_t>(d_mask), vend - vbeg, words, mask_t, bound_flags);
   else if (bound_flags)
     GK_HIP(hipMemsetAsync(bound_flags, 0, sizeof(uint32_t), ctx->stream));
+  // Row classes (gk_rowclass.hip): the chains run on one representative per distinct kept sequence, into a compact table
+  // [class][ldc] of float64 from the pool (ldc: the columns, up to a multiple of 8), and the expansion copies every row's
+  // entries into place.  The class count stays on the device, so the table has room for as many classes as rows: the
+  // scratch costs what the float64 table costs, 8 bytes per row and column, until the expansion has been queued.  The
+  // kernel's mismatch bytes of class c go to row c of the table's own columns (c < n_rows <= ldm) -- they raise flag bit 0
+  // on their way -- and the expansion, which reads the counts back from the log-likelihoods as the kernel does, then
+  // writes every byte of those columns.
+  gk_rowclass classes;
+  const int32_t* k_rows = gk_ptr<int32_t>(d_rows);
+  const uint32_t* k_n_dev = nullptr;
+  double* k_out = out;
+  int64_t k_ld = n_rows;
+  double* Lc = nullptr;
+  const bool by_class = kLog && out && miss8 && bound_flags && !lidx && use_row_classes(n_rows, n_allele);
+  if (by_class) {
+    const int64_t ldc = gk_rowclass_ld(n_allele);
+    int rc = gk_rowclass_enqueue(ctx, tab, k_rows, n_rows, gk_ptr<uint8_t>(d_vflag), &classes);
+    if (rc == GK_OK && gk_pool_malloc(ctx, (void**)&Lc, (size_t)n_rows * ldc * sizeof(double)) != hipSuccess) {
+      gk_set_error("out of device memory for the compact compatibility table");
+      rc = GK_ERR_HIP;
+    }
+    if (rc) {
+      gk_rowclass_free(ctx, &classes);
+      gk_pool_free(ctx, mask_t);
+      gk_pool_free(ctx, d_cols);
+      return rc;
+    }
+    k_rows = classes.rep_rows; k_n_dev = classes.n_classes;
+    k_out = Lc; k_ld = ldc;
+  }
   for (int a_base = 0; a_base < n_allele; a_base += 64 * kMaxSlots) {
     const int slots = std::min(kMaxSlots, (n_allele - a_base + 63) / 64);
 #define GK_COMPAT_GO(S, IDX)                                                                                        \
-  GK_KERNEL((compat_kernel<kLog, S, !kLog, IDX>), grid, block, 0, ctx->stream, gk_ptr<int32_t>(d_rows), n_rows,     \
-            tab->d_off, tab->d_ids, gk_ptr<uint8_t>(d_vflag), vbeg, vend, mask_t, words, n_allele, a_base, out,     \
-            miss, nvar, view, empty_p, miss8, ldm, bound_flags, lidx)
+  GK_KERNEL((compat_kernel<kLog, S, !kLog, IDX>), grid, block, 0, ctx->stream, k_rows, n_rows,                      \
+            tab->d_off, tab->d_ids, gk_ptr<uint8_t>(d_vflag), vbeg, vend, mask_t, words, n_allele, a_base, k_out,   \
+            miss, nvar, view, empty_p, miss8, ldm, bound_flags, lidx, k_n_dev, k_ld)
 #define GK_COMPAT_LAUNCH(S)                              \
   GK_PROF(ctx, "compat_kernel", {                        \
     if (kLog && lidx) GK_COMPAT_GO(S, (kLog && true));   \
@@ -736,8 +798,15 @@ int launch_compat(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_d
 #undef GK_COMPAT_LAUNCH
 #undef GK_COMPAT_GO
   }
+  int rc_expand = GK_OK;
+  if (by_class) {
+    rc_expand = gk_rowclass_expand(ctx, &classes, Lc, k_ld, n_allele, n_rows, out, miss8, ldm);
+    gk_rowclass_free(ctx, &classes);
+    gk_pool_free(ctx, Lc);
+  }
   gk_pool_free(ctx, mask_t);   // stream-ordered reuse: the next user of the block runs after these launches
   gk_pool_free(ctx, d_cols);
+  if (rc_expand) return rc_expand;
   GK_HIP(hipGetLastError());
   return GK_OK;
 }
