@@ -384,6 +384,13 @@ int gk_setsum(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t ld, const int32_
  * sums of a table of at most 8 columns): the same bits.  c = 1: value_out = the column's sum, every share 1. */
 int gk_setsum_few(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t ld, const int32_t* ids, int32_t n_sets, int32_t c,
                   double* value_out, double* frac_out);
+/* TEST ONLY (tests/test_gpu_pool_ownership.py): failure injection into the pool of device blocks.  nth > 0: the nth
+ * allocation from the pool from now on, of any context of the process, fails as if the device were out of memory; once it
+ * has, nothing is armed.  nth = 0 disarms.  *live_out = the blocks of `ctx` that are out of its pool now (handles and device
+ * arrays of the caller included); *mallocs_out = the allocations counted since the call before this one -- they are counted
+ * while a failure is armed only, so a clean run is counted by arming an nth beyond its reach.  Either pointer may be null.
+ * Not for use while other threads allocate. */
+int gk_test_pool_fail(gk_ctx* ctx, int64_t nth, int64_t* live_out, int64_t* mallocs_out);
 
 /* ---- the whole greedy search of one gene, host half included: AlleleTyping.addCandidate called n_steps times
  * (typing_mulit_allele.py:478-598 with 156-214, 456-476), in the calling thread, without the host language's

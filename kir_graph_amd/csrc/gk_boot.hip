@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "gk_common.h"
+#include "gk_blocks.h"
 #include "gk_squarem.h"
 
 namespace {
@@ -199,13 +200,13 @@ int gk_em_bootstrap(gk_ctx* ctx, const gk_boot_job* jobs, int32_t n_jobs, int32_
   if (draws.empty()) return GK_OK;
   // ---- device
   hipStream_t st = ctx->stream;
-  PoolTemps temps(ctx);
+  GkBlocks temps(ctx);
   // a failure after the first queued copy: the stream still reads this call's vectors and may write its outputs
   auto fail = [&](const char* what) {
     const hipError_t e = hipGetLastError();
     gk_fetch_cancel(ctx);
     gk_set_error("EM bootstrap: %s: %s", what, hipGetErrorString(e));
-    return temps.done(GK_ERR_HIP);
+    return GK_ERR_HIP;
   };
   BootDraw* d_draws = nullptr;
   EmGene* d_genes = nullptr;
@@ -216,19 +217,19 @@ int gk_em_bootstrap(gk_ctx* ctx, const gk_boot_job* jobs, int32_t n_jobs, int32_
   const size_t cnt_bytes = (size_t)n_boot * row_sets * sizeof(uint32_t);
   const size_t prob_bytes = (size_t)n_boot * row_prob * sizeof(double);
   const size_t it_bytes = (size_t)n_boot * n_jobs * sizeof(int);
-  if (temps.take((void**)&d_draws, draws.size() * sizeof(BootDraw)) != hipSuccess ||
-      temps.take((void**)&d_cum, cum.size() * sizeof(uint32_t)) != hipSuccess ||
-      temps.take((void**)&d_cnt, cnt_bytes) != hipSuccess ||
-      temps.take((void**)&d_genes, h.genes.size() * sizeof(EmGene)) != hipSuccess ||
-      temps.take((void**)&d_so, h.set_off.size() * sizeof(uint32_t)) != hipSuccess ||
-      temps.take((void**)&d_mem, h.members.size() * sizeof(uint16_t)) != hipSuccess ||
-      temps.take((void**)&d_ao, h.al_off.size() * sizeof(uint32_t)) != hipSuccess ||
-      temps.take((void**)&d_as, h.al_sets.size() * sizeof(uint32_t)) != hipSuccess ||
-      temps.take((void**)&d_scale, (size_t)n_boot * row_scale * sizeof(double)) != hipSuccess ||
-      temps.take((void**)&d_prob, prob_bytes) != hipSuccess ||
-      temps.take((void**)&d_it, it_bytes) != hipSuccess) {
+  if (temps.take(&d_draws, draws.size() * sizeof(BootDraw)) != hipSuccess ||
+      temps.take(&d_cum, cum.size() * sizeof(uint32_t)) != hipSuccess ||
+      temps.take(&d_cnt, cnt_bytes) != hipSuccess ||
+      temps.take(&d_genes, h.genes.size() * sizeof(EmGene)) != hipSuccess ||
+      temps.take(&d_so, h.set_off.size() * sizeof(uint32_t)) != hipSuccess ||
+      temps.take(&d_mem, h.members.size() * sizeof(uint16_t)) != hipSuccess ||
+      temps.take(&d_ao, h.al_off.size() * sizeof(uint32_t)) != hipSuccess ||
+      temps.take(&d_as, h.al_sets.size() * sizeof(uint32_t)) != hipSuccess ||
+      temps.take(&d_scale, (size_t)n_boot * row_scale * sizeof(double)) != hipSuccess ||
+      temps.take(&d_prob, prob_bytes) != hipSuccess ||
+      temps.take(&d_it, it_bytes) != hipSuccess) {
     gk_set_error("out of device memory for the EM bootstrap of a sample");
-    return temps.done(GK_ERR_HIP);
+    return GK_ERR_HIP;
   }
   const size_t em_lds = sizeof(EmLds) + (size_t)std::min(h.max_sets, kBootScaleLds) * sizeof(double);
   if ((draw_lds > 48 * 1024 && hipFuncSetAttribute((const void*)boot_resample, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -236,7 +237,7 @@ int gk_em_bootstrap(gk_ctx* ctx, const gk_boot_job* jobs, int32_t n_jobs, int32_
       (em_lds > 48 * 1024 && hipFuncSetAttribute((const void*)boot_em_batch, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                 (int)em_lds) != hipSuccess)) {
     gk_set_error("EM bootstrap: %zu / %zu bytes of LDS refused", draw_lds, em_lds);
-    return temps.done(GK_ERR_HIP);
+    return GK_ERR_HIP;
   }
   // the sources of the large copies live until the stream is waited for below
   if (gk_send(ctx, d_draws, draws.data(), draws.size() * sizeof(BootDraw)) != hipSuccess ||
@@ -264,7 +265,7 @@ int gk_em_bootstrap(gk_ctx* ctx, const gk_boot_job* jobs, int32_t n_jobs, int32_
   }
   if (counts_out && gk_fetch_queue(ctx, counts_out, d_cnt, cnt_bytes) != hipSuccess) return fail("queueing the counts");
   if (hipGetLastError() != hipSuccess || gk_fetch_wait(ctx) != hipSuccess) return fail("launch");
-  return temps.done(GK_OK);
+  return GK_OK;
 }
 
 }  // extern "C"

@@ -22,7 +22,7 @@
 // (4 x 8): move them together.
 #include <algorithm>
 
-#include "gk_common.h"
+#include "gk_blocks.h"
 
 namespace {
 
@@ -177,13 +177,13 @@ int gk_weighted_sums(gk_ctx* ctx, gk_dptr d_V, int64_t ld, int64_t n_rows, int32
     return GK_ERR_CAPACITY;
   }
   hipStream_t st = ctx->stream;
+  GkBlocks temps(ctx);
   double *d_partial = nullptr, *d_out = nullptr;
-  if (gk_pool_malloc(ctx, (void**)&d_partial, (size_t)(n_chunks * n_cells) * sizeof(double)) != hipSuccess) {
+  if (temps.take(&d_partial, (size_t)(n_chunks * n_cells) * sizeof(double)) != hipSuccess) {
     gk_set_error("out of device memory for the partial sums of a call bootstrap");
     return GK_ERR_HIP;
   }
-  if (gk_pool_malloc(ctx, (void**)&d_out, (size_t)n_cells * sizeof(double)) != hipSuccess) {
-    gk_pool_free(ctx, d_partial);
+  if (temps.take(&d_out, (size_t)n_cells * sizeof(double)) != hipSuccess) {
     gk_set_error("out of device memory for the sums of a call bootstrap");
     return GK_ERR_HIP;
   }
@@ -197,10 +197,9 @@ int gk_weighted_sums(gk_ctx* ctx, gk_dptr d_V, int64_t ld, int64_t n_rows, int32
   if (e != hipSuccess) {
     gk_fetch_cancel(ctx);
     gk_set_error("call bootstrap: weighted sums: %s", hipGetErrorString(e));
+    return GK_ERR_HIP;
   }
-  gk_pool_free(ctx, d_partial);
-  gk_pool_free(ctx, d_out);
-  return e == hipSuccess ? GK_OK : GK_ERR_HIP;
+  return GK_OK;
 }
 
 }  // extern "C"

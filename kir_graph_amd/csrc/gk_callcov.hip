@@ -40,7 +40,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "gk_common.h"
+#include "gk_blocks.h"
 
 namespace {
 
@@ -234,16 +234,23 @@ int gk_call_coverage(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compac
   const int64_t n_tracks = 2 + 2 * (int64_t)n_cols;
   const int64_t slots = n_tracks * (gene_len + 1), total = n_tracks * gene_len;
   hipStream_t st = ctx->stream;
-  uint32_t *diff = nullptr, *scan = nullptr;
-  if (gk_pool_malloc(ctx, (void**)&diff, (size_t)slots * sizeof(uint32_t)) != hipSuccess ||
-      gk_pool_malloc(ctx, (void**)&scan, (size_t)slots * sizeof(uint32_t)) != hipSuccess) {
-    if (diff) gk_pool_free(ctx, diff);
+  GkBlocks temps(ctx);
+  // the depths get a block of their own: written over the scan, word i would be gone before the thread that reads it
+  // as slot i = at' of an earlier track's position runs
+  uint32_t *diff = nullptr, *scan = nullptr, *depth = nullptr;
+  if (temps.take(&diff, (size_t)slots * sizeof(uint32_t)) != hipSuccess ||
+      temps.take(&scan, (size_t)slots * sizeof(uint32_t)) != hipSuccess) {
     gk_set_error("out of device memory for the tracks of a call coverage");
     return GK_ERR_HIP;
   }
+  auto fail = [&](hipError_t err) {
+    gk_fetch_cancel(ctx);
+    gk_set_error("call coverage: %s", hipGetErrorString(err));
+    return GK_ERR_HIP;
+  };
   hipError_t e = hipMemsetAsync(diff, 0, (size_t)slots * sizeof(uint32_t), st);
-  int rc = GK_OK;
-  if (e == hipSuccess) {
+  if (e != hipSuccess) return fail(e);
+  {
     CovSample s;
     const uint32_t* c_off = gk_ptr<const uint32_t>(d_compact);
     s.mates = gk_ptr<const gk_mate>(d_mates);
@@ -307,30 +314,19 @@ int gk_call_coverage(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compac
     if (e == hipSuccess) e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(scan, diff, (size_t)slots * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess) rc = gk_scan_u32(ctx, scan, slots, nullptr);
-  if (e == hipSuccess && rc == GK_OK) {
-    // the depths get a block of their own: written over the scan, word i would be gone before the thread that reads it
-    // as slot i = at' of an earlier track's position runs
-    uint32_t* depth = nullptr;
-    if (gk_pool_malloc(ctx, (void**)&depth, (size_t)total * sizeof(uint32_t)) != hipSuccess) {
-      gk_set_error("out of device memory for the tracks of a call coverage");
-      rc = GK_ERR_HIP;
-    } else {
-      GK_PROF(ctx, "callcov_finish", GK_KERNEL(callcov_finish, dim3((unsigned)((total + kCovThreads - 1) / kCovThreads)),
-                                               dim3(kCovThreads), 0, st, scan, diff, gene_len, total, depth));
-      e = hipGetLastError();
-      if (e == hipSuccess) e = gk_fetch(ctx, depth_out, depth, (size_t)total * sizeof(uint32_t));
-      gk_pool_free(ctx, depth);
-    }
+  if (e != hipSuccess) return fail(e);
+  const int rc = gk_scan_u32(ctx, scan, slots, nullptr);
+  if (rc) return rc;
+  if (temps.take(&depth, (size_t)total * sizeof(uint32_t)) != hipSuccess) {
+    gk_set_error("out of device memory for the tracks of a call coverage");
+    return GK_ERR_HIP;
   }
-  if (e != hipSuccess) {
-    gk_fetch_cancel(ctx);
-    gk_set_error("call coverage: %s", hipGetErrorString(e));
-    rc = GK_ERR_HIP;
-  }
-  gk_pool_free(ctx, diff);
-  gk_pool_free(ctx, scan);
-  return rc;
+  GK_PROF(ctx, "callcov_finish", GK_KERNEL(callcov_finish, dim3((unsigned)((total + kCovThreads - 1) / kCovThreads)),
+                                           dim3(kCovThreads), 0, st, scan, diff, gene_len, total, depth));
+  e = hipGetLastError();
+  if (e == hipSuccess) e = gk_fetch(ctx, depth_out, depth, (size_t)total * sizeof(uint32_t));
+  if (e != hipSuccess) return fail(e);
+  return GK_OK;
 }
 
 }  // extern "C"

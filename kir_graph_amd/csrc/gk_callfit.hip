@@ -27,7 +27,7 @@
 // move them together.
 #include <algorithm>
 
-#include "gk_common.h"
+#include "gk_blocks.h"
 
 namespace {
 
@@ -274,8 +274,9 @@ int gk_call_fit(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32
     fc.c[k] = cols[k];
   }
   hipStream_t st = ctx->stream;
+  GkBlocks temps(ctx);
   unsigned long long* d_out = nullptr;
-  if (gk_pool_malloc(ctx, (void**)&d_out, kFitCounters * sizeof(unsigned long long)) != hipSuccess) {
+  if (temps.take(&d_out, kFitCounters * sizeof(unsigned long long)) != hipSuccess) {
     gk_set_error("out of device memory for the counters of a call fit");
     return GK_ERR_HIP;
   }
@@ -300,9 +301,8 @@ int gk_call_fit(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32
   if (e != hipSuccess) {
     gk_fetch_cancel(ctx);
     gk_set_error("call fit: %s", hipGetErrorString(e));
+    return GK_ERR_HIP;
   }
-  gk_pool_free(ctx, d_out);
-  if (e != hipSuccess) return GK_ERR_HIP;
   for (int i = 0; i < kFitBins; ++i) hist_out[i] = host[i];
   m_out[0] = host[kFitBins];
   for (int i = 0; i < 3 * n_cols; ++i) col_out[i] = host[kFitBins + 1 + i];
@@ -324,7 +324,8 @@ int gk_call_fit_extra(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows,
   hipStream_t st = ctx->stream;
   unsigned long long* d_with = nullptr;
   const size_t bytes = (size_t)n_table_cols * sizeof(unsigned long long);
-  if (gk_pool_malloc(ctx, (void**)&d_with, bytes) != hipSuccess) {
+  GkBlocks temps(ctx);
+  if (temps.take(&d_with, bytes) != hipSuccess) {
     gk_set_error("out of device memory for the sums of a call fit");
     return GK_ERR_HIP;
   }
@@ -339,9 +340,9 @@ int gk_call_fit_extra(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows,
   if (e != hipSuccess) {
     gk_fetch_cancel(ctx);
     gk_set_error("call fit: extra copies: %s", hipGetErrorString(e));
+    return GK_ERR_HIP;
   }
-  gk_pool_free(ctx, d_with);
-  return e == hipSuccess ? GK_OK : GK_ERR_HIP;
+  return GK_OK;
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 #include <utility>
 #include <vector>
 
-#include "gk_common.h"
+#include "gk_blocks.h"
 
 // What a call took from the context, owned: its pool blocks and the pending delivery of its result (GkCallOf<T>::back).
 // An enqueue starts with begin(), takes everything through take / send / result and ends with finish(); `collect` ends
@@ -31,7 +31,6 @@ struct GkCall {
       blocks_ = std::move(o.blocks_);
       due_ = o.due_;
       pending_ = o.pending_;
-      o.blocks_.clear();
       o.due_ = nullptr;
       o.pending_ = false;
     }
@@ -42,18 +41,13 @@ struct GkCall {
   void begin(gk_ctx* ctx) {
     drop();
     ctx_ = ctx;
+    blocks_.begin(ctx);
   }
   // a pool block of the call
-  hipError_t take(void** p, size_t bytes) {
-    const hipError_t e = gk_pool_malloc(ctx_, p, bytes);
-    if (e == hipSuccess) blocks_.push_back(*p);
-    return e;
-  }
+  template <typename T>
+  hipError_t take(T** p, size_t bytes) { return blocks_.take(p, bytes); }
   // the block stays out when the call is over (it has another owner now)
-  void keep(void* p) {
-    for (size_t i = 0; i < blocks_.size(); ++i)
-      if (blocks_[i] == p) { blocks_.erase(blocks_.begin() + (long)i); return; }
-  }
+  void keep(const void* p) { blocks_.keep(p); }
   // host -> device; `src` may be reused at once (a transfer too large for the pinned ring goes straight from `src`, so
   // the stream is waited for)
   hipError_t send(void* dst_dev, const void* src, size_t bytes) {
@@ -73,8 +67,7 @@ struct GkCall {
   void done() {
     pending_ = false;
     due_ = nullptr;
-    for (void* p : blocks_) gk_pool_free(ctx_, p);
-    blocks_.clear();
+    blocks_.release();
   }
   // the call is given up while its result may still be on the way: the stream is drained and the queued deliveries of
   // the context are dropped (gk_fetch_cancel) before the result's memory may go away.  Nothing to do for a record that
@@ -103,7 +96,7 @@ struct GkCall {
 
  private:
   gk_ctx* ctx_ = nullptr;
-  std::vector<void*> blocks_;
+  GkBlocks blocks_;
   void* dst_ = nullptr;            // where the result is delivered (the owner's `back`)
   size_t dst_bytes_ = 0;
   const void* due_ = nullptr;      // pool block whose copy to dst_ finish() queues

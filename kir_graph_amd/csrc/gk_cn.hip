@@ -7,7 +7,7 @@
 // linspace / the reference's formulas produce them; exp / log come from the device math library,
 // so likelihoods agree with scipy to a few ulp and the integer copy numbers are identical unless
 // two candidate bases tie to that precision.
-#include "gk_common.h"
+#include "gk_blocks.h"
 
 namespace {
 
@@ -72,7 +72,8 @@ int gk_cn_fit(gk_ctx* ctx, const double* x, const double* density, int32_t bins,
   hipStream_t st = ctx->stream;
   double* d = nullptr;
   const size_t n_all = (size_t)2 * bins + n_bases + n_cn + n_bases;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d, n_all * sizeof(double)));
+  GkBlocks temps(ctx);
+  GK_HIP(temps.take(&d, n_all * sizeof(double)));
   double *d_x = d, *d_den = d + bins, *d_bases = d + 2 * bins, *d_dev = d_bases + n_bases, *d_ll = d_dev + n_cn;
   GK_HIP(hipMemcpyAsync(d_x, x, (size_t)bins * sizeof(double), hipMemcpyHostToDevice, st));
   GK_HIP(hipMemcpyAsync(d_den, density, (size_t)bins * sizeof(double), hipMemcpyHostToDevice, st));
@@ -83,7 +84,6 @@ int gk_cn_fit(gk_ctx* ctx, const double* x, const double* density, int32_t bins,
   GK_HIP(hipGetLastError());
   GK_HIP(hipMemcpyAsync(loglik_out, d_ll, (size_t)n_bases * sizeof(double), hipMemcpyDeviceToHost, st));
   GK_HIP(hipStreamSynchronize(st));
-  gk_pool_free(ctx, d);
   return GK_OK;
 }
 
@@ -94,8 +94,9 @@ int gk_cn_assign(gk_ctx* ctx, const double* x, int32_t bins, double base, const 
   hipStream_t st = ctx->stream;
   double* d = nullptr;
   int32_t* d_cn = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d, (size_t)(bins + n_cn) * sizeof(double)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_cn, (size_t)bins * sizeof(int32_t)));
+  GkBlocks temps(ctx);
+  GK_HIP(temps.take(&d, (size_t)(bins + n_cn) * sizeof(double)));
+  GK_HIP(temps.take(&d_cn, (size_t)bins * sizeof(int32_t)));
   GK_HIP(hipMemcpyAsync(d, x, (size_t)bins * sizeof(double), hipMemcpyHostToDevice, st));
   GK_HIP(hipMemcpyAsync(d + bins, dev, (size_t)n_cn * sizeof(double), hipMemcpyHostToDevice, st));
   GK_KERNEL(cn_assign_kernel, dim3((unsigned)((bins + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, d,
@@ -103,8 +104,6 @@ int gk_cn_assign(gk_ctx* ctx, const double* x, int32_t bins, double base, const 
   GK_HIP(hipGetLastError());
   GK_HIP(hipMemcpyAsync(cn_of_bin_out, d_cn, (size_t)bins * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   GK_HIP(hipStreamSynchronize(st));
-  gk_pool_free(ctx, d);
-  gk_pool_free(ctx, d_cn);
   return GK_OK;
 }
 

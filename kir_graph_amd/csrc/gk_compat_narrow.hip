@@ -10,7 +10,7 @@
 // 64 lanes multiply factors nobody stores, and its time is the issue of those instructions whatever the column count.
 #include <algorithm>
 
-#include "gk_common.h"
+#include "gk_blocks.h"
 #include "gk_lut.h"
 
 namespace {
@@ -273,8 +273,9 @@ int gk_compat_log_miss_narrow(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t 
   const int n_span = vend - vbeg;
   NarrowCols cols{};
   for (int c = 0; c < n_table_cols; ++c) cols.c[c] = table_cols[c];
+  GkBlocks temps(ctx);
   uint8_t* colbits = nullptr;
-  if (gk_pool_malloc(ctx, (void**)&colbits, (size_t)std::max(n_span, 4)) != hipSuccess) {
+  if (temps.take(&colbits, (size_t)std::max(n_span, 4)) != hipSuccess) {
     gk_set_error("out of device memory for the column bytes");
     return GK_ERR_HIP;
   }
@@ -293,7 +294,6 @@ int gk_compat_log_miss_narrow(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t 
     else GK_ROWS8_GO(8);
   });
 #undef GK_ROWS8_GO
-  gk_pool_free(ctx, colbits);   // stream-ordered reuse: the next user of the block runs after these launches
   GK_HIP(hipGetLastError());
   return GK_OK;
 }

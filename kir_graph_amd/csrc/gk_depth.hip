@@ -8,7 +8,7 @@
 // the concatenated backbones, one exclusive scan turns it into depths.
 #include <cstddef>
 
-#include "gk_common.h"
+#include "gk_blocks.h"
 
 namespace {
 
@@ -85,9 +85,10 @@ static int depth_of(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compact
   hipStream_t st = ctx->stream;
   uint32_t *diff = nullptr, *scan = nullptr;
   int64_t* d_off = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&diff, (size_t)(total + 1) * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&scan, (size_t)(total + 1) * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_off, (size_t)(n_gene + 1) * sizeof(int64_t)));
+  GkBlocks temps(ctx);
+  GK_HIP(temps.take(&diff, (size_t)(total + 1) * sizeof(uint32_t)));
+  GK_HIP(temps.take(&scan, (size_t)(total + 1) * sizeof(uint32_t)));
+  GK_HIP(temps.take(&d_off, (size_t)(n_gene + 1) * sizeof(int64_t)));
   GK_HIP(hipMemsetAsync(diff, 0, (size_t)(total + 1) * sizeof(uint32_t), st));
   GK_HIP(hipMemcpyAsync(d_off, gene_off, (size_t)(n_gene + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
   if (tab->n_valid) {
@@ -108,9 +109,6 @@ static int depth_of(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compact
   GK_HIP(hipGetLastError());
   GK_HIP(hipMemcpyAsync(depth_out, diff, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   GK_HIP(hipStreamSynchronize(st));
-  gk_pool_free(ctx, diff);
-  gk_pool_free(ctx, scan);
-  gk_pool_free(ctx, d_off);
   return GK_OK;
 }
 

@@ -31,7 +31,7 @@
 #include <cstddef>
 #include <vector>
 
-#include "gk_common.h"
+#include "gk_blocks.h"
 
 namespace {
 
@@ -291,31 +291,32 @@ int gk_depth_weighted(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compa
   // replicates of one slice: their difference arrays and the scan copy stay within the budget
   const int64_t slice = std::max<int64_t>(1, std::min<int64_t>(n_boot, (int64_t)(depthw_budget() / (2 * sizeof(uint32_t) * (size_t)slots))));
   hipStream_t st = ctx->stream;
-  std::vector<void*> blocks;
-  auto take = [&](size_t bytes) -> void* {
-    void* p = nullptr;
-    if (gk_pool_malloc(ctx, &p, bytes) != hipSuccess) return nullptr;
-    blocks.push_back(p);
-    return p;
+  GkBlocks temps(ctx);
+  uint32_t *diff = nullptr, *scan = nullptr, *d_stat = nullptr;
+  int64_t *d_off = nullptr, *d_rank = nullptr;
+  unsigned long long* d_sum = nullptr;
+  uint8_t* d_sel = nullptr;
+  // every way out but the last drains the stream: sel / rank / gene_off and depth_out are the caller's again
+  auto fail = [&](hipError_t err) {
+    gk_fetch_cancel(ctx);
+    gk_set_error("weighted depth: %s", hipGetErrorString(err));
+    return GK_ERR_HIP;
   };
-  uint32_t* diff = (uint32_t*)take((size_t)slice * slots * sizeof(uint32_t));
-  uint32_t* scan = (uint32_t*)take((size_t)slice * slots * sizeof(uint32_t));
-  int64_t* d_off = (int64_t*)take((size_t)(n_gene + 1) * sizeof(int64_t));
-  int64_t* d_rank = (int64_t*)take((size_t)2 * n_gene * sizeof(int64_t));
-  uint32_t* d_stat = (uint32_t*)take(2 * n_cells * sizeof(uint32_t));
-  unsigned long long* d_sum = (unsigned long long*)take(n_cells * sizeof(unsigned long long));
-  uint8_t* d_sel = sel ? (uint8_t*)take((size_t)total) : nullptr;
-  int rc = GK_OK;
-  hipError_t e = hipSuccess;
-  if (!diff || !scan || !d_off || !d_rank || !d_stat || !d_sum || (sel && !d_sel)) {
+  if (temps.take(&diff, (size_t)slice * slots * sizeof(uint32_t)) != hipSuccess ||
+      temps.take(&scan, (size_t)slice * slots * sizeof(uint32_t)) != hipSuccess ||
+      temps.take(&d_off, (size_t)(n_gene + 1) * sizeof(int64_t)) != hipSuccess ||
+      temps.take(&d_rank, (size_t)2 * n_gene * sizeof(int64_t)) != hipSuccess ||
+      temps.take(&d_stat, 2 * n_cells * sizeof(uint32_t)) != hipSuccess ||
+      temps.take(&d_sum, n_cells * sizeof(unsigned long long)) != hipSuccess ||
+      (sel && temps.take(&d_sel, (size_t)total) != hipSuccess)) {
+    gk_fetch_cancel(ctx);
     gk_set_error("out of device memory for the replicates of a weighted depth");
-    rc = GK_ERR_HIP;
+    return GK_ERR_HIP;
   }
-  if (rc == GK_OK) {
-    e = gk_send(ctx, d_off, gene_off, (size_t)(n_gene + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = gk_send(ctx, d_rank, rank, (size_t)2 * n_gene * sizeof(int64_t));
-    if (e == hipSuccess && sel) e = gk_send(ctx, d_sel, sel, (size_t)total);      // once, for every slice
-  }
+  hipError_t e = gk_send(ctx, d_off, gene_off, (size_t)(n_gene + 1) * sizeof(int64_t));
+  if (e == hipSuccess) e = gk_send(ctx, d_rank, rank, (size_t)2 * n_gene * sizeof(int64_t));
+  if (e == hipSuccess && sel) e = gk_send(ctx, d_sel, sel, (size_t)total);      // once, for every slice
+  if (e != hipSuccess) return fail(e);
   DwSample s;
   const uint32_t* c_off = gk_ptr<const uint32_t>(d_compact);
   s.mates = gk_ptr<const gk_mate>(d_mates);
@@ -329,11 +330,11 @@ int gk_depth_weighted(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compa
   s.n_spill = tab->n_spill;
   const uint32_t* W = gk_ptr<const uint32_t>(d_W);
   const unsigned mate_groups = (unsigned)((2 * tab->n_valid + kDwThreads - 1) / kDwThreads);
-  for (int64_t b0 = 0; b0 < n_boot && rc == GK_OK && e == hipSuccess; b0 += slice) {
+  for (int64_t b0 = 0; b0 < n_boot; b0 += slice) {
     const int nb = (int)std::min<int64_t>(slice, n_boot - b0);
     const int64_t n = (int64_t)nb * slots;
     e = hipMemsetAsync(diff, 0, (size_t)n * sizeof(uint32_t), st);
-    if (e != hipSuccess) break;
+    if (e != hipSuccess) return fail(e);
     const dim3 grid(mate_groups, (unsigned)((nb + kBootPerThread - 1) / kBootPerThread));
     if (c_off)
       GK_PROF(ctx, "depthw_mark", GK_KERNEL(depthw_mark<true>, grid, dim3(kDwThreads), 0, st, s, (int)multiple, d_off, (int)n_gene,
@@ -343,9 +344,9 @@ int gk_depth_weighted(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compa
                                             W + b0 * ldw, ldw, nb, slots, diff));
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(scan, diff, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) break;
-    rc = gk_scan_u32(ctx, scan, n, nullptr);
-    if (rc != GK_OK) break;
+    if (e != hipSuccess) return fail(e);
+    const int rc = gk_scan_u32(ctx, scan, n, nullptr);
+    if (rc) { gk_fetch_cancel(ctx); return rc; }
     GK_PROF(ctx, "depthw_finish", GK_KERNEL(depthw_finish, dim3((unsigned)((n + kDwThreads - 1) / kDwThreads)), dim3(kDwThreads), 0,
                                             st, scan, diff, n));
     GK_PROF(ctx, "depthw_select", GK_KERNEL(depthw_select, dim3((unsigned)n_gene, (unsigned)nb), dim3(kDwThreads), 0, st, diff, slots,
@@ -354,19 +355,13 @@ int gk_depth_weighted(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compa
     if (e == hipSuccess && depth_out)      // the tracks without their extra slots (the tests ask for them)
       e = hipMemcpy2DAsync(depth_out + b0 * total, (size_t)total * sizeof(uint32_t), diff, (size_t)slots * sizeof(uint32_t),
                            (size_t)total * sizeof(uint32_t), (size_t)nb, hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) return fail(e);
   }
-  if (rc == GK_OK && e == hipSuccess) e = gk_fetch_queue(ctx, stat_out, d_stat, 2 * n_cells * sizeof(uint32_t));
-  if (rc == GK_OK && e == hipSuccess) e = gk_fetch_queue(ctx, sum_out, d_sum, n_cells * sizeof(uint64_t));
-  if (rc == GK_OK && e == hipSuccess) e = gk_fetch_wait(ctx);
-  if (e != hipSuccess || rc != GK_OK) {
-    gk_fetch_cancel(ctx);      // drains the stream: sel / rank / gene_off may be the caller's again
-    if (e != hipSuccess) {
-      gk_set_error("weighted depth: %s", hipGetErrorString(e));
-      rc = GK_ERR_HIP;
-    }
-  }
-  for (void* p : blocks) gk_pool_free(ctx, p);
-  return rc;
+  e = gk_fetch_queue(ctx, stat_out, d_stat, 2 * n_cells * sizeof(uint32_t));
+  if (e == hipSuccess) e = gk_fetch_queue(ctx, sum_out, d_sum, n_cells * sizeof(uint64_t));
+  if (e == hipSuccess) e = gk_fetch_wait(ctx);
+  if (e != hipSuccess) return fail(e);
+  return GK_OK;
 }
 
 }  // extern "C"

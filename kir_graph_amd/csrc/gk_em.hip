@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "gk_common.h"
+#include "gk_blocks.h"
 #include "gk_squarem.h"
 
 namespace {
@@ -455,23 +456,23 @@ struct EmHost : EmForms {
 int run_em(gk_ctx* ctx, EmHost& h, int64_t n_prob, int iter_max, double diff_threshold, std::vector<double>& probs,
            std::vector<int>& iters) {
   hipStream_t st = ctx->stream;
-  PoolTemps temps(ctx);
+  GkBlocks temps(ctx);
   EmGene* d_genes = nullptr;
   double *d_w = nullptr, *d_scale = nullptr, *d_prob = nullptr;
   uint32_t *d_so = nullptr, *d_ao = nullptr, *d_as = nullptr;
   uint16_t* d_mem = nullptr;
   int* d_it = nullptr;
-  if (temps.take((void**)&d_genes, h.genes.size() * sizeof(EmGene)) != hipSuccess ||
-      temps.take((void**)&d_w, h.weight.size() * sizeof(double)) != hipSuccess ||
-      temps.take((void**)&d_scale, h.weight.size() * sizeof(double)) != hipSuccess ||
-      temps.take((void**)&d_so, h.set_off.size() * sizeof(uint32_t)) != hipSuccess ||
-      temps.take((void**)&d_mem, h.members.size() * sizeof(uint16_t)) != hipSuccess ||
-      temps.take((void**)&d_ao, h.al_off.size() * sizeof(uint32_t)) != hipSuccess ||
-      temps.take((void**)&d_as, h.al_sets.size() * sizeof(uint32_t)) != hipSuccess ||
-      temps.take((void**)&d_prob, (size_t)std::max<int64_t>(n_prob, 1) * sizeof(double)) != hipSuccess ||
-      temps.take((void**)&d_it, h.genes.size() * sizeof(int)) != hipSuccess) {
+  if (temps.take(&d_genes, h.genes.size() * sizeof(EmGene)) != hipSuccess ||
+      temps.take(&d_w, h.weight.size() * sizeof(double)) != hipSuccess ||
+      temps.take(&d_scale, h.weight.size() * sizeof(double)) != hipSuccess ||
+      temps.take(&d_so, h.set_off.size() * sizeof(uint32_t)) != hipSuccess ||
+      temps.take(&d_mem, h.members.size() * sizeof(uint16_t)) != hipSuccess ||
+      temps.take(&d_ao, h.al_off.size() * sizeof(uint32_t)) != hipSuccess ||
+      temps.take(&d_as, h.al_sets.size() * sizeof(uint32_t)) != hipSuccess ||
+      temps.take(&d_prob, (size_t)std::max<int64_t>(n_prob, 1) * sizeof(double)) != hipSuccess ||
+      temps.take(&d_it, h.genes.size() * sizeof(int)) != hipSuccess) {
     gk_set_error("out of device memory for the EM of a sample");
-    return temps.done(GK_ERR_HIP);
+    return GK_ERR_HIP;
   }
   // the sources of these copies live until the stream is waited for below
   hipMemcpyAsync(d_genes, h.genes.data(), h.genes.size() * sizeof(EmGene), hipMemcpyHostToDevice, st);
@@ -487,7 +488,7 @@ int run_em(gk_ctx* ctx, EmHost& h, int64_t n_prob, int iter_max, double diff_thr
   if (lds > 48 * 1024 &&
       hipFuncSetAttribute((const void*)em_kernel_genes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
     gk_set_error("EM: %zu bytes of LDS refused", lds);
-    return temps.done(GK_ERR_HIP);
+    return GK_ERR_HIP;
   }
   const EmArrays A{d_w, d_scale, d_so, d_mem, d_ao, d_as};
   GK_PROF(ctx, "em_kernel_genes", GK_KERNEL(em_kernel_genes, dim3((unsigned)h.genes.size()), dim3(kEmThreads), lds, st, d_genes, A,
@@ -498,9 +499,9 @@ int run_em(gk_ctx* ctx, EmHost& h, int64_t n_prob, int iter_max, double diff_thr
   hipMemcpyAsync(iters.data(), d_it, h.genes.size() * sizeof(int), hipMemcpyDeviceToHost, st);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
     gk_set_error("EM: %s", hipGetErrorString(hipGetLastError()));
-    return temps.done(GK_ERR_HIP);
+    return GK_ERR_HIP;
   }
-  return temps.done(GK_OK);
+  return GK_OK;
 }
 
 }  // namespace
@@ -521,11 +522,11 @@ int gk_em_sets(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, int32_t
   j.vbeg = vbeg; j.n_span = vend - vbeg; j.words = words; j.mask_in_lds = mask_fits_lds(vend - vbeg, words) ? 1 : 0;
   j.sets = gk_ptr<uint32_t>(d_sets_out);
   j.n_blocks = blocks_for(n_rows, lanes_per_pair(words));
+  GkBlocks temps(ctx);
   EmSetsJob* d_jobs = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_jobs, sizeof(EmSetsJob)));
+  GK_HIP(temps.take(&d_jobs, sizeof(EmSetsJob)));
   const hipError_t e = gk_send(ctx, d_jobs, jobs.data(), sizeof(EmSetsJob));
   const int rc = e == hipSuccess ? launch_sets(ctx, tab, jobs, d_jobs) : GK_ERR_HIP;
-  gk_pool_free(ctx, d_jobs);
   if (rc) return rc;
   GK_HIP(hipGetLastError());
   return GK_OK;
@@ -543,10 +544,10 @@ int gk_em_distinct(gk_ctx* ctx, gk_dptr d_sets, int64_t n_rows, int32_t words, i
   char* block = nullptr;      // [tag | cnt | row | n_out, flags | job]
   const size_t o_cnt = (size_t)n_slots * 8, o_row = o_cnt + (size_t)n_slots * 4, o_n = o_row + (size_t)n_slots * 4, o_job = o_n + 16;
   uint32_t *d_out_sets = nullptr, *d_out_count = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&block, o_job + sizeof(EmSetsJob)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_out_sets, (size_t)max_out * words * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_out_count, (size_t)max_out * sizeof(uint32_t)));
-  auto done = [&](int rc) { gk_pool_free(ctx, block); gk_pool_free(ctx, d_out_sets); gk_pool_free(ctx, d_out_count); return rc; };
+  GkBlocks temps(ctx);
+  GK_HIP(temps.take(&block, o_job + sizeof(EmSetsJob)));
+  GK_HIP(temps.take(&d_out_sets, (size_t)max_out * words * sizeof(uint32_t)));
+  GK_HIP(temps.take(&d_out_count, (size_t)max_out * sizeof(uint32_t)));
   std::vector<EmSetsJob> jobs(1);
   uint32_t back[2] = {0, 0};      // distinct sets, flags
   for (uint32_t seed = 0; seed < 4; ++seed) {
@@ -558,17 +559,17 @@ int gk_em_distinct(gk_ctx* ctx, gk_dptr d_sets, int64_t n_rows, int32_t words, i
     j.n_blocks = blocks_for(n_rows, lanes_per_pair(words));
     j.out_sets = d_out_sets; j.out_count = d_out_count; j.max_out = (uint32_t)max_out;
     if (hipMemsetAsync(block, 0, o_row, st) != hipSuccess || hipMemsetAsync(block + o_row, 0xFF, (size_t)n_slots * 4, st) != hipSuccess ||
-        hipMemsetAsync(block + o_n, 0, 16, st) != hipSuccess) return done(GK_ERR_HIP);
+        hipMemsetAsync(block + o_n, 0, 16, st) != hipSuccess) return GK_ERR_HIP;
     EmSetsJob* d_jobs = (EmSetsJob*)(block + o_job);
-    if (gk_send(ctx, d_jobs, jobs.data(), sizeof(EmSetsJob)) != hipSuccess) return done(GK_ERR_HIP);
+    if (gk_send(ctx, d_jobs, jobs.data(), sizeof(EmSetsJob)) != hipSuccess) return GK_ERR_HIP;
     launch_hash(ctx, jobs, d_jobs);
     launch_verify_emit(ctx, jobs, d_jobs);
     if (hipGetLastError() != hipSuccess || gk_fetch(ctx, back, block + o_n, sizeof(back)) != hipSuccess) {
       gk_set_error("distinct candidate sets: %s", hipGetErrorString(hipGetLastError()));
-      return done(GK_ERR_HIP);
+      return GK_ERR_HIP;
     }
     if (!(back[1] & 2u)) break;       // no two different sets under one hash
-    if (seed == 3) { gk_set_error("candidate sets: hash collisions under four seeds"); return done(GK_ERR_ASSERT); }
+    if (seed == 3) { gk_set_error("candidate sets: hash collisions under four seeds"); return GK_ERR_ASSERT; }
   }
   const uint32_t n = back[0];
   int rc = GK_OK;
@@ -580,11 +581,11 @@ int gk_em_distinct(gk_ctx* ctx, gk_dptr d_sets, int64_t n_rows, int32_t words, i
         gk_fetch_queue(ctx, count_out, d_out_count, (size_t)n * sizeof(uint32_t)) != hipSuccess ||
         gk_fetch_wait(ctx) != hipSuccess) {
       gk_fetch_cancel(ctx);
-      return done(GK_ERR_HIP);
+      return GK_ERR_HIP;
     }
   }
   *n_out = (int32_t)n;
-  return done(rc);
+  return rc;
 }
 
 int gk_em_run(gk_ctx* ctx, const uint32_t* sets, const double* weight, int32_t n_sets, int32_t words, int32_t n_allele,
@@ -625,7 +626,7 @@ int gk_sample_em(gk_ctx* ctx, gk_tab* tab, gk_em_job* jobs, int32_t n_jobs, int3
     std::vector<int64_t> order;
   };
   std::vector<Work> work((size_t)n_jobs);
-  PoolTemps temps(ctx);
+  GkBlocks temps(ctx);
   int64_t out_off = 0;
   std::vector<int64_t> prob_off((size_t)n_jobs, 0);
   for (int i = 0; i < n_jobs; ++i) {
@@ -657,18 +658,18 @@ int gk_sample_em(gk_ctx* ctx, gk_tab* tab, gk_em_job* jobs, int32_t n_jobs, int3
   EmSetsJob* d_sj = nullptr;
   const size_t o_row = tag_bytes, o_small = tag_bytes + row_bytes, table_bytes = o_small + live.size() * 16;
   if (!live.empty()) {
-    if (temps.take((void**)&table, table_bytes) != hipSuccess || temps.take((void**)&d_sj, live.size() * sizeof(EmSetsJob)) != hipSuccess) {
+    if (temps.take(&table, table_bytes) != hipSuccess || temps.take(&d_sj, live.size() * sizeof(EmSetsJob)) != hipSuccess) {
       gk_set_error("out of device memory for the candidate sets of a sample");
-      return temps.done(GK_ERR_HIP);
+      return GK_ERR_HIP;
     }
     for (int i : live) {
       gk_em_job& j = jobs[i];
       Work& w = work[i];
-      if (temps.take((void**)&w.d_sets, (size_t)j.n_rows * j.words * sizeof(uint32_t)) != hipSuccess ||
-          temps.take((void**)&w.d_out_sets, (size_t)w.cap * j.words * sizeof(uint32_t)) != hipSuccess ||
-          temps.take((void**)&w.d_out_count, (size_t)w.cap * sizeof(uint32_t)) != hipSuccess) {
+      if (temps.take(&w.d_sets, (size_t)j.n_rows * j.words * sizeof(uint32_t)) != hipSuccess ||
+          temps.take(&w.d_out_sets, (size_t)w.cap * j.words * sizeof(uint32_t)) != hipSuccess ||
+          temps.take(&w.d_out_count, (size_t)w.cap * sizeof(uint32_t)) != hipSuccess) {
         gk_set_error("out of device memory for the candidate sets of a gene");
-        return temps.done(GK_ERR_HIP);
+        return GK_ERR_HIP;
       }
     }
   }
@@ -696,33 +697,33 @@ int gk_sample_em(gk_ctx* ctx, gk_tab* tab, gk_em_job* jobs, int32_t n_jobs, int3
         hipMemsetAsync(table + o_small, 0, live.size() * 16, st) != hipSuccess ||
         gk_send(ctx, d_sj, sj.data(), sj.size() * sizeof(EmSetsJob)) != hipSuccess) {
       gk_set_error("sample EM: %s", hipGetErrorString(hipGetLastError()));
-      return temps.done(GK_ERR_HIP);
+      return GK_ERR_HIP;
     }
     if (seed == 0) {
       const int rc = launch_sets(ctx, tab, sj, d_sj);
-      if (rc) return temps.done(rc);
+      if (rc) return rc;
     } else {
       launch_hash(ctx, sj, d_sj);      // the sets stand; only their hashes are taken again
     }
     launch_verify_emit(ctx, sj, d_sj);
     for (size_t q = 0; q < live.size(); ++q)
-      if (gk_fetch_queue(ctx, work[live[q]].back, sj[q].n_out, 8) != hipSuccess) { gk_fetch_cancel(ctx); return temps.done(GK_ERR_HIP); }
+      if (gk_fetch_queue(ctx, work[live[q]].back, sj[q].n_out, 8) != hipSuccess) { gk_fetch_cancel(ctx); return GK_ERR_HIP; }
     if (hipGetLastError() != hipSuccess || gk_fetch_wait(ctx) != hipSuccess) {
       gk_fetch_cancel(ctx);
       gk_set_error("sample EM: %s", hipGetErrorString(hipGetLastError()));
-      return temps.done(GK_ERR_HIP);
+      return GK_ERR_HIP;
     }
     bool collided = false;
     for (int i : live) collided = collided || (work[i].back[1] & 2u);
     if (!collided) break;
-    if (seed == 3) { gk_set_error("candidate sets: hash collisions under four seeds"); return temps.done(GK_ERR_ASSERT); }
+    if (seed == 3) { gk_set_error("candidate sets: hash collisions under four seeds"); return GK_ERR_ASSERT; }
   }
   for (int i : live) {
     Work& w = work[i];
     const uint32_t n = w.back[0];
     if ((w.back[1] & 1u) || n > w.cap) {
       gk_set_error("%u distinct candidate sets exceed the capacity %u of the one-call EM", n, w.cap);
-      return temps.done(GK_ERR_CAPACITY);
+      return GK_ERR_CAPACITY;
     }
     if (!n) continue;
     w.sets.resize((size_t)n * jobs[i].words);
@@ -730,10 +731,10 @@ int gk_sample_em(gk_ctx* ctx, gk_tab* tab, gk_em_job* jobs, int32_t n_jobs, int3
     if (gk_fetch_queue(ctx, w.sets.data(), w.d_out_sets, w.sets.size() * sizeof(uint32_t)) != hipSuccess ||
         gk_fetch_queue(ctx, w.mult.data(), w.d_out_count, w.mult.size() * sizeof(uint32_t)) != hipSuccess) {
       gk_fetch_cancel(ctx);
-      return temps.done(GK_ERR_HIP);
+      return GK_ERR_HIP;
     }
   }
-  if (gk_fetch_wait(ctx) != hipSuccess) { gk_fetch_cancel(ctx); return temps.done(GK_ERR_HIP); }
+  if (gk_fetch_wait(ctx) != hipSuccess) { gk_fetch_cancel(ctx); return GK_ERR_HIP; }
   // ---- phase 2 (host): numpy.unique's order, the reads naming each allele, the empty set dropped, the sparse forms
   EmHost h;
   std::vector<int> gene_job;
@@ -776,18 +777,18 @@ int gk_sample_em(gk_ctx* ctx, gk_tab* tab, gk_em_job* jobs, int32_t n_jobs, int3
       gene_job.push_back(i);
     }
   }
-  if (h.genes.empty()) return temps.done(GK_OK);
+  if (h.genes.empty()) return GK_OK;
   // ---- phase 3: every gene's SQUAREM loop in one launch
   std::vector<double> probs;
   std::vector<int> iters;
   const int rc = run_em(ctx, h, out_off, iter_max, diff_threshold, probs, iters);
-  if (rc) return temps.done(rc);
+  if (rc) return rc;
   for (size_t k = 0; k < h.genes.size(); ++k) {
     const int i = gene_job[k];
     jobs[i].iterations = iters[k];
     for (int a = 0; a < jobs[i].n_allele; ++a) prob_out[prob_off[i] + a] = probs[(size_t)(prob_off[i] + a)];
   }
-  return temps.done(GK_OK);
+  return GK_OK;
 }
 
 }  // extern "C"

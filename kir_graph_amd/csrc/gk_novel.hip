@@ -24,7 +24,7 @@
 // (novel_discover.py:139-143).  All counts are integers: the result does not depend on the order of arrival.
 #include <climits>
 
-#include "gk_common.h"
+#include "gk_blocks.h"
 
 namespace {
 
@@ -177,18 +177,16 @@ int gk_novel_assign(gk_ctx* ctx, gk_dptr d_probs, int64_t n_rows, int32_t n_cols
     return GK_OK;
   }
   GK_REQUIRE(d_probs && d_code, "null device pointer");
+  GkBlocks temps(ctx);
   uint32_t *d_count = nullptr, *d_cols = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_count, sizeof(uint32_t) * 2 * bins));
+  GK_HIP(temps.take(&d_count, sizeof(uint32_t) * 2 * bins));
   int32_t* d_first = (int32_t*)(d_count + bins);
-  if (gk_pool_malloc(ctx, (void**)&d_cols, sizeof(uint32_t) * kMaxEntries) != hipSuccess) {
-    gk_pool_free(ctx, d_count);
+  if (temps.take(&d_cols, sizeof(uint32_t) * kMaxEntries) != hipSuccess) {
     gk_set_error("device allocation failed");
     return GK_ERR_HIP;
   }
   auto fail = [&](const char* what) {
     gk_fetch_cancel(ctx);            // nothing queued may be delivered into the caller's buffers after we return
-    gk_pool_free(ctx, d_count);
-    gk_pool_free(ctx, d_cols);
     gk_set_error("%s", what);
     return GK_ERR_HIP;
   };
@@ -211,8 +209,6 @@ int gk_novel_assign(gk_ctx* ctx, gk_dptr d_probs, int64_t n_rows, int32_t n_cols
       (code_out && gk_fetch_queue(ctx, code_out, gk_ptr<void>(d_code), sizeof(uint16_t) * n_rows) != hipSuccess) ||
       gk_fetch_wait(ctx) != hipSuccess)
     return fail("novel_assign: fetch failed");
-  gk_pool_free(ctx, d_count);
-  gk_pool_free(ctx, d_cols);
   return GK_OK;
 }
 
@@ -237,16 +233,10 @@ int gk_novel_confusion(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows,
   if (n_rows == 0 || n_slots == 0 || nvt == 0) return GK_OK;
   GK_REQUIRE(d_rows && d_code && d_vflag && (d_carry || vend == vbeg), "null device pointer");
   const int64_t n_cells = nvt * n_slots;
-  std::vector<void*> temps;
-  auto release = [&]() { for (void* p : temps) gk_pool_free(ctx, p); };
-  auto take = [&](void** p, size_t bytes) {
-    if (gk_pool_malloc(ctx, p, bytes ? bytes : 16) != hipSuccess) return false;
-    temps.push_back(*p);
-    return true;
-  };
+  GkBlocks temps(ctx);
+  auto take = [&](auto** p, size_t bytes) { return temps.take(p, bytes) == hipSuccess; };
   auto fail = [&](const char* what) {
     gk_fetch_cancel(ctx);            // drop what is queued: the caller's buffers may go away
-    release();
     gk_set_error("%s", what);
     return GK_ERR_HIP;
   };
@@ -254,9 +244,9 @@ int gk_novel_confusion(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows,
   unsigned long long *d_key = nullptr, *d_tot = nullptr;
   int32_t* d_meta = nullptr;       // entry_col[16], entry_slot[16]
   uint32_t* d_n = nullptr;
-  if (!take((void**)&d_cnt, sizeof(uint32_t) * n_cells) || !take((void**)&d_key, sizeof(uint64_t) * n_cells) ||
-      !take((void**)&d_tot, sizeof(uint64_t) * kStats * n_slots) || !take((void**)&d_meta, sizeof(int32_t) * 2 * kMaxEntries) ||
-      !take((void**)&d_n, sizeof(uint32_t)))
+  if (!take(&d_cnt, sizeof(uint32_t) * n_cells) || !take(&d_key, sizeof(uint64_t) * n_cells) ||
+      !take(&d_tot, sizeof(uint64_t) * kStats * n_slots) || !take(&d_meta, sizeof(int32_t) * 2 * kMaxEntries) ||
+      !take(&d_n, sizeof(uint32_t)))
     return fail("novel_confusion: device allocation failed");
   int32_t meta[2 * kMaxEntries];
   for (int e = 0; e < kMaxEntries; ++e) {
@@ -280,8 +270,8 @@ int gk_novel_confusion(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows,
   uint32_t* d_count = nullptr;
   unsigned long long* d_okey = nullptr;
   const int64_t cap = std::min<int64_t>(n_cells, std::max<int64_t>(max_out, 1));
-  if (!take((void**)&d_slot, sizeof(int32_t) * cap) || !take((void**)&d_ord, sizeof(int32_t) * cap) ||
-      !take((void**)&d_count, sizeof(uint32_t) * cap) || !take((void**)&d_okey, sizeof(uint64_t) * cap))
+  if (!take(&d_slot, sizeof(int32_t) * cap) || !take(&d_ord, sizeof(int32_t) * cap) ||
+      !take(&d_count, sizeof(uint32_t) * cap) || !take(&d_okey, sizeof(uint64_t) * cap))
     return fail("novel_confusion: device allocation failed");
   GK_PROF(ctx, "novel_compact",
           GK_KERNEL(novel_compact, dim3(nblk(n_cells)), dim3(kThreads), 0, ctx->stream, d_cnt, d_key, n_cells, nvt, cap,
@@ -293,7 +283,6 @@ int gk_novel_confusion(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows,
     return fail("novel_confusion: fetch failed");
   *n_out = found;
   if ((int64_t)found > max_out) {
-    release();
     gk_set_error("novel_confusion: %u counted variants, room for %lld", found, (long long)max_out);
     return GK_ERR_CAPACITY;
   }
@@ -303,7 +292,6 @@ int gk_novel_confusion(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows,
        gk_fetch_queue(ctx, count_out, d_count, sizeof(uint32_t) * found) != hipSuccess ||
        gk_fetch_queue(ctx, key_out, d_okey, sizeof(uint64_t) * found) != hipSuccess || gk_fetch_wait(ctx) != hipSuccess))
     return fail("novel_confusion: fetch failed");
-  release();
   return GK_OK;
 }
 

@@ -1,20 +1,18 @@
 // Row classes of one gene's rows (gk_rowclass.hip): which rows of the compatibility table carry the same kept
 // (id, sign) sequence.  Everything is queued on the context's stream; nothing is waited for.
 #pragma once
-#include "gk_common.h"
+#include "gk_blocks.h"
 
 struct gk_rowclass {
   int32_t* rep_rows = nullptr;      // [n_rows]: rows[] of the classes' representatives, in row order; *n_classes are set
   uint32_t* class_of = nullptr;     // [n_rows]: class of every row = the rank of its representative
   uint32_t* n_classes = nullptr;    // device: 1 <= *n_classes <= n_rows
-  std::vector<void*> temps;         // pool blocks behind all of it (gk_rowclass_free)
+  GkBlocks blocks;                  // the pool blocks behind all of it: they go back with the record
 };
 
-// n_rows > 0.  On an error nothing is left allocated.
+// n_rows > 0.  On an error `rc` is left as it was.
 int gk_rowclass_enqueue(gk_ctx* ctx, gk_tab* tab, const int32_t* d_rows, int64_t n_rows, const uint8_t* d_vflag,
                         gk_rowclass* rc);
-// stream-ordered: the blocks may be given back as soon as their last user has been queued
-void gk_rowclass_free(gk_ctx* ctx, gk_rowclass* rc);
 // L [n_cols][n_rows] from the compact table Lc [class][ldc] (ldc = gk_rowclass_ld(n_cols): the columns, up to a multiple of
 // 8), and miss8 [n_cols][ldm], every byte of it: the counts read back from the log-likelihoods as compat_kernel reads
 // them back, rows from n_rows to ldm zero

@@ -23,7 +23,6 @@
 //                     store, as pass 2 of compat_kernel -- and as there the count is read back from the log-likelihood
 //                     (the same arithmetic on the same double gives the same byte), so one gather serves both tables; the
 //                     rows of miss8 from n_rows up to its stride are zeroed.
-#include "gk_common.h"
 #include "gk_rowclass.h"
 
 namespace {
@@ -239,12 +238,6 @@ inline unsigned nblk(int64_t n) { return (unsigned)((n + kThreads - 1) / kThread
 
 int64_t gk_rowclass_ld(int n_cols) { return ((int64_t)n_cols + kExpandCols - 1) / kExpandCols * kExpandCols; }
 
-void gk_rowclass_free(gk_ctx* ctx, gk_rowclass* rc) {
-  for (void* t : rc->temps) gk_pool_free(ctx, t);
-  rc->temps.clear();
-  rc->rep_rows = nullptr; rc->class_of = nullptr; rc->n_classes = nullptr;
-}
-
 int gk_rowclass_enqueue(gk_ctx* ctx, gk_tab* tab, const int32_t* d_rows, int64_t n_rows, const uint8_t* d_vflag,
                         gk_rowclass* rc) {
   GK_REQUIRE(ctx && tab && rc && d_rows && d_vflag && n_rows > 0 && n_rows <= 0x7FFFFFFFll, "bad row-class arguments");      // row numbers are int32
@@ -254,28 +247,23 @@ int gk_rowclass_enqueue(gk_ctx* ctx, gk_tab* tab, const int32_t* d_rows, int64_t
   const uint64_t hash_mask = bits >= 63 ? ~0ull : bits <= 0 ? 0ull : (1ull << bits) - 1ull;
   uint64_t n_slots = 64;
   while (n_slots < 2 * (uint64_t)n_rows) n_slots <<= 1;
-  auto take = [&](void** p, size_t bytes) {
-    if (gk_pool_malloc(ctx, p, bytes) != hipSuccess) return false;
-    rc->temps.push_back(*p);
-    return true;
-  };
+  GkBlocks temps(ctx);
   char* slots = nullptr;      // [n_slots] keys, then [n_slots] representatives: all bits set = empty / no row yet
-  uint32_t *slot_of = nullptr, *is_rep = nullptr, *rep_of = nullptr, *rank_of = nullptr;
-  int32_t* rep_idx = nullptr;
+  uint32_t *slot_of = nullptr, *is_rep = nullptr, *rep_of = nullptr, *rank_of = nullptr, *class_of = nullptr, *n_classes = nullptr;
+  int32_t *rep_idx = nullptr, *rep_rows = nullptr;
   const size_t per_row = (size_t)n_rows * sizeof(uint32_t);
-  if (!take((void**)&slots, (size_t)n_slots * 12) || !take((void**)&slot_of, per_row) || !take((void**)&is_rep, per_row) ||
-      !take((void**)&rep_of, per_row) || !take((void**)&rank_of, per_row) || !take((void**)&rep_idx, per_row) ||
-      !take((void**)&rc->rep_rows, per_row) || !take((void**)&rc->class_of, per_row)) {
-    gk_rowclass_free(ctx, rc);
+  if (temps.take(&slots, (size_t)n_slots * 12) != hipSuccess || temps.take(&slot_of, per_row) != hipSuccess ||
+      temps.take(&is_rep, per_row) != hipSuccess || temps.take(&rep_of, per_row) != hipSuccess ||
+      temps.take(&rank_of, per_row) != hipSuccess || temps.take(&rep_idx, per_row) != hipSuccess ||
+      temps.take(&rep_rows, per_row) != hipSuccess || temps.take(&class_of, per_row) != hipSuccess) {
     gk_set_error("out of device memory for the row classes");
     return GK_ERR_HIP;
   }
   unsigned long long* const slot_key = reinterpret_cast<unsigned long long*>(slots);
   uint32_t* const slot_rep = reinterpret_cast<uint32_t*>(slots + (size_t)n_slots * 8);
-  auto fail = [&](int code) { gk_rowclass_free(ctx, rc); return code; };
   if (hipMemsetAsync(slots, 0xFF, (size_t)n_slots * 12, st) != hipSuccess) {
     gk_set_error("row classes: clearing the slots failed");
-    return fail(GK_ERR_HIP);
+    return GK_ERR_HIP;
   }
   const unsigned groups = nblk(n_rows * kGroup);
   GK_PROF(ctx, "rowclass_keys", GK_KERNEL(rowclass_keys, dim3(groups), dim3(kThreads), 0, st, d_rows, n_rows, tab->d_off,
@@ -283,17 +271,19 @@ int gk_rowclass_enqueue(gk_ctx* ctx, gk_tab* tab, const int32_t* d_rows, int64_t
                                           slot_of));
   GK_PROF(ctx, "rowclass_verify", GK_KERNEL(rowclass_verify, dim3(groups), dim3(kThreads), 0, st, d_rows, n_rows,
                                             tab->d_off, tab->d_ids, d_vflag, slot_rep, slot_of, is_rep, rep_of));
-  int code = gk_compact_enqueue(ctx, is_rep, nullptr, n_rows, rep_idx, &rc->n_classes, rc->temps);
-  if (code) return fail(code);
+  const int code = gk_compact_enqueue(ctx, is_rep, nullptr, n_rows, rep_idx, &n_classes, temps);
+  if (code) return code;
   GK_PROF(ctx, "rowclass_rank", {
-    GK_KERNEL(rowclass_rank, dim3(nblk(n_rows)), dim3(kThreads), 0, st, rep_idx, rc->n_classes, n_rows, d_rows, rank_of,
-              rc->rep_rows);
-    GK_KERNEL(rowclass_classof, dim3(nblk(n_rows)), dim3(kThreads), 0, st, rep_of, rank_of, n_rows, rc->class_of);
+    GK_KERNEL(rowclass_rank, dim3(nblk(n_rows)), dim3(kThreads), 0, st, rep_idx, n_classes, n_rows, d_rows, rank_of,
+              rep_rows);
+    GK_KERNEL(rowclass_classof, dim3(nblk(n_rows)), dim3(kThreads), 0, st, rep_of, rank_of, n_rows, class_of);
   });
   if (hipGetLastError() != hipSuccess) {
     gk_set_error("row classes: a launch failed");
-    return fail(GK_ERR_HIP);
+    return GK_ERR_HIP;
   }
+  rc->rep_rows = rep_rows; rc->class_of = class_of; rc->n_classes = n_classes;
+  rc->blocks = std::move(temps);
   return GK_OK;
 }
 
@@ -320,9 +310,7 @@ extern "C" int gk_row_classes(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t 
     (void)hipMemcpyAsync(gk_ptr<void>(d_class_of), rc.class_of, (size_t)n_rows * sizeof(uint32_t), hipMemcpyDeviceToDevice,
                          ctx->stream);
   uint32_t n = 0;
-  const hipError_t e = gk_fetch(ctx, &n, rc.n_classes, sizeof(uint32_t));
-  gk_rowclass_free(ctx, &rc);
-  GK_HIP(e);
+  GK_HIP(gk_fetch(ctx, &n, rc.n_classes, sizeof(uint32_t)));
   *n_classes = n;
   return GK_OK;
 }

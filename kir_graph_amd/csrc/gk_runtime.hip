@@ -429,7 +429,15 @@ static size_t release_big(int device, size_t keep) {
   return given;
 }
 
+// gk_test_pool_fail: calls of gk_pool_malloc left until one fails (0: not armed) and the value it was armed with
+static std::atomic<int64_t> g_pool_fail_in{0};
+static int64_t g_pool_fail_armed = 0;
+
 hipError_t gk_pool_malloc(gk_ctx* ctx, void** out, size_t bytes) {
+  if (g_pool_fail_in.load(std::memory_order_relaxed) != 0 && g_pool_fail_in.fetch_sub(1, std::memory_order_relaxed) == 1) {
+    *out = nullptr;
+    return hipErrorOutOfMemory;
+  }
   const size_t cls = pool_class(bytes);
   static const bool trace = gk_trace("pool");      // dev: every large pool miss and what it costs
   const bool big = cls >= kBigBlock;
@@ -535,6 +543,21 @@ void gk_pool_free(gk_ctx* ctx, void* p) {
     over = dp.cached > pool_cache_limit();
   }
   if (over) release_big(ctx->device, pool_cache_limit());
+}
+
+extern "C" int gk_test_pool_fail(gk_ctx* ctx, int64_t nth, int64_t* live_out, int64_t* mallocs_out) {
+  GK_REQUIRE(nth >= 0, "gk_test_pool_fail: nth must not be negative");
+  const int64_t left = g_pool_fail_in.exchange(nth, std::memory_order_relaxed);
+  if (mallocs_out) *mallocs_out = g_pool_fail_armed - std::max<int64_t>(left, 0);
+  g_pool_fail_armed = nth;
+  if (live_out) {
+    *live_out = 0;
+    if (ctx) {
+      std::lock_guard<std::mutex> lock(ctx->pool_mutex);
+      *live_out = (int64_t)ctx->pool_live.size();
+    }
+  }
+  return GK_OK;
 }
 
 extern "C" int gk_device_memory(gk_ctx* ctx, int64_t* free_bytes, int64_t* total_bytes, int64_t* pool_cached_bytes) {

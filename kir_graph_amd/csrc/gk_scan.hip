@@ -1,5 +1,5 @@
 // Exclusive scan and stable compaction on the context stream (wave64 shuffles + LDS).
-#include "gk_common.h"
+#include "gk_blocks.h"
 
 namespace {
 
@@ -143,26 +143,23 @@ int gk_scan_u32(gk_ctx* ctx, uint32_t* d_data, int64_t n, uint32_t* d_total) {
   // scratch for tile sums of every level: tiles + tiles/kTile + ... <= tiles + tiles/1024 + 64
   int64_t tiles = (n + kTile - 1) / kTile;
   size_t need = (size_t)(tiles + tiles / 1024 + 4096) * sizeof(uint32_t);
+  GkBlocks temps(ctx);
   uint32_t* area = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&area, need));
-  const int rc = scan_rec(ctx, d_data, n, area, d_total);
-  gk_pool_free(ctx, area);   // stream-ordered reuse
-  return rc;
+  GK_HIP(temps.take(&area, need));
+  return scan_rec(ctx, d_data, n, area, d_total);
 }
 
 // The compaction queued on the stream, its total left on the device (*d_total_out points into a temporary): nothing is
-// waited for.  `temps` are the pool blocks to give back once the stream has passed the compaction (stream-ordered reuse:
-// at once is fine too, as gk_compact does).
+// waited for.  `temps` owns the scratch, the total's word included.
 int gk_compact_enqueue(gk_ctx* ctx, const uint32_t* d_flag, const int32_t* d_values, int64_t n, int32_t* d_out,
-                       uint32_t** d_total_out, std::vector<void*>& temps) {
+                       uint32_t** d_total_out, GkBlocks& temps) {
   gk_bind(ctx);
   *d_total_out = nullptr;
   if (n <= 0) return GK_OK;
   const int64_t blocks2 = (n + kCompactTile - 1) / kCompactTile;
   if (blocks2 <= kCompactMaxBlocks) {
     uint32_t* cnt = nullptr;
-    GK_HIP(gk_pool_malloc(ctx, (void**)&cnt, (size_t)(blocks2 + 1) * sizeof(uint32_t)));
-    temps.push_back(cnt);
+    GK_HIP(temps.take(&cnt, (size_t)(blocks2 + 1) * sizeof(uint32_t)));
     GK_PROF(ctx, "compact_count", GK_KERNEL(compact_count, dim3((unsigned)blocks2), dim3(kThreads), 0, ctx->stream,
                                              d_flag, n, cnt));
     GK_PROF(ctx, "compact_scatter", GK_KERNEL(compact_scatter, dim3((unsigned)blocks2), dim3(kThreads), 0, ctx->stream,
@@ -172,8 +169,7 @@ int gk_compact_enqueue(gk_ctx* ctx, const uint32_t* d_flag, const int32_t* d_val
     return GK_OK;
   }
   uint32_t* pos = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&pos, (size_t)(n + 1) * sizeof(uint32_t)));
-  temps.push_back(pos);
+  GK_HIP(temps.take(&pos, (size_t)(n + 1) * sizeof(uint32_t)));
   unsigned blocks = (unsigned)((n + kThreads - 1) / kThreads);
   GK_PROF(ctx, "flags_to_u32", GK_KERNEL(flags_to_u32, dim3(blocks), dim3(kThreads), 0, ctx->stream, d_flag, pos, n));
   int rc = gk_scan_u32(ctx, pos, n, pos + n);
@@ -190,15 +186,15 @@ int gk_compact(gk_ctx* ctx, const uint32_t* d_flag, const int32_t* d_values, int
     if (n_out) *n_out = 0;
     return GK_OK;
   }
-  std::vector<void*> temps;
+  GkBlocks temps(ctx);
   uint32_t* d_total = nullptr;
-  int rc = gk_compact_enqueue(ctx, d_flag, d_values, n, d_out, &d_total, temps);
+  const int rc = gk_compact_enqueue(ctx, d_flag, d_values, n, d_out, &d_total, temps);
+  if (rc) return rc;
   uint32_t total = 0;
-  if (rc == GK_OK && gk_fetch(ctx, &total, d_total, sizeof(uint32_t)) != hipSuccess) {
+  if (gk_fetch(ctx, &total, d_total, sizeof(uint32_t)) != hipSuccess) {
     gk_set_error("compaction: fetching the count failed");
-    rc = GK_ERR_HIP;
+    return GK_ERR_HIP;
   }
-  for (void* t : temps) gk_pool_free(ctx, t);
-  if (rc == GK_OK && n_out) *n_out = total;
-  return rc;
+  if (n_out) *n_out = total;
+  return GK_OK;
 }

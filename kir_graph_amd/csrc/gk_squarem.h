@@ -182,21 +182,4 @@ struct EmForms {
   }
 };
 
-// the device temporaries of one call, from the context's pool; done(rc) gives them all back and passes rc on
-struct PoolTemps {
-  gk_ctx* ctx;
-  std::vector<void*> held;
-  explicit PoolTemps(gk_ctx* c) : ctx(c) {}
-  hipError_t take(void** p, size_t bytes) {
-    hipError_t e = gk_pool_malloc(ctx, p, bytes ? bytes : 16);
-    if (e == hipSuccess) held.push_back(*p);
-    return e;
-  }
-  int done(int rc) {
-    for (void* p : held) gk_pool_free(ctx, p);
-    held.clear();
-    return rc;
-  }
-};
-
 }  // namespace

@@ -22,10 +22,11 @@
 // hash table keyed by the packed variant key, ranked by first appearance through a bitmap over
 // (mate, event) sequence numbers, so that the numbering equals the reference's sequential counter.
 #include <algorithm>
+#include <memory>
 #include <type_traits>
 #include <vector>
 
-#include "gk_common.h"
+#include "gk_blocks.h"
 
 namespace {
 
@@ -988,7 +989,7 @@ int gk_index_create(gk_ctx* ctx, const uint64_t* key, int32_t n_var, const int32
              "bad index arguments");
   GK_REQUIRE(gene_vbeg[0] == 0 && gene_vbeg[n_gene] == n_var, "gene_vbeg must cover the key table");
   for (int i = 1; i < n_var; ++i) GK_REQUIRE(key[i - 1] < key[i], "index keys must be strictly increasing");
-  gk_index* idx = new gk_index();
+  std::unique_ptr<gk_index, int (*)(gk_index*)> idx(new gk_index(), gk_index_destroy);
   idx->ctx = ctx; idx->n_var = n_var; idx->n_gene = n_gene;
   idx->gene_vbeg.assign(gene_vbeg, gene_vbeg + n_gene + 1);
   // 16-bp bucket table per gene: bucket b holds the first ordinal at or after (gene, 16 * b); one
@@ -1005,10 +1006,10 @@ int gk_index_create(gk_ctx* ctx, const uint64_t* key, int32_t n_var, const int32
       bucket.push_back((int32_t)(std::lower_bound(key, key + n_var, gk_make_key((uint32_t)g, (uint32_t)b << 4, 0, 0)) - key));
     boff[g + 1] = (int32_t)bucket.size();
   }
-  GK_HIP(gk_pool_malloc(ctx, (void**)&idx->d_key, (size_t)(n_var + 1) * sizeof(uint64_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&idx->d_gene_vbeg, (size_t)(n_gene + 1) * sizeof(int32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&idx->d_bucket, bucket.size() * sizeof(int32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&idx->d_gene_boff, boff.size() * sizeof(int32_t)));
+  GK_HIP(gk_take_into(ctx, &idx->d_key, (size_t)(n_var + 1) * sizeof(uint64_t)));
+  GK_HIP(gk_take_into(ctx, &idx->d_gene_vbeg, (size_t)(n_gene + 1) * sizeof(int32_t)));
+  GK_HIP(gk_take_into(ctx, &idx->d_bucket, bucket.size() * sizeof(int32_t)));
+  GK_HIP(gk_take_into(ctx, &idx->d_gene_boff, boff.size() * sizeof(int32_t)));
   GK_HIP(hipMemcpyAsync(idx->d_key, key, (size_t)n_var * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
   GK_HIP(hipMemcpyAsync(idx->d_gene_vbeg, gene_vbeg, (size_t)(n_gene + 1) * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   GK_HIP(hipMemcpyAsync(idx->d_bucket, bucket.data(), bucket.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -1038,21 +1039,21 @@ int gk_index_create(gk_ctx* ctx, const uint64_t* key, int32_t n_var, const int32
     lb_t.push_back(v1);
     for (int q = 0; q < 4; ++q) snp_ord.push_back(-1);
   }
-  GK_HIP(gk_pool_malloc(ctx, (void**)&idx->d_snp_ord, snp_ord.size() * sizeof(int32_t)));
+  GK_HIP(gk_take_into(ctx, &idx->d_snp_ord, snp_ord.size() * sizeof(int32_t)));
   GK_HIP(hipMemcpyAsync(idx->d_snp_ord, snp_ord.data(), snp_ord.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&idx->d_lb_a, lb_a.size() * sizeof(int32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&idx->d_lb_t, lb_t.size() * sizeof(int32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&idx->d_gene_pbase, pbase.size() * sizeof(int32_t)));
+  GK_HIP(gk_take_into(ctx, &idx->d_lb_a, lb_a.size() * sizeof(int32_t)));
+  GK_HIP(gk_take_into(ctx, &idx->d_lb_t, lb_t.size() * sizeof(int32_t)));
+  GK_HIP(gk_take_into(ctx, &idx->d_gene_pbase, pbase.size() * sizeof(int32_t)));
   GK_HIP(hipMemcpyAsync(idx->d_lb_a, lb_a.data(), lb_a.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   GK_HIP(hipMemcpyAsync(idx->d_lb_t, lb_t.data(), lb_t.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   GK_HIP(hipMemcpyAsync(idx->d_gene_pbase, pbase.data(), pbase.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   std::vector<uint32_t> del_bits((size_t)(n_var + 31) / 32 + 2, 0u);
   for (int32_t v = 0; v < n_var; ++v)
     if (gk_key_typ(key[v]) == GK_TYP_DEL) del_bits[(size_t)v >> 5] |= 1u << (v & 31);
-  GK_HIP(gk_pool_malloc(ctx, (void**)&idx->d_del_bits, del_bits.size() * sizeof(uint32_t)));
+  GK_HIP(gk_take_into(ctx, &idx->d_del_bits, del_bits.size() * sizeof(uint32_t)));
   GK_HIP(hipMemcpyAsync(idx->d_del_bits, del_bits.data(), del_bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
   GK_HIP(hipStreamSynchronize(ctx->stream));
-  *out = idx;
+  *out = idx.release();
   return GK_OK;
 }
 
@@ -1144,16 +1145,17 @@ static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, gk
   const uint32_t* c_words = c_off ? c_off + n_mates + 1 : nullptr;
   GK_REQUIRE(n_mates == 0 || mates || c_off, "no records");
   hipStream_t st = ctx->stream;
-  gk_tab* tab = new gk_tab();
+  std::unique_ptr<gk_tab, int (*)(gk_tab*)> tab(new gk_tab(), gk_tab_destroy);
+  GkBlocks temps(ctx);      // the scratch of the call; what the tabulation keeps is taken into `tab`
   tab->ctx = ctx; tab->idx = idx; tab->n_pairs = n_pairs; tab->n_var = idx->n_var;
 
   // novel hash table of 2^log2cap slots, load factor <= 0.5 (checked below)
   NovelTable nt;
   const size_t cap = 1ull << log2cap;
   nt.mask = (uint32_t)(cap - 1);
-  GK_HIP(gk_pool_malloc(ctx, (void**)&nt.keys, cap * sizeof(uint64_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&nt.seq, cap * sizeof(uint64_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&nt.rank, cap * sizeof(uint32_t)));
+  GK_HIP(temps.take(&nt.keys, cap * sizeof(uint64_t)));
+  GK_HIP(temps.take(&nt.seq, cap * sizeof(uint64_t)));
+  GK_HIP(temps.take(&nt.rank, cap * sizeof(uint32_t)));
   GK_HIP(hipMemsetAsync(nt.keys, 0xFF, cap * sizeof(uint64_t), st));
   GK_HIP(hipMemsetAsync(nt.seq, 0xFF, cap * sizeof(uint64_t), st));
 
@@ -1162,14 +1164,14 @@ static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, gk
   int* d_err = nullptr;
   // what pass 1 saves for pass 2: per mate 16 dense bytes of event words, 16 of kept bits, the window's first ordinal, and
   // overflow rows that a mate with more than four events / a window beyond 128 candidates writes
-  GK_HIP(gk_pool_malloc(ctx, (void**)&ev_save, (size_t)(n_mates + 1) * sizeof(uint4)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&ev_more, (size_t)(n_mates + 1) * kEvMore * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&lo_save, (size_t)(n_mates + 1) * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&mask_save, (size_t)(n_mates + 1) * sizeof(uint4)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&mask_more, (size_t)(n_mates + 1) * (kMaskWords - kMaskRegs) * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&cnt, (size_t)(4 * n_pairs + 2) * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&valid, (size_t)(n_pairs + 1) * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&d_err, sizeof(int)));
+  GK_HIP(temps.take(&ev_save, (size_t)(n_mates + 1) * sizeof(uint4)));
+  GK_HIP(temps.take(&ev_more, (size_t)(n_mates + 1) * kEvMore * sizeof(uint32_t)));
+  GK_HIP(temps.take(&lo_save, (size_t)(n_mates + 1) * sizeof(uint32_t)));
+  GK_HIP(temps.take(&mask_save, (size_t)(n_mates + 1) * sizeof(uint4)));
+  GK_HIP(temps.take(&mask_more, (size_t)(n_mates + 1) * (kMaskWords - kMaskRegs) * sizeof(uint32_t)));
+  GK_HIP(temps.take(&cnt, (size_t)(4 * n_pairs + 2) * sizeof(uint32_t)));
+  GK_HIP(temps.take(&valid, (size_t)(n_pairs + 1) * sizeof(uint32_t)));
+  GK_HIP(temps.take(&d_err, sizeof(int)));
   GK_HIP(hipMemsetAsync(d_err, 0, sizeof(int), st));
   nt.flags = d_err;
 
@@ -1187,9 +1189,9 @@ static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, gk
   int64_t* d_spill_pair = nullptr;
   uint32_t* wide_ev = nullptr;
   if (n_spill) {   // the wide pairs overwrite the zeros the kernel above left for them
-    GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_wide, (size_t)(2 * n_spill) * sizeof(gk_mate_wide)));
-    GK_HIP(gk_pool_malloc(ctx, (void**)&d_spill_pair, (size_t)n_spill * sizeof(int64_t)));
-    GK_HIP(gk_pool_malloc(ctx, (void**)&wide_ev, (size_t)(2 * n_spill) * GK_WIDE_EVENTS * sizeof(uint32_t)));
+    GK_HIP(gk_take_into(ctx, &tab->d_wide, (size_t)(2 * n_spill) * sizeof(gk_mate_wide)));
+    GK_HIP(temps.take(&d_spill_pair, (size_t)n_spill * sizeof(int64_t)));
+    GK_HIP(temps.take(&wide_ev, (size_t)(2 * n_spill) * GK_WIDE_EVENTS * sizeof(uint32_t)));
     GK_HIP(hipMemcpyAsync(tab->d_wide, wide, (size_t)(2 * n_spill) * sizeof(gk_mate_wide), hipMemcpyHostToDevice, st));
     GK_HIP(hipMemcpyAsync(d_spill_pair, spill_pair, (size_t)n_spill * sizeof(int64_t), hipMemcpyHostToDevice, st));
     GK_HIP(hipStreamSynchronize(st));   // the caller's arrays are free again
@@ -1204,9 +1206,9 @@ static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, gk
   // novel ranks: event bits per mate (bitmap) + per wide mate (wide_bits), per-mate counts scanned into `prefix`
   const int64_t n_words = n_mates + 1;
   uint32_t *bitmap = nullptr, *prefix = nullptr, *wide_bits = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&bitmap, (size_t)n_words * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&prefix, (size_t)(n_words + 1) * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&wide_bits, (size_t)(2 * n_spill + 1) * kWideWords * sizeof(uint32_t)));
+  GK_HIP(temps.take(&bitmap, (size_t)n_words * sizeof(uint32_t)));
+  GK_HIP(temps.take(&prefix, (size_t)(n_words + 1) * sizeof(uint32_t)));
+  GK_HIP(temps.take(&wide_bits, (size_t)(2 * n_spill + 1) * kWideWords * sizeof(uint32_t)));
   GK_HIP(hipMemsetAsync(bitmap, 0, (size_t)n_words * sizeof(uint32_t), st));
   GK_HIP(hipMemsetAsync(wide_bits, 0, (size_t)(2 * n_spill + 1) * kWideWords * sizeof(uint32_t), st));
   GK_PROF(ctx, "novel_mark", GK_KERNEL(novel_mark, dim3(nblk((int64_t)cap)), dim3(kThreads), 0, st, nt, bitmap, wide_bits,
@@ -1219,10 +1221,13 @@ static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, gk
 
   uint32_t totals[2] = {0, 0};
   int err = 0;
-  GK_HIP(gk_fetch_queue(ctx, &totals[0], cnt + 4 * n_pairs, sizeof(uint32_t)));
-  GK_HIP(gk_fetch_queue(ctx, &totals[1], prefix + n_words, sizeof(uint32_t)));
-  GK_HIP(gk_fetch_queue(ctx, &err, d_err, sizeof(int)));
-  GK_HIP(gk_fetch_wait(ctx));
+  if (gk_fetch_queue(ctx, &totals[0], cnt + 4 * n_pairs, sizeof(uint32_t)) != hipSuccess ||
+      gk_fetch_queue(ctx, &totals[1], prefix + n_words, sizeof(uint32_t)) != hipSuccess ||
+      gk_fetch_queue(ctx, &err, d_err, sizeof(int)) != hipSuccess || gk_fetch_wait(ctx) != hipSuccess) {
+    gk_fetch_cancel(ctx);      // `totals` and `err` go away
+    gk_set_error("tabulation: fetching the totals failed: %s", hipGetErrorString(hipGetLastError()));
+    return GK_ERR_HIP;
+  }
   tab->n_ids = totals[0];
   tab->n_novel = (int32_t)totals[1];
   tab->err_flags = err & 3;   // bit 2 (a window beyond the saved bits) only selects the pass-2 kernel
@@ -1230,19 +1235,14 @@ static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, gk
     gk_set_error("novel variant table overflow (%d novel variants in %llu slots)", tab->n_novel, (unsigned long long)cap);
     *table_too_small = true;
     GK_HIP(hipStreamSynchronize(st));
-    gk_pool_free(ctx,cnt); gk_pool_free(ctx,valid); gk_pool_free(ctx,d_err); gk_pool_free(ctx,bitmap); gk_pool_free(ctx,prefix); gk_pool_free(ctx,wide_bits);
-    gk_pool_free(ctx,ev_save); gk_pool_free(ctx,lo_save); gk_pool_free(ctx,mask_save); gk_pool_free(ctx,ev_more); gk_pool_free(ctx,mask_more);
-    gk_pool_free(ctx,d_spill_pair); gk_pool_free(ctx,wide_ev);
-    gk_pool_free(ctx,nt.keys); gk_pool_free(ctx,nt.seq); gk_pool_free(ctx,nt.rank);
-    gk_tab_destroy(tab);
     return GK_ERR_CAPACITY;
   }
 
-  GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_novel_key, (size_t)(tab->n_novel + 1) * sizeof(uint64_t)));
+  GK_HIP(gk_take_into(ctx, &tab->d_novel_key, (size_t)(tab->n_novel + 1) * sizeof(uint64_t)));
   GK_PROF(ctx, "novel_assign", GK_KERNEL(novel_assign, dim3(nblk((int64_t)cap)), dim3(kThreads), 0, st, nt, bitmap, wide_bits,
                      d_spill_pair, n_spill, prefix, tab->d_novel_key));
 
-  GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_ids, (size_t)(tab->n_ids + 1) * sizeof(uint32_t)));
+  GK_HIP(gk_take_into(ctx, &tab->d_ids, (size_t)(tab->n_ids + 1) * sizeof(uint32_t)));
   gk_mate* expanded = nullptr;
   if (n_mates) {
     // pass 2: from what pass 1 saved; the second walk only when some window did not fit the saved bits
@@ -1250,7 +1250,7 @@ static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, gk
     if ((err & 4) || two_walks) {
       const gk_mate* records = mates;
       if (!records) {      // rare: the second walk reads 128-byte records, expanded here for the length of this call
-        GK_HIP(gk_pool_malloc(ctx, (void**)&expanded, (size_t)n_mates * sizeof(gk_mate)));
+        GK_HIP(temps.take(&expanded, (size_t)n_mates * sizeof(gk_mate)));
         GK_KERNEL(mates_unpack_words, dim3(nblk(n_mates)), dim3(kThreads), 0, st, c_off, c_words, n_mates, expanded);
         records = expanded;
       }
@@ -1267,27 +1267,22 @@ static int tabulate_with_table(gk_ctx* ctx, gk_index* idx, gk_dptr d_mates_p, gk
                 cnt, valid, tab->d_ids, wide_ev);
   }
   // compact valid pairs (order preserving)
-  GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_pair_src, (size_t)(n_pairs + 1) * sizeof(int32_t)));
+  GK_HIP(gk_take_into(ctx, &tab->d_pair_src, (size_t)(n_pairs + 1) * sizeof(int32_t)));
   rc = gk_compact(ctx, valid, nullptr, n_pairs, tab->d_pair_src, &tab->n_valid);
   if (rc) return rc;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_off, (size_t)(4 * tab->n_valid + 1) * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_pair_gene, (size_t)tab->n_valid + 1));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_pair_nh, (size_t)tab->n_valid + 1));
+  GK_HIP(gk_take_into(ctx, &tab->d_off, (size_t)(4 * tab->n_valid + 1) * sizeof(uint32_t)));
+  GK_HIP(gk_take_into(ctx, &tab->d_pair_gene, (size_t)tab->n_valid + 1));
+  GK_HIP(gk_take_into(ctx, &tab->d_pair_nh, (size_t)tab->n_valid + 1));
   GK_PROF(ctx, "gather_pairs", GK_KERNEL(gather_pairs, dim3(nblk(tab->n_valid + 1)), dim3(kThreads), 0, st, mates, c_off, c_words,
                      tab->d_pair_src, tab->n_valid, cnt, tab->d_off, tab->d_pair_gene, tab->d_pair_nh, (uint32_t)tab->n_ids));
   GK_HIP(hipGetLastError());
   GK_HIP(hipStreamSynchronize(st));
-  gk_pool_free(ctx,cnt); gk_pool_free(ctx,valid); gk_pool_free(ctx,d_err); gk_pool_free(ctx,bitmap); gk_pool_free(ctx,prefix); gk_pool_free(ctx,wide_bits);
-  gk_pool_free(ctx,ev_save); gk_pool_free(ctx,lo_save); gk_pool_free(ctx,mask_save); gk_pool_free(ctx,ev_more); gk_pool_free(ctx,mask_more);
-  gk_pool_free(ctx,d_spill_pair); gk_pool_free(ctx,wide_ev); gk_pool_free(ctx,expanded);
-  gk_pool_free(ctx,nt.keys); gk_pool_free(ctx,nt.seq); gk_pool_free(ctx,nt.rank);
   if (err & 2) {
     gk_set_error("a filter-passing mate carries more variant events than its record format allows (%d, wide %d)", kMaxEv,
                  GK_WIDE_EVENTS);
-    gk_tab_destroy(tab);
     return GK_ERR_CAPACITY;
   }
-  *out = tab;
+  *out = tab.release();
   return GK_OK;
 }
 
@@ -1298,14 +1293,14 @@ int gk_tab_from_csr(gk_ctx* ctx, int32_t n_var_total, int64_t n_valid, const uin
   const int64_t n_ids = off[4 * n_valid];
   for (int64_t i = 0; i < 4 * n_valid; ++i) GK_REQUIRE(off[i] <= off[i + 1], "CSR offsets must be non-decreasing");
   for (int64_t i = 0; i < n_ids; ++i) GK_REQUIRE(ids[i] < (uint32_t)n_var_total, "variant ordinal out of range");
-  gk_tab* tab = new gk_tab();
+  std::unique_ptr<gk_tab, int (*)(gk_tab*)> tab(new gk_tab(), gk_tab_destroy);
   tab->ctx = ctx; tab->n_pairs = n_valid; tab->n_valid = n_valid; tab->n_ids = n_ids;
   tab->n_var = n_var_total; tab->n_novel = 0;
   hipStream_t st = ctx->stream;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_off, (size_t)(4 * n_valid + 1) * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_ids, (size_t)(n_ids + 1) * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_pair_gene, (size_t)n_valid + 1));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&tab->d_pair_nh, (size_t)n_valid + 1));
+  GK_HIP(gk_take_into(ctx, &tab->d_off, (size_t)(4 * n_valid + 1) * sizeof(uint32_t)));
+  GK_HIP(gk_take_into(ctx, &tab->d_ids, (size_t)(n_ids + 1) * sizeof(uint32_t)));
+  GK_HIP(gk_take_into(ctx, &tab->d_pair_gene, (size_t)n_valid + 1));
+  GK_HIP(gk_take_into(ctx, &tab->d_pair_nh, (size_t)n_valid + 1));
   GK_HIP(hipMemcpyAsync(tab->d_off, off, (size_t)(4 * n_valid + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   if (n_ids) GK_HIP(hipMemcpyAsync(tab->d_ids, ids, (size_t)n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   if (n_valid) {
@@ -1313,7 +1308,7 @@ int gk_tab_from_csr(gk_ctx* ctx, int32_t n_var_total, int64_t n_valid, const uin
     GK_HIP(hipMemcpyAsync(tab->d_pair_nh, pair_nh, (size_t)n_valid, hipMemcpyHostToDevice, st));
   }
   GK_HIP(hipStreamSynchronize(st));
-  *out = tab;
+  *out = tab.release();
   return GK_OK;
 }
 
@@ -1355,19 +1350,20 @@ int gk_mates_compact(gk_ctx* ctx, gk_dptr d_mates, int64_t n_mates, gk_dptr* d_c
   GK_REQUIRE(n_mates < (1ll << 27), "more than 2^26 pairs per call");
   hipStream_t st = ctx->stream;
   const gk_mate* mates = gk_ptr<const gk_mate>(d_mates);
+  GkBlocks temps(ctx);
   uint32_t* cnt = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&cnt, (size_t)(n_mates + 2) * sizeof(uint32_t)));
+  GK_HIP(temps.take(&cnt, (size_t)(n_mates + 2) * sizeof(uint32_t)));
   if (n_mates) GK_KERNEL(mates_count_words, dim3(nblk(n_mates)), dim3(kThreads), 0, st, mates, n_mates, cnt);
   int rc = gk_scan_u32(ctx, cnt, n_mates, cnt + n_mates);
-  if (rc) { gk_pool_free(ctx, cnt); return rc; }
+  if (rc) return rc;
   uint32_t total = 0;
   GK_HIP(gk_fetch(ctx, &total, cnt + n_mates, sizeof(uint32_t)));
   const size_t bytes = ((size_t)(n_mates + 1) + (size_t)total) * sizeof(uint32_t);
   uint32_t* out = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&out, bytes));
+  GK_HIP(temps.take(&out, bytes));
   GK_KERNEL(mates_pack_words, dim3(nblk(n_mates + 1)), dim3(kThreads), 0, st, mates, n_mates, cnt, out, out + n_mates + 1, total);
   GK_HIP(hipGetLastError());
-  gk_pool_free(ctx, cnt);      // stream-ordered reuse
+  temps.keep(out);      // the caller's from here (gk_free)
   *d_compact_out = gk_addr(out);
   *bytes_out = (int64_t)bytes;
   return GK_OK;

@@ -16,7 +16,7 @@
 // the scalar cache's miss path: DESIGN.md section 8, profiles/r03_compat_variants.txt.)
 #include <algorithm>
 
-#include "gk_common.h"
+#include "gk_blocks.h"
 #include "gk_lut.h"
 #include "gk_rowclass.h"
 
@@ -719,13 +719,13 @@ int launch_compat(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_d
                   uint16_t* lidx = nullptr, const int32_t* table_cols = nullptr, int n_table_cols = 0) {
   const double empty_p = keep_empty ? 0.999 : 1.0;
   const int words_in = words;
+  GkBlocks temps(ctx);
   int32_t* d_cols = nullptr;
   if (n_table_cols > 0) {      // the kernel sees a gene of the listed alleles
     n_allele = n_table_cols;
     words = (n_table_cols + 31) / 32;
-    GK_HIP(gk_pool_malloc(ctx, (void**)&d_cols, (size_t)n_table_cols * sizeof(int32_t)));
+    GK_HIP(temps.take(&d_cols, (size_t)n_table_cols * sizeof(int32_t)));
     if (gk_send(ctx, d_cols, table_cols, (size_t)n_table_cols * sizeof(int32_t)) != hipSuccess) {
-      gk_pool_free(ctx, d_cols);
       gk_set_error("compatibility table: sending the column list failed: %s", hipGetErrorString(hipGetLastError()));
       return GK_ERR_HIP;
     }
@@ -734,8 +734,7 @@ int launch_compat(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_d
   const dim3 grid((unsigned)(want < 2048 ? (want < 8 ? 8 : want) : 2048)), block(kCompatThreads);
   const int64_t n_mask = (int64_t)(vend - vbeg) * words;
   uint32_t* mask_t = nullptr;
-  if (gk_pool_malloc(ctx, (void**)&mask_t, (size_t)std::max<int64_t>(n_mask, 1) * sizeof(uint32_t)) != hipSuccess) {
-    gk_pool_free(ctx, d_cols);
+  if (temps.take(&mask_t, (size_t)std::max<int64_t>(n_mask, 1) * sizeof(uint32_t)) != hipSuccess) {
     gk_set_error("out of device memory for the transposed bit matrix");
     return GK_ERR_HIP;
   }
@@ -764,16 +763,11 @@ int launch_compat(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_d
   const bool by_class = kLog && out && miss8 && bound_flags && !lidx && use_row_classes(n_rows, n_allele);
   if (by_class) {
     const int64_t ldc = gk_rowclass_ld(n_allele);
-    int rc = gk_rowclass_enqueue(ctx, tab, k_rows, n_rows, gk_ptr<uint8_t>(d_vflag), &classes);
-    if (rc == GK_OK && gk_pool_malloc(ctx, (void**)&Lc, (size_t)n_rows * ldc * sizeof(double)) != hipSuccess) {
+    const int rc = gk_rowclass_enqueue(ctx, tab, k_rows, n_rows, gk_ptr<uint8_t>(d_vflag), &classes);
+    if (rc) return rc;
+    if (temps.take(&Lc, (size_t)n_rows * ldc * sizeof(double)) != hipSuccess) {
       gk_set_error("out of device memory for the compact compatibility table");
-      rc = GK_ERR_HIP;
-    }
-    if (rc) {
-      gk_rowclass_free(ctx, &classes);
-      gk_pool_free(ctx, mask_t);
-      gk_pool_free(ctx, d_cols);
-      return rc;
+      return GK_ERR_HIP;
     }
     k_rows = classes.rep_rows; k_n_dev = classes.n_classes;
     k_out = Lc; k_ld = ldc;
@@ -798,15 +792,10 @@ int launch_compat(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_d
 #undef GK_COMPAT_LAUNCH
 #undef GK_COMPAT_GO
   }
-  int rc_expand = GK_OK;
   if (by_class) {
-    rc_expand = gk_rowclass_expand(ctx, &classes, Lc, k_ld, n_allele, n_rows, out, miss8, ldm);
-    gk_rowclass_free(ctx, &classes);
-    gk_pool_free(ctx, Lc);
+    const int rc = gk_rowclass_expand(ctx, &classes, Lc, k_ld, n_allele, n_rows, out, miss8, ldm);
+    if (rc) return rc;
   }
-  gk_pool_free(ctx, mask_t);   // stream-ordered reuse: the next user of the block runs after these launches
-  gk_pool_free(ctx, d_cols);
-  if (rc_expand) return rc_expand;
   GK_HIP(hipGetLastError());
   return GK_OK;
 }
@@ -821,11 +810,12 @@ static int build_partition(gk_ctx* ctx, gk_tab* tab, int multiple) {
   const int n_bins = tab->idx ? tab->idx->n_gene : 256;
   const int64_t n_tiles = (n + 63) / 64;
   const size_t n_hist = (size_t)n_bins * n_tiles;
+  GkBlocks temps(ctx);
   uint32_t *hist = nullptr, *goff = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&hist, (n_hist + 1) * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&goff, (size_t)(n_bins + 1) * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&part.d_rows, (size_t)(n + 1) * sizeof(int32_t)));
-  part.owner = ctx;
+  int32_t* d_rows = nullptr;      // the partition's once the offsets have arrived
+  GK_HIP(temps.take(&hist, (n_hist + 1) * sizeof(uint32_t)));
+  GK_HIP(temps.take(&goff, (size_t)(n_bins + 1) * sizeof(uint32_t)));
+  GK_HIP(temps.take(&d_rows, (size_t)(n + 1) * sizeof(int32_t)));
   GK_HIP(hipMemsetAsync(hist, 0, n_hist * sizeof(uint32_t), ctx->stream));
   GK_PROF(ctx, "part_pass", GK_KERNEL(part_pass<false>, dim3(nblk(n)), dim3(kThreads), 0, ctx->stream,
                                                tab->d_pair_gene, tab->d_pair_nh, n, multiple, n_bins, n_tiles, hist,
@@ -834,15 +824,20 @@ static int build_partition(gk_ctx* ctx, gk_tab* tab, int multiple) {
   if (rc) return rc;
   GK_PROF(ctx, "part_pass", GK_KERNEL(part_pass<true>, dim3(nblk(n)), dim3(kThreads), 0, ctx->stream,
                                                tab->d_pair_gene, tab->d_pair_nh, n, multiple, n_bins, n_tiles, hist,
-                                               part.d_rows));
+                                               d_rows));
   GK_KERNEL(part_offsets, dim3((unsigned)(n_bins / 256 + 1)), dim3(256), 0, ctx->stream, hist, hist + n_hist,
                      n_bins, n_tiles, goff);
   GK_HIP(hipGetLastError());
   std::vector<uint32_t> host((size_t)n_bins + 1);
-  GK_HIP(gk_fetch(ctx, host.data(), goff, host.size() * sizeof(uint32_t)));
+  if (gk_fetch(ctx, host.data(), goff, host.size() * sizeof(uint32_t)) != hipSuccess) {
+    gk_fetch_cancel(ctx);      // `host` goes away
+    gk_set_error("row partition: fetching the offsets failed: %s", hipGetErrorString(hipGetLastError()));
+    return GK_ERR_HIP;
+  }
   part.gene_off.assign(host.begin(), host.end());
-  gk_pool_free(ctx, hist);
-  gk_pool_free(ctx, goff);
+  part.owner = ctx;
+  part.d_rows = d_rows;
+  temps.keep(d_rows);
   return GK_OK;
 }
 
@@ -875,13 +870,12 @@ int gk_select_nonempty(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows,
   gk_bind(ctx);
   GK_REQUIRE(ctx && tab && n_out, "null pointer");
   if (n_rows == 0) { *n_out = 0; return GK_OK; }
+  GkBlocks temps(ctx);
   uint32_t* flag = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&flag, (size_t)n_rows * sizeof(uint32_t)));
+  GK_HIP(temps.take(&flag, (size_t)n_rows * sizeof(uint32_t)));
   GK_PROF(ctx, "flag_nonempty", GK_KERNEL(flag_nonempty, dim3(nblk(n_rows)), dim3(kThreads), 0, ctx->stream, gk_ptr<int32_t>(d_rows),
                      n_rows, tab->d_off, tab->d_ids, gk_ptr<uint8_t>(d_vflag), flag, (uint32_t*)nullptr, 0));
-  int rc = gk_compact(ctx, flag, gk_ptr<int32_t>(d_rows), n_rows, gk_ptr<int32_t>(d_rows_out), n_out);
-  gk_pool_free(ctx,flag);
-  return rc;
+  return gk_compact(ctx, flag, gk_ptr<int32_t>(d_rows), n_rows, gk_ptr<int32_t>(d_rows_out), n_out);
 }
 
 int gk_variant_count_range(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag, gk_dptr d_cnt,
@@ -977,30 +971,33 @@ static int variant_surviving(gk_ctx* ctx, gk_tab* tab, gk_dptr d_cnt, gk_dptr d_
   uint32_t* cnt = gk_ptr<uint32_t>(d_cnt);
   uint32_t *flag = nullptr, *vals = nullptr;
   int32_t* ord = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&flag, (size_t)nv * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&ord, (size_t)nv * sizeof(int32_t)));
+  GkBlocks temps(ctx);
+  GK_HIP(temps.take(&flag, (size_t)nv * sizeof(uint32_t)));
+  GK_HIP(temps.take(&ord, (size_t)nv * sizeof(int32_t)));
   GK_KERNEL(flag_surviving, dim3(nblk(nv)), dim3(kThreads), 0, ctx->stream, cnt, cnt + nv,
                      gk_ptr<uint8_t>(d_vflag), nv, flag, gene, vbeg, vend, tab->n_var, tab->d_novel_key);
   int64_t n = 0;
-  int rc = gk_compact(ctx, flag, nullptr, nv, ord, &n);
-  if (rc == GK_OK && n > max_out) {
+  const int rc = gk_compact(ctx, flag, nullptr, nv, ord, &n);
+  if (rc) return rc;
+  if (n > max_out) {
     gk_set_error("surviving-variant buffer too small (%lld > %lld)", (long long)n, (long long)max_out);
-    rc = GK_ERR_CAPACITY;
+    return GK_ERR_CAPACITY;
   }
-  if (rc == GK_OK && n) {
-    GK_HIP(gk_pool_malloc(ctx, (void**)&vals, (size_t)(2 * n) * sizeof(uint32_t)));
+  if (n) {
+    GK_HIP(temps.take(&vals, (size_t)(2 * n) * sizeof(uint32_t)));
     GK_KERNEL(gather_surviving, dim3(nblk(n)), dim3(kThreads), 0, ctx->stream, ord, n, cnt, cnt + nv,
                        gk_ptr<uint8_t>(d_vflag), vals);
-    GK_HIP(gk_fetch_queue(ctx, ord_out, ord, (size_t)n * sizeof(int32_t)));
-    GK_HIP(gk_fetch_queue(ctx, pos_out, vals, (size_t)n * sizeof(uint32_t)));
-    GK_HIP(gk_fetch_queue(ctx, neg_out, vals + n, (size_t)n * sizeof(uint32_t)));
-    GK_HIP(gk_fetch_wait(ctx));
-    gk_pool_free(ctx, vals);
+    if (gk_fetch_queue(ctx, ord_out, ord, (size_t)n * sizeof(int32_t)) != hipSuccess ||
+        gk_fetch_queue(ctx, pos_out, vals, (size_t)n * sizeof(uint32_t)) != hipSuccess ||
+        gk_fetch_queue(ctx, neg_out, vals + n, (size_t)n * sizeof(uint32_t)) != hipSuccess ||
+        gk_fetch_wait(ctx) != hipSuccess) {
+      gk_fetch_cancel(ctx);      // the caller's arrays may go away
+      gk_set_error("surviving variants: %s", hipGetErrorString(hipGetLastError()));
+      return GK_ERR_HIP;
+    }
   }
-  gk_pool_free(ctx, flag);
-  gk_pool_free(ctx, ord);
-  if (rc == GK_OK) *n_out = n;
-  return rc;
+  *n_out = n;
+  return GK_OK;
 }
 
 int gk_variant_surviving(gk_ctx* ctx, gk_tab* tab, gk_dptr d_cnt, gk_dptr d_vflag, int64_t max_out, int32_t* ord_out,
@@ -1129,6 +1126,7 @@ static int sample_prepare(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d_
   }
   const int max_local = std::min(max_span, 60 * 1024 / 8);   // LDS budget per workgroup
   const size_t n_wg = wg_gene.size();
+  GkBlocks temps(ctx);
   char* d_tab = nullptr;
   const size_t o_row0 = (n_wg * sizeof(int32_t) + 15) / 16 * 16, o_row1 = o_row0 + n_wg * sizeof(int64_t),
                o_goff = o_row1 + n_wg * sizeof(int64_t), tab_bytes = o_goff + (size_t)(n_gene + 1) * sizeof(int64_t);
@@ -1138,15 +1136,15 @@ static int sample_prepare(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d_
     memcpy(packed.data() + o_row0, wg_row0.data(), n_wg * sizeof(int64_t));
     memcpy(packed.data() + o_row1, wg_row1.data(), n_wg * sizeof(int64_t));
     memcpy(packed.data() + o_goff, goff.data(), (size_t)(n_gene + 1) * sizeof(int64_t));
-    GK_HIP(gk_pool_malloc(ctx, (void**)&d_tab, tab_bytes));
+    GK_HIP(temps.take(&d_tab, tab_bytes));
     GK_HIP(gk_send(ctx, d_tab, packed.data(), tab_bytes));
   }
   uint32_t* cnt = gk_ptr<uint32_t>(d_cnt);
   uint8_t* vflag = gk_ptr<uint8_t>(d_vflag);
   // per pair: did the last tally count any of its ids / does one survive the correction (flag_pairs)
   uint8_t *maybe = nullptr, *alive = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&maybe, (size_t)tab->n_valid));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&alive, (size_t)tab->n_valid));
+  GK_HIP(temps.take(&maybe, (size_t)tab->n_valid));
+  GK_HIP(temps.take(&alive, (size_t)tab->n_valid));
   GK_HIP(hipMemsetAsync(maybe, 0, (size_t)tab->n_valid, st));      // pairs outside the partition: never asked for
   for (int round = 0; round < rounds; ++round) {      // the exon model corrects its lists twice (typing_mulit_allele.py:644-645, 664)
     if (round) GK_HIP(hipMemsetAsync(cnt, 0, (size_t)(2 * nv) * sizeof(uint32_t), st));
@@ -1164,8 +1162,8 @@ static int sample_prepare(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d_
   }
   // rows with a surviving id, compacted in place of the grouping (stable: the groups stay contiguous and ordered)
   uint32_t *flag = nullptr, *kept = nullptr;
-  GK_HIP(gk_pool_malloc(ctx, (void**)&flag, (size_t)n_rows * sizeof(uint32_t)));
-  GK_HIP(gk_pool_malloc(ctx, (void**)&kept, (size_t)n_gene * sizeof(uint32_t)));
+  GK_HIP(temps.take(&flag, (size_t)n_rows * sizeof(uint32_t)));
+  GK_HIP(temps.take(&kept, (size_t)n_gene * sizeof(uint32_t)));
   GK_PROF(ctx, "flag_pairs", GK_KERNEL(flag_pairs, dim3(nblk(4 * (int64_t)tab->n_valid)), dim3(kThreads), 0, st, (int64_t)tab->n_valid,
                                    tab->d_off, tab->d_ids, vflag, maybe, alive));
   GK_PROF(ctx, "gather_pair_flags", GK_KERNEL(gather_pair_flags, dim3(nblk(std::max<int64_t>(n_rows, n_gene))), dim3(kThreads), 0, st,
@@ -1175,14 +1173,9 @@ static int sample_prepare(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d_
   GK_HIP(hipGetLastError());
   // everything below is queued, then ONE wait: the compaction of the rows, the rows kept per gene, and -- when asked for --
   // the surviving tallies of every variant and the novel keys
-  std::vector<void*> temps{flag, kept, d_tab, alive, maybe};
-  auto done = [&](int code) {
-    for (void* t : temps) gk_pool_free(ctx, t);
-    return code;
-  };
   uint32_t* d_total = nullptr;
   int rc = gk_compact_enqueue(ctx, flag, part.d_rows, n_rows, gk_ptr<int32_t>(d_rows), &d_total, temps);
-  if (rc) return done(rc);
+  if (rc) return rc;
   uint32_t total = 0, n_surv = 0;
   std::vector<uint32_t> host((size_t)n_gene);
   bool queued = gk_fetch_queue(ctx, &total, d_total, sizeof(uint32_t)) == hipSuccess &&
@@ -1191,21 +1184,16 @@ static int sample_prepare(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d_
     const int64_t cap = std::min<int64_t>(nv, surv->max_out);
     uint32_t *sflag = nullptr, *vals = nullptr, *d_n = nullptr;
     int32_t* ord = nullptr;
-    auto take = [&](void** p, size_t bytes) {
-      if (gk_pool_malloc(ctx, p, bytes) != hipSuccess) return false;
-      temps.push_back(*p);
-      return true;
-    };
-    if (!take((void**)&sflag, (size_t)nv * sizeof(uint32_t)) || !take((void**)&ord, (size_t)nv * sizeof(int32_t)) ||
-        !take((void**)&vals, (size_t)std::max<int64_t>(2 * cap, 1) * sizeof(uint32_t))) {
+    if (temps.take(&sflag, (size_t)nv * sizeof(uint32_t)) != hipSuccess || temps.take(&ord, (size_t)nv * sizeof(int32_t)) != hipSuccess ||
+        temps.take(&vals, (size_t)std::max<int64_t>(2 * cap, 1) * sizeof(uint32_t)) != hipSuccess) {
       gk_fetch_cancel(ctx);
       gk_set_error("out of device memory for the surviving tallies");
-      return done(GK_ERR_HIP);
+      return GK_ERR_HIP;
     }
     GK_KERNEL(flag_surviving, dim3(nblk(nv)), dim3(kThreads), 0, st, cnt, cnt + nv, vflag, nv, sflag, -1, 0, 0, tab->n_var,
               tab->d_novel_key);
     rc = gk_compact_enqueue(ctx, sflag, nullptr, nv, ord, &d_n, temps);
-    if (rc) { gk_fetch_cancel(ctx); return done(rc); }
+    if (rc) { gk_fetch_cancel(ctx); return rc; }
     if (cap > 0) {
       GK_KERNEL(gather_surviving_queued, dim3(nblk(cap)), dim3(kThreads), 0, st, ord, d_n, cap, cnt, cnt + nv, vflag, vals);
       queued = gk_fetch_queue(ctx, surv->ord, ord, (size_t)cap * sizeof(int32_t)) == hipSuccess &&
@@ -1219,20 +1207,20 @@ static int sample_prepare(gk_ctx* ctx, gk_tab* tab, int32_t multiple, gk_dptr d_
   if (!queued || gk_fetch_wait(ctx) != hipSuccess) {
     gk_fetch_cancel(ctx);
     gk_set_error("sample preamble: %s", hipGetErrorString(hipGetLastError()));
-    return done(GK_ERR_HIP);
+    return GK_ERR_HIP;
   }
   int64_t run = 0;
   for (int g = 0; g < n_gene; ++g) { gene_off_out[g] = run; run += host[g]; }
   gene_off_out[n_gene] = run;
-  if (run != (int64_t)total) { gk_set_error("non-empty rows per gene do not add up"); return done(GK_ERR_ASSERT); }
+  if (run != (int64_t)total) { gk_set_error("non-empty rows per gene do not add up"); return GK_ERR_ASSERT; }
   if (surv) {
     if ((int64_t)n_surv > surv->max_out) {
       gk_set_error("surviving-variant buffer too small (%lld > %lld)", (long long)n_surv, (long long)surv->max_out);
-      return done(GK_ERR_CAPACITY);
+      return GK_ERR_CAPACITY;
     }
     *surv->n_out = n_surv;
   }
-  return done(GK_OK);
+  return GK_OK;
 }
 
 int gk_compat(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag, int32_t vbeg, int32_t vend,

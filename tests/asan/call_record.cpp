@@ -1,4 +1,5 @@
-// Test infrastructure: the ownership rules of a call record (csrc/gk_calls.h: GkCall) on the CPU, under AddressSanitizer.
+// Test infrastructure: the ownership rules of a call record (csrc/gk_calls.h: GkCall) and of the owner of pool blocks that it
+// holds (csrc/gk_blocks.h: GkBlocks) on the CPU, under AddressSanitizer.
 // A stand-alone program: it supplies the pool, the two transfer directions and the result ring that the record uses --
 // they count live blocks, cancels and waits, keep the list of pending deliveries, and make the k-th fallible call fail.
 // gk_fetch_wait copies into EVERY pending destination, so a delivery left pointing into a dead record is a sanitizer
@@ -204,6 +205,85 @@ void kept_block() {
   gk_pool_free(ctx(), p);
 }
 
+// ---- the bare owner (csrc/gk_blocks.h: GkBlocks), as a host function that takes scratch uses it
+int five_takes(void** kept) {
+  GkBlocks temps(ctx());
+  char *a = nullptr, *c = nullptr;
+  uint32_t *b = nullptr, *d = nullptr;
+  double* e = nullptr;
+  GK_HIP(temps.take(&a, 10));
+  GK_HIP(temps.take(&b, 0));        // zero bytes is a block like any other
+  GK_HIP(temps.take(&c, 30));
+  GK_HIP(temps.take(&d, 40));
+  GK_HIP(temps.take(&e, 50));
+  if (kept) {
+    temps.keep(c);
+    *kept = c;
+  }
+  return GK_OK;
+}
+
+void owner_failures() {
+  for (int k = 1; k <= 5; ++k) {     // the k-th take fails: the k - 1 before it go back on the way out
+    reset(k);
+    CHECK(five_takes(nullptr) != GK_OK);
+    CHECK(g_calls == k);
+    CHECK(g_live.empty());
+  }
+  reset(0);
+  CHECK(five_takes(nullptr) == GK_OK);
+  CHECK(g_calls == 5 && g_live.empty());
+}
+
+void owner_keep() {
+  reset(0);
+  void* kept = nullptr;
+  CHECK(five_takes(&kept) == GK_OK);
+  CHECK(g_live.size() == 1 && g_live.count(kept) == 1);      // exactly that block stays out
+  gk_pool_free(ctx(), kept);                                 // its new owner gives it back: accepted
+  CHECK(g_live.empty());
+  GkBlocks temps(ctx());
+  int other = 0;
+  temps.keep(&other);                                        // not a block of the owner: nothing happens
+}
+
+void owner_moves() {
+  reset(0);
+  void *p = nullptr, *q = nullptr;
+  {
+    GkBlocks to;
+    {
+      GkBlocks from(ctx());
+      CHECK(from.take(&p, 10) == hipSuccess);
+      to = std::move(from);
+    }                                                        // the moved-from owner frees nothing
+    CHECK(g_live.size() == 1);
+    GkBlocks built(std::move(to));
+    CHECK(built.take(&q, 20) == hipSuccess);                 // the context came along
+    CHECK(g_live.size() == 2);
+  }                                                          // the moved-to owner frees once (twice is a FAILED of the pool)
+  CHECK(g_live.empty());
+  // a move onto an owner that holds blocks gives those back first
+  GkBlocks a(ctx()), b(ctx());
+  CHECK(a.take(&p, 10) == hipSuccess && b.take(&q, 20) == hipSuccess);
+  a = std::move(b);
+  CHECK(g_live.size() == 1 && g_live.count(q) == 1);
+}
+
+void owner_release_twice() {
+  reset(0);
+  void* p = nullptr;
+  GkBlocks temps(ctx());
+  CHECK(temps.take(&p, 10) == hipSuccess);
+  temps.release();
+  CHECK(g_live.empty());
+  temps.release();                                           // a second free would be a FAILED of the pool
+  CHECK(temps.take(&p, 10) == hipSuccess);                   // and the owner serves on
+  CHECK(g_live.size() == 1);
+  temps.begin(ctx());
+  CHECK(g_live.empty());
+}
+
 }  // namespace
 
 int main() {
@@ -215,6 +295,11 @@ int main() {
   large_result();
   large_send();
   kept_block();
+  CHECK(g_live.empty());
+  owner_failures();
+  owner_keep();
+  owner_moves();
+  owner_release_twice();
   CHECK(g_live.empty());
   if (g_failed) return 1;
   printf("call record: ok\n");
