@@ -487,7 +487,9 @@ int gk_site_verdict_genes(const uint64_t* keys, int64_t n_keys, const int64_t* l
 
 /* ---- EM strategy: typing_em.py:68-188.
  * gk_em_sets: per-row candidate-allele bit sets (getCandidateAllelePerRead + getMostFreqAllele).
- * gk_em_run:  SQUAREM EM on weighted distinct sets (hisatEMnp 107-188), one workgroup. */
+ * gk_em_run:  SQUAREM EM on weighted distinct sets (hisatEMnp 107-188), one workgroup.  *iters_out: the number (from 0)
+ *             of the pass that met diff_threshold, iter_max when none did.  When no set of non-zero weight names an
+ *             allele below n_allele (all weights zero, say) the abundances are zeros and *iters_out is 0. */
 int gk_em_sets(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, int32_t vbeg, int32_t vend,
                gk_dptr d_mask, int32_t words, gk_dptr d_sets_out /* uint32 [n_rows][words] */);
 /* distinct rows of d_sets (uint32 [n_rows][words], as written by gk_em_sets) with their multiplicities,

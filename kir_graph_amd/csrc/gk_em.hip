@@ -596,6 +596,16 @@ int gk_em_run(gk_ctx* ctx, const uint32_t* sets, const double* weight, int32_t n
              "bad EM geometry");
   EmHost h;
   h.add(sets, weight, n_sets, words, n_allele, 0);
+  // No set of non-zero weight names an allele (all weights zero; or the weight lies on bits past n_allele only): the
+  // first step's total would be zero and every abundance NaN after iter_max passes.  Like a bootstrap replicate that
+  // drew nothing (boot_em_batch), the answer is zeros and 0 steps, without a launch.
+  bool named = false;
+  for (int u = 0; u < n_sets && !named; ++u) named = weight[u] != 0.0 && h.set_off[(size_t)u + 1] > h.set_off[u];
+  if (!named) {
+    std::fill(prob_out, prob_out + n_allele, 0.0);
+    *iters_out = 0;
+    return GK_OK;
+  }
   std::vector<double> probs;
   std::vector<int> iters;
   const int rc = run_em(ctx, h, n_allele, iter_max, diff_threshold, probs, iters);

@@ -91,7 +91,10 @@ __device__ void em_step(const EmView<W>& g, const double* in, double* out, doubl
   __syncthreads();
 }
 
-// the whole SQUAREM loop of one solve by a workgroup of kThreads; abundances to prob_out, the steps taken to *iters_out
+// the whole SQUAREM loop of one solve by a workgroup of kThreads; abundances to prob_out, the steps taken to *iters_out.
+// *iters_out is the number of the pass (from 0) whose difference met diff_threshold -- the abundances are those from
+// before that pass -- or iter_max when no pass did: iter_max says "did not stop", which no stopping pass can (they are
+// 0 .. iter_max - 1).  The reference returns no count; a Python loop variable would be left at iter_max - 1 here.
 template <int kThreads, typename W>
 __device__ void em_solve(EmLds& sh, const EmView<W>& g, int iter_max, double diff_threshold, double* prob_out, int* iters_out) {
   const int tid = threadIdx.x;

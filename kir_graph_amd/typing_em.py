@@ -108,7 +108,9 @@ def hisatEMdevice(tab: Tabulation, sets, n_allele: int, iter_max: int = 300,
 def hisat2TypingPerGene(tab: Tabulation, rows: DeviceBuffer, n_rows: int, vbeg: int, vend: int, mask: DeviceBuffer,
                         words: int, alleles: list[str], info: dict | None = None) -> list[Hisat2AlleleResult]:
     """Per-gene EM report.  Raises like the reference when no read names any allele.  ``info`` (optional)
-    receives ``iterations`` (SQUAREM steps until the 1e-4 stop, at most 300) and ``distinct_sets``."""
+    receives ``iterations`` and ``distinct_sets``.  ``iterations`` is the number (from 0) of the SQUAREM pass whose
+    difference met the 1e-4 stop, so 0 .. 299 for a run that stopped, and 300 (``iter_max``) for a run that did not:
+    the reference returns no count, and its loop variable would read 299 both for a stop in the last pass and for none."""
     sets = candidateSetsDistinct(tab, rows, n_rows, vbeg, vend, mask, words)
     prob, count, iters = hisatEMdevice(tab, sets, len(alleles))
     if info is not None:

@@ -175,6 +175,8 @@ def sameAsOracle(sets, count, alleles, stream, prob, iters, seed=SEED):
                 assert prob[b, a] == pytest.approx(want[name], rel=1e-5, abs=1e-9), (b, name)
             else:
                 assert prob[b, a] == 0.0, (b, name)
+        # The oracle's count is its Python loop variable, iter_max - 1 for a run that uses up iter_max; the solver says
+        # iter_max then (csrc/gk_squarem.h).  The equality holds for runs that stop, which all of these do.
         assert int(iters[b]) == want_iters, b
 
 
@@ -217,6 +219,10 @@ def test_solver_equals_the_oracle_beyond_the_scale_row_in_lds(device):
 # (words, n_allele, n_sets, empty first row, a big count every ... sets): the widths of the bit sets, and the numbers of
 # sets either side of the batch kernel's scale row leaving LDS (the point kernel keeps its own there) and past the point
 # kernel's limit of 8192 (both keep it in HBM).  Every case has sets of 100 000 reads: no replicate is empty.
+# Then the edges of the rounds: a workgroup of 512 threads takes 32 sets or alleles per round, one of 1024 takes 64 -- 31,
+# 32, 33 and 65 sets, 65 and 129 alleles.  The sets of the 512-allele case have some 150 members each (density 0.3):
+# more than one stride of the 16 lanes.  tests/test_gpu_squarem_edges.py ties the point solver to a plain reference;
+# with this test, so is the batch solver.
 SAME_SOLVER_CASES = [
     (1, 20, 17, False, 4),
     (2, 33, 17, True, 4),
@@ -224,18 +230,20 @@ SAME_SOLVER_CASES = [
     (1, 24, LDS_SCALE_SETS, False, 1000),
     (1, 24, LDS_SCALE_SETS + 1, False, 1000),
     (1, 24, 8193, False, 1000),
+    (2, 33, 31, False, 4),
+    (2, 33, 32, False, 4),
+    (2, 33, 33, True, 4),
+    (2, 33, 65, False, 4),
+    (3, 65, 40, False, 4),
+    (5, 129, 40, True, 4),
 ]
 
 
-@pytest.mark.parametrize("words,n_allele,n_sets,empty_first,big_every", SAME_SOLVER_CASES)
-def test_batch_solver_is_the_point_solver(device, words, n_allele, n_sets, empty_first, big_every):
-    """boot_em_batch and em_kernel_genes instantiate one solver (csrc/gk_squarem.h) whose sums do not depend on the
-    workgroup size: a replicate's counts handed to gk_em_run as weights (sets that drew no read included: weight 0 gives
-    scale 0 in both) give the replicate's abundances and step count, bit for bit."""
+def batchIsPoint(device, words, n_allele, n_sets, empty_first, big_every, iter_max):
     rng = np.random.default_rng(n_sets * 37 + words)
     sets = randomSets(rng, n_sets, words, n_allele, empty_first)
     count = mixedCounts(rng, n_sets, big_every)
-    prob, iters, got = bootstrapEM(device, [(sets, count, n_allele, 3)], 2, SEED, want_counts=True)
+    prob, iters, got = bootstrapEM(device, [(sets, count, n_allele, 3)], 2, SEED, iter_max=iter_max, want_counts=True)
     keep = sets.any(axis=1)
     assert keep.sum() == n_sets - empty_first
     uniq = np.ascontiguousarray(sets[keep])
@@ -243,10 +251,26 @@ def test_batch_solver_is_the_point_solver(device, words, n_allele, n_sets, empty
         weight = np.ascontiguousarray(got[b][keep].astype(np.float64))
         assert weight.sum() > 0
         point, point_iters = np.zeros(n_allele, dtype=np.float64), C.c_int32(-1)
-        _lib.check(_lib.lib().gk_em_run(device.ctx, uniq.ctypes.data, weight.ctypes.data, len(uniq), words, n_allele, 300, 1e-4,
+        _lib.check(_lib.lib().gk_em_run(device.ctx, uniq.ctypes.data, weight.ctypes.data, len(uniq), words, n_allele, iter_max, 1e-4,
                                         point.ctypes.data, C.byref(point_iters)))
         assert np.array_equal(prob[b], point), b
         assert int(iters[b, 0]) == point_iters.value, b
+    return prob, iters
+
+
+@pytest.mark.parametrize("words,n_allele,n_sets,empty_first,big_every", SAME_SOLVER_CASES)
+def test_batch_solver_is_the_point_solver(device, words, n_allele, n_sets, empty_first, big_every):
+    """boot_em_batch and em_kernel_genes instantiate one solver (csrc/gk_squarem.h) whose sums do not depend on the
+    workgroup size: a replicate's counts handed to gk_em_run as weights (sets that drew no read included: weight 0 gives
+    scale 0 in both) give the replicate's abundances and step count, bit for bit."""
+    batchIsPoint(device, words, n_allele, n_sets, empty_first, big_every, 300)
+
+
+@pytest.mark.parametrize("words,n_allele,n_sets,empty_first,big_every", SAME_SOLVER_CASES)
+def test_batch_solver_is_the_point_solver_after_two_passes(device, words, n_allele, n_sets, empty_first, big_every):
+    """The same at iter_max = 2: the state after exactly two passes, before any stop (a run that is used up says 2)."""
+    prob, iters = batchIsPoint(device, words, n_allele, n_sets, empty_first, big_every, 2)
+    assert (iters <= 2).all()
 
 
 def test_point_result_does_not_change(typed):
