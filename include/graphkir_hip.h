@@ -575,6 +575,26 @@ int gk_call_fit(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32
 int gk_call_fit_extra(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32_t n_table_cols, gk_dptr d_min,
                       uint64_t* with_out /* [n_table_cols] */);
 
+/* Alternatives of a likelihood call (no reference counterpart; extends typing_mulit_allele.py:540-542, 569): what the reads
+ * say about replacing ONE called allele by any other column of the table, in exact integers, from the u8 mismatch table the
+ * search left in HBM -- no search runs again.  d_miss8, ldm, n_rows, n_table_cols, cols, n_cols: as for gk_call_fit.
+ * Per row r < n_rows, with b_k = d_miss8[cols[k]][r] and x = d_miss8[a][r]: m1 = min_k b_k, rest_k = min_{j != k} b_j (255
+ *   when n_cols == 1), new = min(rest_k, x): the row's smallest byte once every copy of k is replaced by a.
+ *   loss_out[k * n_table_cols + a] = sum_r max(0, new - m1), for_out[k * n_table_cols + a] = rows with new > m1;
+ *   gain_out[a] = sum_r max(0, m1 - new), against_out[a] = rows with new < m1 (neither depends on k: new < m1 <=> x < m1).
+ *   loss - gain = M of the swapped set minus M of the called one.  m_out[0] = M = sum_r m1, bytes as stored;
+ *   out_of_range_out[0] = rows with m1 == 255.
+ * d_state, when not 0: uint8 [3][ldm], 16-byte aligned, used in place of a block of the pool: [0][r] = m1, [1][r] = the
+ *   smallest byte outside the unique holder of m1 (255 when n_cols == 1, m1 on a tie), [2][r] = the index k of that unique
+ *   holder, 255 on a tie; entries r >= n_rows are not written.
+ * Waits for its result.  GK_ERR_ARG, and nothing launched: n_rows < 1 or >= 2^31, ldm < n_rows or ldm % 64 != 0,
+ * n_table_cols < 1, n_cols outside 1 .. 16, a column outside 0 .. n_table_cols - 1 or listed twice, a null output, a table
+ * or d_state that is not 16-byte aligned. */
+int gk_call_swap(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32_t n_table_cols, const int32_t* cols,
+                 int32_t n_cols, uint64_t* loss_out /* [n_cols][n_table_cols] */, uint64_t* for_out /* [n_cols][n_table_cols] */,
+                 uint64_t* gain_out /* [n_table_cols] */, uint64_t* against_out /* [n_table_cols] */, uint64_t* m_out /* [1] */,
+                 uint64_t* out_of_range_out /* [1] */, gk_dptr d_state);
+
 /* Per-allele coverage of a likelihood call (no reference counterpart; serves what the reference's --plot would draw, "not
  * supported in this build"): WHERE along backbone `gene` the reads lie that the called set explains, in exact integers,
  * from the u8 mismatch table the search left in HBM joined with the sample's records -- no search runs again.

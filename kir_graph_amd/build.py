@@ -11,7 +11,8 @@ ROOT = PKG.parent
 SOURCES = ["gk_runtime.hip", "gk_scan.hip", "gk_tabulate.hip", "gk_typing.hip", "gk_lut.hip",
            "gk_search.hip", "gk_bound.hip", "gk_em.hip", "gk_cn.hip", "gk_depth.hip", "gk_sampack.cpp", "gk_bamread.cpp", "gk_textout.cpp",
            "gk_comm.cpp", "gk_hostsearch.cpp", "gk_novel.hip", "gk_boot.hip", "gk_callboot.hip", "gk_compat_narrow.hip",
-           "gk_callfit.hip", "gk_callcov.hip", "gk_depthboot.hip", "gk_setsum_few.hip", "gk_rowclass.hip"]
+           "gk_callfit.hip", "gk_callcov.hip", "gk_depthboot.hip", "gk_setsum_few.hip", "gk_rowclass.hip",
+           "gk_callswap.hip"]
 
 
 def hipcc() -> str:
@@ -68,6 +69,8 @@ KERNEL_SOURCES = {
     "callboot_fold": ["gk_callboot.hip", "gk_common.h"],
     "callfit_profile": ["gk_callfit.hip", "gk_common.h"],
     "callfit_extra": ["gk_callfit.hip", "gk_common.h"],
+    "callswap_rows": ["gk_callswap.hip", "gk_common.h"],
+    "callswap_sums": ["gk_callswap.hip", "gk_common.h"],
     "callcov_mark": ["gk_callcov.hip", "gk_common.h"],
     "callcov_mark_lds": ["gk_callcov.hip", "gk_common.h"],
     "callcov_finish": ["gk_callcov.hip", "gk_common.h"],

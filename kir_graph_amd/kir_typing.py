@@ -24,6 +24,7 @@ from . import _lib
 from ._lib import Device
 from .call_bootstrap import MAX_BOOT, MAX_TOP, CallBootstrap, bootstrapCall, homoFactor
 from .call_coverage import CallCoverage, coverCall
+from .call_alternatives import MAX_LISTED, MAX_WITHIN, CallAlternatives, alternativesOfCall
 from .call_fit import MAX_EXTRA, CallFit, fitCall
 from .engine import PreparedGene, PreparedSample, searchMode
 from .hisat2 import SampleData, loadCompact, loadReadsAndVariantsData
@@ -220,7 +221,8 @@ class TypingWithPosNegAllele(_OnLane):
                  exon_only: bool = False, exon_candidate_threshold: float = .9, variant_correction: bool = False,
                  device: Device | None = None, call_bootstrap: int = 0, call_bootstrap_seed: int = 2022,
                  call_bootstrap_top: int = 32, call_fit: bool = False, call_fit_extra: int = 3,
-                 call_coverage: bool = False, call_coverage_len: dict[str, int] | None = None):
+                 call_coverage: bool = False, call_coverage_len: dict[str, int] | None = None,
+                 call_alternatives: bool = False, call_alternatives_within: int = 1, call_alternatives_max: int = 20):
         """``call_bootstrap`` > 0: every gene's adopted result is rescored in that many read-bootstrap replicates
         (``call_bootstrap.bootstrapCall`` on its first ``call_bootstrap_top`` candidate sets; ``self.call_bootstrap``:
         gene -> ``CallBootstrap``); 0: nothing but the point result, and nothing more is launched.
@@ -229,8 +231,18 @@ class TypingWithPosNegAllele(_OnLane):
         ``call_coverage``: every gene's adopted result gets its per-allele coverage (``call_coverage.coverCall``;
         ``self.call_coverage``: gene -> ``CallCoverage``, None for a gene whose report could not be made);
         ``call_coverage_len``: gene -> backbone length, needed with it.  The sample's records must still be in HBM
-        (``tab.mates``).  False: nothing more is launched."""
+        (``tab.mates``).  False: nothing more is launched.
+        ``call_alternatives``: every gene's adopted result gets the alternatives of each called allele
+        (``call_alternatives.alternativesOfCall``: swaps up to ``call_alternatives_within`` mismatches worse count as near,
+        ``call_alternatives_max`` are listed per called allele; ``self.call_alternatives``: gene -> ``CallAlternatives``);
+        False: nothing more is launched."""
         super().__init__()
+        if not 0 <= int(call_alternatives_within) <= MAX_WITHIN:
+            raise ValueError(f"call_alternatives_within: the largest delta listed must lie in 0 .. {MAX_WITHIN}")
+        if not 1 <= int(call_alternatives_max) <= MAX_LISTED:
+            raise ValueError(f"call_alternatives_max: the alternatives listed per allele must lie in 1 .. {MAX_LISTED}")
+        self._call_alternatives = (bool(call_alternatives), int(call_alternatives_within), int(call_alternatives_max))
+        self.call_alternatives: dict[str, CallAlternatives] = {}
         if call_coverage and not call_coverage_len:
             raise ValueError("call_coverage: needs call_coverage_len, the backbone length of every gene")
         self._call_coverage = (bool(call_coverage), dict(call_coverage_len or {}))
@@ -393,6 +405,7 @@ class TypingWithPosNegAllele(_OnLane):
                     self._result[gene], final = p["results"], p["final"]
                 self._bootstrapCall(gene, cn, final)
                 self._fitCall(gene, cn, final)
+                self._alternativesCall(gene, cn, final)
                 self._coverCall(gene, cn, final)
                 yield gene, _calls(gene, final), p["typ_e"].getReadsNum()
         calls = self._collect(entries(), min_reads_num)
@@ -448,6 +461,7 @@ class TypingWithPosNegAllele(_OnLane):
                 self._result[gene] = typ.result
                 self._bootstrapCall(gene, cn, res)
                 self._fitCall(gene, cn, res)
+                self._alternativesCall(gene, cn, res)
                 self._coverCall(gene, cn, res)
                 yield gene, _calls(gene, res), typ.getReadsNum()
         return self._collect(calls(), min_reads_num)
@@ -513,6 +527,7 @@ class TypingWithPosNegAllele(_OnLane):
         self._result[gene] = typ.result
         self._bootstrapCall(gene, cn, res)
         self._fitCall(gene, cn, res)
+        self._alternativesCall(gene, cn, res)
         self._coverCall(gene, cn, res)
         return _calls(gene, res), typ.getReadsNum()
 
@@ -529,6 +544,21 @@ class TypingWithPosNegAllele(_OnLane):
         fit = fitCall(result, extra, names=self._data.index.tables[g].alleles)
         if fit is not None:
             self.call_fit[gene] = fit
+
+    def _alternativesCall(self, gene: str, cn: int, result) -> None:
+        """With ``call_alternatives``: the alternatives of each called allele of the result just adopted for ``gene``
+        (while the sample's tables are in HBM).  A gene without rows, with a failed result or with ``cn == 0`` gets no
+        entry."""
+        on, within, listed = self._call_alternatives
+        if not on:
+            return
+        self.call_alternatives.pop(gene, None)
+        g = self._data.index.gene_id.get(gene)
+        if cn <= 0 or g is None or result is None or result.isFail():
+            return
+        found = alternativesOfCall(result, within, listed, names=self._data.index.tables[g].alleles)
+        if found is not None:
+            self.call_alternatives[gene] = found
 
     def _coverCall(self, gene: str, cn: int, result) -> None:
         """With ``call_coverage``: the per-allele coverage of the result just adopted for ``gene`` (while the sample's
@@ -706,6 +736,10 @@ def selectKirTypingModel(method: str, filename_variant_json, **kwargs: Any) -> T
         kwargs.pop("call_fit_extra", None)
         if kwargs.pop("call_fit", False):
             raise ValueError(f"call_fit: only the likelihood strategies report the fit of a call, not {method!r}")
+        kwargs.pop("call_alternatives_within", None)
+        kwargs.pop("call_alternatives_max", None)
+        if kwargs.pop("call_alternatives", False):
+            raise ValueError(f"call_alternatives: only the likelihood strategies report the alternatives of a call, not {method!r}")
         kwargs.pop("call_coverage_len", None)
         if kwargs.pop("call_coverage", False):
             raise ValueError(f"call_coverage: only the likelihood strategies report the coverage of a call, not {method!r}")

@@ -284,6 +284,16 @@ def writeCallFit(name: str, fits: dict) -> str:
     return name + ".fit.tsv"
 
 
+def writeCallAlternatives(name: str, calls: dict) -> str:
+    """``{name}.alternatives.tsv`` of one sample typed by a likelihood strategy with ``--call-alternatives``: per gene and
+    distinct called allele the alleles that could stand in for it, and the field of its name the reads resolve
+    (``call_alternatives.callAlternativesText``)."""
+    from .call_alternatives import callAlternativesText
+    with open(name + ".alternatives.tsv", "w") as f:
+        f.write(callAlternativesText(calls))
+    return name + ".alternatives.tsv"
+
+
 def writeCallCoverage(name: str, covers: dict, depth: bool = False) -> list[str]:
     """``{name}.coverage.tsv`` of one sample typed by a likelihood strategy with ``--call-coverage``: per gene, region and
     distinct called allele where the reads lie that the called set explains (``call_coverage.callCoverageText``), and with
@@ -318,7 +328,8 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
                 bootstrap_seed: int = 2022, call_bootstrap: int = 0, call_bootstrap_seed: int = 2022,
                 call_bootstrap_top: int = 32, call_fit: bool = False, call_fit_extra: int = 3,
                 call_coverage: bool = False, call_coverage_depth: bool = False,
-                gene_len: dict[str, int] | None = None) -> "cohort.SampleTyper":
+                gene_len: dict[str, int] | None = None, call_alternatives: bool = False,
+                call_alternatives_within: int = 1, call_alternatives_max: int = 20) -> "cohort.SampleTyper":
     """The typing stage of this process (``cohort.SampleTyper``: the sample lanes, search slots, urgent preamble and
     blocking waits that ``bench.py`` measures), finishing every sample the reference's way: its two files written, its
     tabulation released.  Submit ``(SampleData or hand-off file, copy numbers, (name, cn_file))``.
@@ -333,7 +344,10 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
     ``call_coverage`` (``--call-coverage``, likelihood strategies; ``gene_len``: backbone lengths, needed with it): the
     typer reports the per-allele coverage of every gene's called set from the sample's records, which must still be in
     HBM (``mapSamples(keep_records=True)``), and the finish step writes ``{result}.coverage.tsv`` -- with
-    ``call_coverage_depth`` (``--call-coverage-depth``) also ``{result}.coverage.depth.tsv``."""
+    ``call_coverage_depth`` (``--call-coverage-depth``) also ``{result}.coverage.depth.tsv``.
+    ``call_alternatives`` (``--call-alternatives``, likelihood strategies): the typer reports the alternatives of every
+    called allele (``call_alternatives_within``: the largest delta listed as near, ``call_alternatives_max``: alleles listed
+    per called allele), and the finish step writes ``{result}.alternatives.tsv``."""
     def finish(typer, called_alleles, warning_genes, item):
         name, cn_file, source = item
         result = name + typingSuffix(name, cn_file, method)
@@ -358,6 +372,8 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
                 writeCallFit(result, typer.call_fit)
             if call_coverage:
                 writeCallCoverage(result, typer.call_coverage, depth=call_coverage_depth)
+            if call_alternatives:
+                writeCallAlternatives(result, typer.call_alternatives)
         return written
 
     extra = {"bootstrap": bootstrap, "bootstrap_seed": bootstrap_seed} if bootstrap > 0 else {}
@@ -368,6 +384,9 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
         extra.update(call_fit=True, call_fit_extra=call_fit_extra)
     if call_coverage:
         extra.update(call_coverage=True, call_coverage_len=gene_len)
+    if call_alternatives:
+        extra.update(call_alternatives=True, call_alternatives_within=call_alternatives_within,
+                     call_alternatives_max=call_alternatives_max)
     return cohort.SampleTyper(method, finish=finish, **extra)
 
 
@@ -472,6 +491,14 @@ def createParser() -> argparse.ArgumentParser:
                         "explains best and alone, the alleles that would explain the most as one more copy)")
     p.add_argument("--call-fit-extra", type=int, default=3,
                    help="Extra alleles the fit report lists per gene (0 .. 64; 0: none are looked for)")
+    p.add_argument("--call-alternatives", action="store_true",
+                   help="Likelihood strategies (full / pv / exonfirst) only: report for every called allele the alleles that "
+                        "could stand in for it -- better, identical (no read tells them apart), balanced, near -- and the field "
+                        "of its name the reads resolve; writes {result}.alternatives.tsv")
+    p.add_argument("--call-alternatives-within", type=int, default=1,
+                   help="The largest number of mismatches a swap may cost and still be listed as near (0 .. 64)")
+    p.add_argument("--call-alternatives-max", type=int, default=20,
+                   help="Alternatives listed per called allele (1 .. 256); every class is always counted in full")
     p.add_argument("--call-coverage", action="store_true",
                    help="Likelihood strategies (full / pv / exonfirst) only: report where along every gene the reads lie that "
                         "its called set explains; writes {result}.coverage.tsv (per region -- upstream, exons, introns, "
@@ -518,6 +545,20 @@ def _callFitArgs(args: argparse.Namespace) -> dict:
     return {"call_fit": True, "call_fit_extra": extra}
 
 
+def _callAlternativesArgs(args: argparse.Namespace) -> dict:
+    """The ``sampleTyper`` keywords of ``--call-alternatives`` (none when the flag is not given); a
+    ``--call-alternatives-within`` outside 0 .. 64, a ``--call-alternatives-max`` outside 1 .. 256 or the EM strategy is an
+    error."""
+    if not getattr(args, "call_alternatives", False):
+        return {}
+    within = int(getattr(args, "call_alternatives_within", 1))
+    listed = int(getattr(args, "call_alternatives_max", 20))
+    if not 0 <= within <= 64 or not 1 <= listed <= 256 or args.allele_strategy in ("em", "report"):
+        raise ValueError("--call-alternatives needs a --call-alternatives-within in 0 .. 64, a --call-alternatives-max in "
+                         "1 .. 256 and a likelihood strategy (--allele-strategy full, pv or exonfirst)")
+    return {"call_alternatives": True, "call_alternatives_within": within, "call_alternatives_max": listed}
+
+
 def _callCoverageArgs(args: argparse.Namespace, index_ref: str | None = None) -> dict:
     """The ``sampleTyper`` keywords of ``--call-coverage`` / ``--call-coverage-depth`` (none when neither is given; the
     backbone lengths are read when ``index_ref`` is); the EM strategy is an error."""
@@ -559,6 +600,7 @@ def main(args: argparse.Namespace) -> None:
         raise ValueError("--em-bootstrap needs a positive count and --allele-strategy em (or report)")
     _callBootstrapArgs(args)
     _callFitArgs(args)
+    _callAlternativesArgs(args)
     _callCoverageArgs(args)
     _cnBootstrapArgs(args)
 
@@ -634,7 +676,7 @@ def _runCohort(args, names, reads, cn_files, index, index_ref, cohort_name, comm
     novel = getattr(args, "novel_discovery", False)
     lanes = sampleTyper(method, novel_index=index_ref if novel else None, bootstrap=int(getattr(args, "em_bootstrap", 0) or 0),
                         bootstrap_seed=int(getattr(args, "em_bootstrap_seed", 2022)), **_callBootstrapArgs(args),
-                        **_callFitArgs(args), **_callCoverageArgs(args, index_ref))
+                        **_callFitArgs(args), **_callCoverageArgs(args, index_ref), **_callAlternativesArgs(args))
     try:
         confidence: list | None = [] if _cnBootstrapArgs(args) else None
         allele_files, my_cn = _typeShare(args, lanes, pick(names), pick(reads), my_cn, pick, index, index_ref, cohort_name,
