@@ -377,6 +377,21 @@ int gk_expand_index(gk_ctx* ctx, gk_lut* lut, gk_dptr d_lidx, int64_t ldi, int64
 int gk_bound_step(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, gk_dptr d_msum, const int32_t* ids,
                   int32_t n_sets, int32_t c_prev, const int32_t* cols, int32_t n_cols, const uint8_t* first,
                   int32_t top_n, int32_t cap, uint32_t* hdr_out, int32_t* idx_out, uint32_t* m_out);
+/* gk_bound_step on the PSEUDO-ROWS of a table whose rows fall into classes (csrc/gk_classrows.h): d_class_of (device,
+ * uint32 [n_rows]) names the class of every row, 0 <= class < n_classes <= n_rows, and rows of one class hold the same
+ * byte in every column.  A class of w rows becomes one row in plane b for every set bit b of w; the bound sums plane by
+ * plane and counts plane b 2^b times -- the same totals, cut and selection.  d_msum (device, uint32, an entry per column
+ * up to the highest that ids or cols name) receives the column sums, formed by class.  GK_TEST_HOOKS=class_bound=off: the
+ * row route.  For the tests and tools; waits for the stream. */
+int gk_bound_step_classes(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, gk_dptr d_class_of, int64_t n_classes,
+                          gk_dptr d_msum, const int32_t* ids, int32_t n_sets, int32_t c_prev, const int32_t* cols,
+                          int32_t n_cols, const uint8_t* first, int32_t top_n, int32_t cap, uint32_t* hdr_out,
+                          int32_t* idx_out, uint32_t* m_out);
+/* The slice planner of that route, on the host: plane_counts[24] = classes per plane, `want` = slices that fill the GPU;
+ * slices_out receives (first block, end block, shift, 0) per slice of 128-row blocks, at most `capacity` of them,
+ * *n_slices their number, plane_blk0_out[25] (may be NULL) the first block of every plane and the block count. */
+int gk_class_slice_plan(const uint32_t* plane_counts, int64_t want, int32_t* slices_out, int32_t capacity, int32_t* n_slices,
+                        int64_t* plane_blk0_out);
 int gk_setsum(gk_ctx* ctx, gk_dptr d_L, int64_t n_rows, int64_t ld, const int32_t* ids, int32_t n_sets, int32_t c,
               double* value_out, double* frac_out);
 /* gk_setsum for a FEW sets (at most 4096) of c = 1 .. 4 alleles by workgroups that own a chunk of 8192 rows and read only

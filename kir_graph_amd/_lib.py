@@ -224,6 +224,10 @@ _SIGS = {
     "gk_bound_step": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_uint64, C.c_void_p, C.c_int32,
                                 C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),
+    "gk_bound_step_classes": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.c_uint64,
+                                        C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gk_class_slice_plan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "gk_setsum": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
                             C.c_void_p, C.c_void_p]),
     "gk_setsum_few": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,

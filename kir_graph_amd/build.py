@@ -12,7 +12,7 @@ SOURCES = ["gk_runtime.hip", "gk_scan.hip", "gk_tabulate.hip", "gk_typing.hip", 
            "gk_search.hip", "gk_bound.hip", "gk_em.hip", "gk_cn.hip", "gk_depth.hip", "gk_sampack.cpp", "gk_bamread.cpp", "gk_textout.cpp",
            "gk_comm.cpp", "gk_hostsearch.cpp", "gk_novel.hip", "gk_boot.hip", "gk_callboot.hip", "gk_compat_narrow.hip",
            "gk_callfit.hip", "gk_callcov.hip", "gk_depthboot.hip", "gk_setsum_few.hip", "gk_rowclass.hip",
-           "gk_callswap.hip"]
+           "gk_callswap.hip", "gk_classrows.hip"]
 
 
 def hipcc() -> str:
@@ -42,12 +42,12 @@ KERNEL_SOURCES = {
     "tab_count": ["gk_tabulate.hip", "gk_common.h"],
     "tab_emit": ["gk_tabulate.hip", "gk_common.h"],
     "tab_expand": ["gk_tabulate.hip", "gk_common.h"],
-    "minsum_sad": ["gk_bound.hip", "gk_common.h"],
-    "minsum_finish": ["gk_bound.hip", "gk_common.h"],
+    "minsum_sad": ["gk_bound.hip", "gk_classrows.h", "gk_common.h"],
+    "minsum_finish": ["gk_bound.hip", "gk_classrows.h", "gk_common.h"],
     "select_hist1": ["gk_bound.hip", "gk_common.h"],
     "select_hist2": ["gk_bound.hip", "gk_common.h"],
     "select_append": ["gk_bound.hip", "gk_common.h"],
-    "setmin_u8": ["gk_bound.hip", "gk_common.h"],
+    "setmin_u8": ["gk_bound.hip", "gk_classrows.h", "gk_common.h"],
     "fraction_chunks": ["gk_search.hip", "gk_common.h"],
     "setsum_leaves": ["gk_search.hip", "gk_common.h"],
     "fold_leaves": ["gk_search.hip", "gk_common.h"],
@@ -82,6 +82,11 @@ KERNEL_SOURCES = {
     "rowclass_verify": ["gk_rowclass.hip", "gk_rowclass.h", "gk_common.h"],
     "rowclass_rank": ["gk_rowclass.hip", "gk_rowclass.h", "gk_common.h"],
     "rowclass_expand": ["gk_rowclass.hip", "gk_rowclass.h", "gk_common.h"],
+    "class_clear": ["gk_classrows.hip", "gk_classrows.h", "gk_common.h"],
+    "class_weights": ["gk_classrows.hip", "gk_classrows.h", "gk_common.h"],
+    "class_planes": ["gk_classrows.hip", "gk_classrows.h", "gk_common.h"],
+    "class_scatter": ["gk_classrows.hip", "gk_classrows.h", "gk_common.h"],
+    "class_gather": ["gk_classrows.hip", "gk_classrows.h", "gk_common.h"],
 }
 
 

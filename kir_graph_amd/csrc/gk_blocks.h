@@ -52,6 +52,8 @@ struct GkBlocks {
     for (size_t i = 0; i < blocks_.size(); ++i)
       if (blocks_[i] == p) { blocks_.erase(blocks_.begin() + (long)i); return; }
   }
+  // a pool block of ctx() that another owner let go of (keep) is this one's from now on
+  void adopt(void* p) { blocks_.push_back(p); }
   // everything back to the pool, now
   void release() {
     for (void* p : blocks_) gk_pool_free(ctx_, p);

@@ -22,9 +22,15 @@
 // 8 words per 64 SADs.  Integer sums are associative, so the reads are cut into as many slices as fill the
 // GPU; a second small kernel adds the slices, and a two-level radix select over three more one-element-per-
 // thread kernels finds M_T and compacts the selection.
+//
+// Rows of one class hold the same bytes (gk_rowclass.hip), and the sums are integers: with a pseudo-row table
+// (gk_classrows.h: one row per set bit of a class's weight, plane by plane) the same kernels run over the pseudo-rows --
+// a slice lies inside one plane, and what it sums counts 2^plane times when the slices are added.
 #include <algorithm>
+#include <type_traits>
 
 #include "gk_calls.h"
+#include "gk_classrows.h"
 
 namespace {
 
@@ -64,14 +70,17 @@ __global__ __launch_bounds__(kThreads) void colsum_u8(const uint8_t* __restrict_
   if (threadIdx.x == 0) out[blockIdx.x] = part[0];
 }
 
-// P[t][r] = min over the c columns of set t (allele_prob of a set in mismatch counts, line 569), psum[t] = its sum
+// P[t][r] = min over the c columns of set t (allele_prob of a set in mismatch counts, line 569), psum[t] = its sum.
+// kPlanes: the table holds pseudo-rows; a word of 16 of them counts 2^blk_shift[its block] times, summed in 64 bits (the
+// weighted sum is a sum over the rows: below 2^32)
+template <bool kPlanes>
 __global__ __launch_bounds__(kThreads) void setmin_u8(const uint8_t* __restrict__ m, int64_t ldm,
                                                       const int32_t* __restrict__ ids, int c, uint8_t* __restrict__ P,
-                                                      uint32_t* __restrict__ psum) {
+                                                      uint32_t* __restrict__ psum, const uint8_t* __restrict__ blk_shift) {
   const int t = blockIdx.x;
   const int64_t n16 = ldm / 16;
   uint4* dst = reinterpret_cast<uint4*>(P + (int64_t)t * ldm);
-  uint32_t acc = 0;
+  typename std::conditional<kPlanes, uint64_t, uint32_t>::type acc = 0;
   for (int64_t i = threadIdx.x; i < n16; i += kThreads) {
     uint4 w = reinterpret_cast<const uint4*>(m + (int64_t)ids[t * c] * ldm)[i];
     for (int k = 1; k < c; ++k) {
@@ -79,26 +88,32 @@ __global__ __launch_bounds__(kThreads) void setmin_u8(const uint8_t* __restrict_
       w.x = min_u8x4(w.x, v.x); w.y = min_u8x4(w.y, v.y); w.z = min_u8x4(w.z, v.z); w.w = min_u8x4(w.w, v.w);
     }
     dst[i] = w;
-    acc = sad4(w.x, 0, acc); acc = sad4(w.y, 0, acc); acc = sad4(w.z, 0, acc); acc = sad4(w.w, 0, acc);
+    if (kPlanes) {
+      const uint32_t word = sad4(w.w, 0, sad4(w.z, 0, sad4(w.y, 0, sad4(w.x, 0, 0))));
+      acc += (uint64_t)word << blk_shift[i / kW];
+    } else {
+      acc = sad4(w.x, 0, acc); acc = sad4(w.y, 0, acc); acc = sad4(w.z, 0, acc); acc = sad4(w.w, 0, acc);
+    }
   }
-  __shared__ uint32_t part[kThreads];
+  __shared__ decltype(acc) part[kThreads];
   part[threadIdx.x] = acc;
   __syncthreads();
   for (int s = kThreads / 2; s > 0; s >>= 1) {
     if (threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
     __syncthreads();
   }
-  if (threadIdx.x == 0) psum[t] = part[0];
+  if (threadIdx.x == 0) psum[t] = (uint32_t)part[0];
 }
 
-// partial[slice][t][a] = sum over the slice's reads of |P_t[r] - m_a[r]|
+// partial[slice][t][a] = sum over the slice's reads of |P_t[r] - m_a[r]|; the slice is blocks_per_slice blocks from its
+// number on, or, with a slice table (pseudo-rows), the blocks [x, y) of its entry
 __global__ __launch_bounds__(kThreads, 2) void minsum_sad(const uint8_t* __restrict__ Pbase, int64_t ldp,
                                                           const int32_t* __restrict__ pcol, int n_sets,
                                                           const uint8_t* __restrict__ Cbase, int64_t ldc,
                                                           const int32_t* __restrict__ cols, int n_cols, int64_t n16,
                                                           int blocks_per_slice, int tiles_a,
                                                           uint32_t* __restrict__ partial, uint32_t* zero_state,
-                                                          int n_zero_words) {
+                                                          int n_zero_words, const int4* __restrict__ slice_tab) {
   __shared__ uint4 lds[(kBT + kBA) * kLd];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   // the selection state of the kernels that follow this one on the stream starts at zero (was a fill of its own)
@@ -106,9 +121,14 @@ __global__ __launch_bounds__(kThreads, 2) void minsum_sad(const uint8_t* __restr
     for (int w = tid; w < n_zero_words; w += kThreads) zero_state[w] = 0;
   const int tile_t = blockIdx.x / tiles_a, tile_a = blockIdx.x % tiles_a;
   const int t0 = tile_t * kBT, c0 = tile_a * kBA;
-  const int64_t blk0 = (int64_t)blockIdx.y * blocks_per_slice;
   const int64_t n_blk = (n16 + kW - 1) / kW;
-  const int64_t blk1 = min<int64_t>(blk0 + blocks_per_slice, n_blk);
+  int64_t blk0 = (int64_t)blockIdx.y * blocks_per_slice;
+  int64_t blk1 = min<int64_t>(blk0 + blocks_per_slice, n_blk);
+  if (slice_tab) {
+    const int4 s = slice_tab[blockIdx.y];
+    blk0 = s.x;
+    blk1 = min<int64_t>(s.y, n_blk);
+  }
 
   // staging: thread -> word (tid & 7) of columns (tid >> 3) + 32 q; columns 0..63 are the sets, 64..127 the alleles
   const int sw = tid & (kW - 1);
@@ -189,19 +209,23 @@ struct SelState {
   uint32_t hist1[kBins], hist2[kBins];
 };
 
-// M[t][a] = (psum[t] + msum[col a] - sum of the slices) / 2 for first occurrences, kNotFirst otherwise
+// M[t][a] = (psum[t] + msum[col a] - sum of the slices) / 2 for first occurrences, kNotFirst otherwise; with a slice
+// table a slice counts 2^z of its entry times (64 bits: the weighted sum is the SAD over the rows, below 2^32)
 __global__ __launch_bounds__(kThreads) void minsum_finish(const uint32_t* __restrict__ partial, int n_slices,
                                                           int64_t n_out, int n_cols, const uint32_t* __restrict__ psum,
                                                           const int32_t* __restrict__ pcol,
                                                           const uint32_t* __restrict__ msum,
                                                           const int32_t* __restrict__ cols,
                                                           const uint8_t* __restrict__ first, uint32_t* __restrict__ M,
-                                                          SelState* __restrict__ st) {
+                                                          SelState* __restrict__ st, const int4* __restrict__ slice_tab) {
   const int64_t o = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   uint32_t v = kNotFirst;
   if (o < n_out && first[o]) {
-    uint32_t sad = 0;
-    for (int s = 0; s < n_slices; ++s) sad += partial[(int64_t)s * n_out + o];
+    uint64_t sad = 0;
+    if (slice_tab)
+      for (int s = 0; s < n_slices; ++s) sad += (uint64_t)partial[(int64_t)s * n_out + o] << slice_tab[s].z;
+    else
+      for (int s = 0; s < n_slices; ++s) sad += partial[(int64_t)s * n_out + o];
     const int t = (int)(o / n_cols), a = (int)(o % n_cols);
     const uint32_t sp = pcol ? msum[pcol[t]] : psum[t];
     // sp + msum - sad = 2 M: with bytes up to 255 it passes 2^32 from 8.4 M reads on, while M itself (<= 255 n_rows)
@@ -380,6 +404,13 @@ int gk_bound_step(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, gk_
 int gk_bound_enqueue(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, gk_dptr d_msum, const int32_t* ids,
                      int32_t n_sets, int32_t c_prev, const int32_t* cols, int32_t n_cols, const uint8_t* first,
                      int32_t top_n, int32_t cap, GkBoundCall& call) {
+  return gk_bound_enqueue_classes(ctx, d_miss8, ldm, n_rows, d_msum, ids, n_sets, c_prev, cols, n_cols, first, top_n, cap,
+                                  nullptr, call);
+}
+
+int gk_bound_enqueue_classes(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, gk_dptr d_msum, const int32_t* ids,
+                             int32_t n_sets, int32_t c_prev, const int32_t* cols, int32_t n_cols, const uint8_t* first,
+                             int32_t top_n, int32_t cap, const GkClassRows* rec, GkBoundCall& call) {
   gk_bind(ctx);
   GK_REQUIRE(ctx && d_miss8 && d_msum && ids && cols && first, "null pointer");
   GK_REQUIRE(n_sets >= 1 && n_cols >= 1 && c_prev >= 1 && c_prev <= 8 && top_n >= 1 && cap >= 1, "bad bound arguments");
@@ -387,40 +418,63 @@ int gk_bound_enqueue(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, 
   GK_REQUIRE(n_rows < (int64_t)16000000, "too many reads for 32-bit mismatch totals");
   hipStream_t st = ctx->stream;
   const int64_t n_out = (int64_t)n_sets * n_cols;
+  const uint8_t* miss = gk_ptr<uint8_t>(d_miss8);
+  if (rec) {      // the pseudo-rows of this table stand for its rows: every kernel below runs over them
+    GK_REQUIRE(rec->ready() && rec->n_rows == n_rows && rec->ldq > 0 && rec->ldq % kClassBlockRows == 0,
+               "the pseudo-row table is not this table's");
+    for (size_t i = 0; i < (size_t)n_sets * c_prev; ++i) GK_REQUIRE(ids[i] >= 0 && ids[i] < rec->n_cols, "column outside the pseudo-row table");
+    for (int a = 0; a < n_cols; ++a) GK_REQUIRE(cols[a] >= 0 && cols[a] < rec->n_cols, "column outside the pseudo-row table");
+    miss = rec->Q;
+    ldm = rec->ldq;
+  }
+  const int64_t n16 = ldm / 16;
+  const int64_t n_blk = (n16 + kW - 1) / kW;
+  const int tiles_t = (n_sets + kBT - 1) / kBT, tiles_a = (n_cols + kBA - 1) / kBA;
+  // enough slices of the reads to fill the GPU (256 CUs x 2 workgroups x 4), at least 16 blocks each
+  const int64_t fill = (2048 + (int64_t)tiles_t * tiles_a - 1) / ((int64_t)tiles_t * tiles_a);
+  const int64_t want = std::max<int64_t>(1, std::min<int64_t>(fill, std::max<int64_t>(1, n_blk / 16)));
+  int blocks_per_slice = (int)((n_blk + want - 1) / want);
+  int n_slices = (int)((n_blk + blocks_per_slice - 1) / blocks_per_slice);
+  std::vector<int32_t> slices;      // pseudo-rows: the rule holds plane by plane, and no slice crosses a plane
+  if (rec) {
+    gk_class_slices(rec->plane_blk0, fill, slices);
+    n_slices = (int)(slices.size() / 4);
+    blocks_per_slice = 0;
+  }
   call.begin(ctx);
-  // parameters through the context's pinned ring: [ids | cols | first mask]
+  // parameters through the context's pinned ring: [ids | cols | slice table | first mask]
   const size_t n_ids = (size_t)n_sets * c_prev;
-  const size_t par_bytes = (n_ids + (size_t)n_cols) * sizeof(int32_t) + (size_t)n_out;
+  const size_t n_pad = rec ? (size_t)(-(int64_t)(n_ids + n_cols) & 3) : 0;      // the slice table starts on 16 bytes
+  const size_t int_bytes = (n_ids + (size_t)n_cols + n_pad) * sizeof(int32_t);
+  const size_t slice_bytes = slices.size() * sizeof(int32_t);
+  const size_t par_bytes = int_bytes + slice_bytes + (size_t)n_out;
   char* d_par = nullptr;
   GK_HIP(call.take((void**)&d_par, par_bytes));
   {
     std::vector<char> packed(par_bytes);   // one copy instead of three (every runtime call is contended by the host threads)
     memcpy(packed.data(), ids, n_ids * sizeof(int32_t));
     memcpy(packed.data() + n_ids * sizeof(int32_t), cols, (size_t)n_cols * sizeof(int32_t));
-    memcpy(packed.data() + (n_ids + n_cols) * sizeof(int32_t), first, (size_t)n_out);
+    if (slice_bytes) memcpy(packed.data() + int_bytes, slices.data(), slice_bytes);
+    memcpy(packed.data() + int_bytes + slice_bytes, first, (size_t)n_out);
     GK_HIP(call.send(d_par, packed.data(), par_bytes));
   }
   const int32_t* d_ids = (const int32_t*)d_par;
   const int32_t* d_cols = d_ids + n_ids;
-  const uint8_t* d_first = (const uint8_t*)(d_cols + n_cols);
+  const int4* d_slices = rec ? (const int4*)(d_par + int_bytes) : nullptr;
+  const uint8_t* d_first = (const uint8_t*)(d_par + int_bytes + slice_bytes);
 
-  const uint8_t* miss = gk_ptr<uint8_t>(d_miss8);
   uint8_t* d_P = nullptr;
   uint32_t* d_psum = nullptr;
   if (c_prev >= 2) {   // previous sets of two or more alleles become one column each
     GK_HIP(call.take((void**)&d_P, (size_t)n_sets * (size_t)ldm));
     GK_HIP(call.take((void**)&d_psum, (size_t)n_sets * sizeof(uint32_t)));
-    GK_PROF(ctx, "setmin_u8", GK_KERNEL(setmin_u8, dim3((unsigned)n_sets), dim3(kThreads), 0, st, miss, ldm, d_ids,
-                                        c_prev, d_P, d_psum));
+    if (rec)
+      GK_PROF(ctx, "setmin_u8", GK_KERNEL(setmin_u8<true>, dim3((unsigned)n_sets), dim3(kThreads), 0, st, miss, ldm, d_ids,
+                                          c_prev, d_P, d_psum, rec->blk_shift));
+    else
+      GK_PROF(ctx, "setmin_u8", GK_KERNEL(setmin_u8<false>, dim3((unsigned)n_sets), dim3(kThreads), 0, st, miss, ldm, d_ids,
+                                          c_prev, d_P, d_psum, (const uint8_t*)nullptr));
   }
-  const int64_t n16 = ldm / 16;
-  const int64_t n_blk = (n16 + kW - 1) / kW;
-  const int tiles_t = (n_sets + kBT - 1) / kBT, tiles_a = (n_cols + kBA - 1) / kBA;
-  // enough slices of the reads to fill the GPU (256 CUs x 2 workgroups x 4), at least 16 blocks each
-  int64_t want = (2048 + (int64_t)tiles_t * tiles_a - 1) / ((int64_t)tiles_t * tiles_a);
-  want = std::max<int64_t>(1, std::min<int64_t>(want, std::max<int64_t>(1, n_blk / 16)));
-  const int blocks_per_slice = (int)((n_blk + want - 1) / want);
-  const int n_slices = (int)((n_blk + blocks_per_slice - 1) / blocks_per_slice);
   uint32_t *d_partial = nullptr, *d_M = nullptr;
   // selection state, indices and totals in ONE block, so that one copy brings the result back (the kernels update the
   // state with atomics: it stays in device memory, no slot of the result ring)
@@ -436,12 +490,12 @@ int gk_bound_enqueue(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, 
                 GK_KERNEL(minsum_sad, dim3((unsigned)(tiles_t * tiles_a), (unsigned)n_slices), dim3(kThreads), 0, st,
                           c_prev >= 2 ? d_P : miss, ldm, c_prev >= 2 ? (const int32_t*)nullptr : d_ids, n_sets, miss,
                           ldm, d_cols, n_cols, n16, blocks_per_slice, tiles_a, d_partial, (uint32_t*)d_state,
-                          (int)(sizeof(SelState) / sizeof(uint32_t))));
+                          (int)(sizeof(SelState) / sizeof(uint32_t)), d_slices));
   const dim3 per_elem((unsigned)((n_out + kThreads - 1) / kThreads));
   GK_PROF(ctx, "minsum_finish",
           GK_KERNEL(minsum_finish, per_elem, dim3(kThreads), 0, st, d_partial, n_slices, n_out, n_cols, d_psum,
                     c_prev >= 2 ? (const int32_t*)nullptr : d_ids, gk_ptr<uint32_t>(d_msum), d_cols, d_first, d_M,
-                    d_state));
+                    d_state, d_slices));
   const dim3 strided((unsigned)std::min<int64_t>(kSelBlocks, (n_out + kThreads - 1) / kThreads));
   GK_PROF(ctx, "select_hist1", GK_KERNEL(select_hist1, strided, dim3(kThreads), 0, st, d_M, n_out, d_state));
   GK_PROF(ctx, "select_hist2", GK_KERNEL(select_hist2, strided, dim3(kThreads), 0, st, d_M, n_out, top_n, d_state));

@@ -132,6 +132,11 @@ struct GkBoundCall : GkCallOf<char> {      // back: [SelState | idx[cap] | m[cap
 int gk_bound_enqueue(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, gk_dptr d_msum, const int32_t* ids,
                      int32_t n_sets, int32_t c_prev, const int32_t* cols, int32_t n_cols, const uint8_t* first,
                      int32_t top_n, int32_t cap, GkBoundCall& call);
+// the same on the pseudo-rows of the table (gk_classrows.h) when `rec` is given: same totals, same cut, same selection
+struct GkClassRows;
+int gk_bound_enqueue_classes(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, gk_dptr d_msum, const int32_t* ids,
+                             int32_t n_sets, int32_t c_prev, const int32_t* cols, int32_t n_cols, const uint8_t* first,
+                             int32_t top_n, int32_t cap, const GkClassRows* rec, GkBoundCall& call);
 // hdr_out[4] = candidates, cut, selected, 0; idx_out / m_out hold min(selected, cap) entries
 void gk_bound_collect(gk_ctx* ctx, GkBoundCall& call, uint32_t* hdr_out, int32_t* idx_out, uint32_t* m_out);
 

@@ -1,7 +1,8 @@
 // The two list-valued environment variables of the library (everything else that reads the environment is a setting a
 // user of the command line may want: see README.md):
 //   GK_TRACE       development traces on stderr, comma-separated: pool (large pool misses), search (host / wait split of
-//                  gk_sample_search), ingest (phases of the host ingest), bench (host timeline of bench.py)
+//                  gk_sample_search), ingest (phases of the host ingest), bench (host timeline of bench.py), class_bound (per table
+//                  with a class record: rows, classes, pseudo-rows, padded pseudo-rows and the route of its bound)
 //   GK_TEST_HOOKS  switches the TESTS use to force rarely taken paths, comma-separated `name` or `name=value`:
 //                  two_walks (tabulation: second walk instead of the saved words), novel_log2cap=N (size of the first
 //                  novel-variant table), bam_segments=N (segments of the BAM record index), setsum=tiles|leaves (either one also
@@ -10,7 +11,9 @@
 //                  instead of compat_rows8), depthw_budget=BYTES (gk_depth_weighted: the bytes a slice of replicates may take,
 //                  so that a few replicates already make several slices), row_classes=on|off (gk_compat_log_miss(_cols):
 //                  the table through the row classes of gk_rowclass.hip, or never), rowclass_hashbits=N (their hash cut to
-//                  N bits: rows of different sequences meet in one slot); read by the Python side only:
+//                  N bits: rows of different sequences meet in one slot), class_bound=on|off|nomem (read per call: the integer bound
+//                  over the pseudo-rows of the row classes wherever a class record exists, or never; nomem: taken, and the
+//                  pool refuses the pseudo-row table, gk_classrows.h); read by the Python side only:
 //                  bam_reader=samtools, ingest_ahead=N
 #pragma once
 #include <cstdlib>

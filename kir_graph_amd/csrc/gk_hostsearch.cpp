@@ -25,7 +25,27 @@
 #include <unistd.h>
 
 #include "gk_calls.h"
+#include "gk_classrows.h"
 #include "gk_lut.h"
+#include "gk_rowclass.h"
+
+// The integer bound over the pseudo-rows of a table's row classes (gk_classrows.h), pipelined form only.  Weak: the
+// host-only builds of this file (tests/asan) have no stand-ins for these; without them every table is written, summed
+// and searched over its rows
+__attribute__((weak)) int gk_compat_log_miss_owned(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag,
+                                                   int32_t vbeg, int32_t vend, gk_dptr d_mask, int32_t words, int32_t n_allele,
+                                                   int32_t keep_empty, gk_lut* lut, const int32_t* table_cols,
+                                                   int32_t n_table_cols, gk_dptr d_log, gk_dptr d_miss8, int64_t ldm,
+                                                   gk_dptr d_flags, GkClassOf* owner);
+__attribute__((weak)) int gk_classweights_enqueue(gk_ctx* ctx, const uint32_t* class_of, int64_t n_rows, const uint32_t* d_flags,
+                                                  uint32_t* msum, int n_msum, GkClassWeights* out);
+__attribute__((weak)) int gk_classrows_build(gk_ctx* ctx, const GkClassWeights& cw, const uint32_t* counts_host,
+                                             const uint8_t* miss8, int64_t ldm, int n_cols, uint32_t* msum, GkClassRows* out);
+__attribute__((weak)) bool gk_use_class_bound(int64_t padded_pseudo_rows, int64_t n_rows);
+__attribute__((weak)) int gk_bound_enqueue_classes(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, gk_dptr d_msum,
+                                                   const int32_t* ids, int32_t n_sets, int32_t c_prev, const int32_t* cols,
+                                                   int32_t n_cols, const uint8_t* first, int32_t top_n, int32_t cap,
+                                                   const GkClassRows* rec, GkBoundCall& call);
 
 namespace {
 
@@ -265,6 +285,8 @@ struct GeneSearch {
   std::vector<std::vector<int32_t>> step_cols;
   gk_argsort_fn argsort = nullptr;
   bool bound = false, unique_cols = true;
+  // the pseudo-rows of the table's row classes, shared by every search on the table; null: the bound runs over the rows
+  std::shared_ptr<const GkClassRows> class_rows;
   std::unique_ptr<gk_search> S;
   // state of the step in flight
   std::vector<uint8_t> first;
@@ -373,10 +395,14 @@ struct GeneSearch {
     step_done = bound_in_flight = sums_in_flight = false;
     if (bound && N > 0 && unique_cols) {
       const int cap = 4 * T + 4096;
-      int rc = gk_bound_enqueue(ctx, d_miss8, ldm, n_rows, d_msum, prev.ids.data(), Tp, k, cols.data(), A, first.data(), T,
-                                cap, bcall);
+      const GkClassRows* const rec = class_rows && class_rows->ready() && gk_bound_enqueue_classes ? class_rows.get() : nullptr;
+      int rc = rec ? gk_bound_enqueue_classes(ctx, d_miss8, ldm, n_rows, d_msum, prev.ids.data(), Tp, k, cols.data(), A,
+                                              first.data(), T, cap, rec, bcall)
+                   : gk_bound_enqueue(ctx, d_miss8, ldm, n_rows, d_msum, prev.ids.data(), Tp, k, cols.data(), A, first.data(), T,
+                                      cap, bcall);
       if (rc) return rc;
-      S->note(1, n_rows, Tp, A, k == 1 ? S->distinct(prev.ids.data(), prev.ids.size()) : Tp, 0, 0);
+      // the rows the launch runs over: the padded pseudo-rows with a class record
+      S->note(1, rec ? rec->ldq : n_rows, Tp, A, k == 1 ? S->distinct(prev.ids.data(), prev.ids.size()) : Tp, 0, 0);
       bound_in_flight = true;
     }
     return GK_OK;
@@ -669,7 +695,8 @@ namespace {
 
 /* All genes in LOCK-STEP: each phase is queued for every gene before ONE wait (about ten stream synchronisations per
  * sample).  The form for several streams, for index tables, and the one that settles the value table (repeated passes
- * while log10 values are being defined). */
+ * while log10 values are being defined).  Its integer bound stays on the rows: the class records of the tables
+ * (gk_classrows.h) are kept by the pipelined form only. */
 int sample_search_lockstep(gk_ctx* ctx, const std::vector<gk_ctx*>& cx, gk_tab* tab, gk_dptr d_vflag, gk_lut* lut,
                            gk_gene_job* jobs, int32_t n_jobs, const std::vector<int>& live, gk_argsort_fn argsort,
                            gk_log10_fn log10_fn, gk_search** out) {
@@ -888,6 +915,19 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
   // gene i's table, mismatch sums, flag word and column sums (right behind the kernel that wrote the table: it is still
   // in the Infinity Cache), then a mark
   std::vector<uint32_t> sticky((size_t)n_jobs, 0);      // bit 0 of a gene's flag word survives its patches
+  // The class record of a table that was written through its row classes (gk_rowclass.h), per gene: kept across the patch
+  // passes -- rows and drop flags do not change -- and made anew when the table is written in full again.  Weights, plane
+  // counts and the column sums by class are queued behind the table; the counters come back with the table's mark, the
+  // flag word among them (`flag_in_counts`), so the kTable stage builds the pseudo-row table without a wait of its own.
+  struct ClassState {
+    GkClassOf cls;
+    GkClassWeights cw;
+    uint32_t counts[kClassCounters] = {};
+    bool flag_in_counts = false;
+  };
+  std::vector<std::unique_ptr<ClassState>> cstate((size_t)n_jobs);
+  const bool class_route = gk_compat_log_miss_owned && gk_classweights_enqueue && gk_classrows_build &&
+                           gk_use_class_bound && gk_bound_enqueue_classes;
   // A job with a column list (table_cols) writes the tables of those alleles only: everything below works on its
   // n_table_cols COLUMNS -- the kernels, the column sums, the searches on the table -- and allele ordinals are turned
   // into column numbers on their way in (col_of) and back when a search leaves the call (gk_search::to_alleles).  The
@@ -925,6 +965,16 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
         rc = gk_compat_log_miss_narrow(ctx, tab, j.d_rows, j.n_rows, d_vflag, j.vbeg, j.vend, j.d_mask, j.words, j.n_allele, 0,
                                        lut, j.table_cols, j.n_table_cols, j.d_L, j.d_miss8, j.ldm, j.d_flags, j.d_msum);
         summed = true;
+      } else if (class_route && j.n_rows < (int64_t)16000000 && nc <= 65535) {
+        cstate[i].reset(new ClassState());      // the record of a pass before goes back
+        rc = gk_compat_log_miss_owned(ctx, tab, j.d_rows, j.n_rows, d_vflag, j.vbeg, j.vend, j.d_mask, j.words, j.n_allele, 0,
+                                      lut, j.n_table_cols > 0 ? j.table_cols : nullptr, j.n_table_cols, j.d_L, j.d_miss8,
+                                      j.ldm, j.d_flags, &cstate[i]->cls);
+        // a pool that cannot hold the weights is no error: the table keeps what the row route gives it
+        if (rc == GK_OK && (!cstate[i]->cls.class_of ||
+                            gk_classweights_enqueue(ctx, cstate[i]->cls.class_of, j.n_rows, gk_ptr<uint32_t>(j.d_flags),
+                                                    gk_ptr<uint32_t>(j.d_msum), nc, &cstate[i]->cw) != GK_OK))
+          cstate[i].reset();
       } else if (j.n_table_cols > 0)
         rc = gk_compat_log_miss_cols(ctx, tab, j.d_rows, j.n_rows, d_vflag, j.vbeg, j.vend, j.d_mask, j.words, j.n_allele, 0,
                                      lut, j.table_cols, j.n_table_cols, j.d_L, j.d_miss8, j.ldm, j.d_flags);
@@ -932,8 +982,17 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
         rc = gk_compat_log_miss(ctx, tab, j.d_rows, j.n_rows, d_vflag, j.vbeg, j.vend, j.d_mask, j.words, j.n_allele, 0, lut,
                                 j.d_L, j.d_miss8, j.ldm, j.d_flags);
     }
-    if (rc == GK_OK && !summed) rc = gk_miss_colsum(ctx, j.d_miss8, j.ldm, nc, j.d_msum);
-    if (rc == GK_OK && gk_fetch_queue(ctx, &flags[i], gk_ptr<void>(j.d_flags), sizeof(uint32_t)) != hipSuccess) rc = GK_ERR_HIP;
+    ClassState* const cs = cstate[i].get();
+    // a table with a class record gets its column sums at the kTable stage, once it is final: from its pseudo-rows
+    // where the bound takes them (a few per cent of the pass over the rows), from its rows otherwise -- and a table that
+    // is patched on the way is summed once, not once per pass
+    if (rc == GK_OK && !summed && !cs) rc = gk_miss_colsum(ctx, j.d_miss8, j.ldm, nc, j.d_msum);
+    if (cs) cs->flag_in_counts = !patch;
+    if (rc == GK_OK && cs && !patch) {
+      if (gk_fetch_queue(ctx, cs->counts, cs->cw.counts, sizeof(cs->counts)) != hipSuccess) rc = GK_ERR_HIP;
+    } else if (rc == GK_OK && gk_fetch_queue(ctx, &flags[i], gk_ptr<void>(j.d_flags), sizeof(uint32_t)) != hipSuccess) {
+      rc = GK_ERR_HIP;
+    }
     if (rc) return rc;
     std::vector<int32_t> cols((size_t)nc);
     std::iota(cols.begin(), cols.end(), 0);
@@ -987,6 +1046,10 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
     GeneSearch& g = *gs[at];
     switch (it.stage) {
       case kTable: {
+        if (cstate[(size_t)it.gene] && cstate[(size_t)it.gene]->flag_in_counts) {
+          flags[it.gene] = cstate[(size_t)it.gene]->counts[kClassPlanes + 1];
+          cstate[(size_t)it.gene]->flag_in_counts = false;
+        }
         if (flags[it.gene] & 4u) {
           // the kernel met a product without a log10 and left the product in its place (a sample that brings new values):
           // define what is stored by now -- this gene's kernel has completed, so its own keys are -- and patch THIS gene's
@@ -1005,11 +1068,37 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
         j.bound_ok = ((flags[it.gene] | sticky[it.gene]) & 1u) == 0 ? 1 : 0;
         if (!j.bound_ok) g.bound = false;      // a mismatch count near the underflow range / a very long row: exact steps
         g.colsum_collect();
+        const int nc = n_cols_of(it.gene);               // columns of this gene's table
+        std::shared_ptr<const GkClassRows> class_rows;   // the table is final: its pseudo-rows, where they pay
+        if (ClassState* const cs = cstate[(size_t)it.gene].get()) {
+          int64_t blk0[kClassPlanes + 1];
+          const bool bounded_steps = j.n_steps >= 2 || !dependents[(size_t)it.gene].empty();      // somebody runs a bound
+          const int64_t padded = gk_class_planes(cs->counts, blk0);
+          const bool take = j.bound_ok && bounded_steps && gk_use_class_bound(padded, j.n_rows);
+          if (gk_trace("class_bound")) {      // GK_TRACE=class_bound: what the rule saw (tools/class_rows.py)
+            uint64_t pseudo = 0;
+            int top = 0;
+            for (int b = 0; b < kClassPlanes; ++b) { pseudo += cs->counts[b]; if (cs->counts[b]) top = b + 1; }
+            fprintf(stderr, "[class_bound] rows %lld cols %d classes %u pseudo_rows %llu padded %lld weight_bits %d route %s\n",
+                    (long long)j.n_rows, nc, cs->counts[kClassPlanes], (unsigned long long)pseudo, (long long)padded, top,
+                    take ? "classes" : "rows");
+          }
+          if (take) {
+            std::shared_ptr<GkClassRows> made(new GkClassRows());
+            rc = gk_classrows_build(ctx, cs->cw, cs->counts, gk_ptr<uint8_t>(j.d_miss8), j.ldm, nc, gk_ptr<uint32_t>(j.d_msum),
+                                    made.get());
+            if (rc) break;
+            if (made->ready()) class_rows = made;      // else the pool refused it: the searches run on the rows
+          }
+          if (!class_rows) rc = gk_miss_colsum(ctx, j.d_miss8, j.ldm, nc, j.d_msum);      // queued before any bound on the table
+          if (rc) break;
+          cstate[(size_t)it.gene].reset();             // what was queued from it runs before its blocks are used again
+        }
+        g.class_rows = class_rows;
         if (j.n_steps > 0) {
           rc = g.first_step();
           if (rc == GK_OK) rc = advance(it.gene, true);
         }
-        const int nc = n_cols_of(it.gene);               // columns of this gene's table
         std::vector<int> one_set;                        // the dependents whose steps offer one allele each
         for (int d : dependents[(size_t)it.gene]) {      // the table is final: the searches that read it begin
           if (rc) break;
@@ -1042,6 +1131,7 @@ int sample_search_pipelined(gk_ctx* ctx, gk_tab* tab, gk_dptr d_vflag, gk_lut* l
                            every.data(), nc, jd.n_steps, jd.top_n, argsort);
           if (rc) break;
           if (!j.bound_ok) gs[d]->bound = false;
+          gs[d]->class_rows = class_rows;
           gs[d]->S->colsum = g.S->colsum;
           if (jd.n_step_cols > 0) {
             gs[d]->step_cols.resize((size_t)jd.n_step_cols);

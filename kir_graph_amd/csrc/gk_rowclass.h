@@ -19,3 +19,16 @@ int gk_rowclass_enqueue(gk_ctx* ctx, gk_tab* tab, const int32_t* d_rows, int64_t
 int64_t gk_rowclass_ld(int n_cols);
 int gk_rowclass_expand(gk_ctx* ctx, const gk_rowclass* rc, const double* Lc, int64_t ldc, int n_cols, int64_t n_rows,
                        double* L, uint8_t* miss8, int64_t ldm);
+
+// The class record of a table that was written through its row classes, kept beyond the table call: the class of every
+// row.  The rows and the drop flags decide it, so it holds for every later pass over the table's entries.
+struct GkClassOf {
+  uint32_t* class_of = nullptr;     // [n_rows]; null: the table was written row by row
+  int64_t n_rows = 0;
+  GkBlocks blocks;
+};
+// gk_compat_log_miss (table_cols == nullptr) / gk_compat_log_miss_cols with an owner (may be null) for that record
+int gk_compat_log_miss_owned(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag, int32_t vbeg,
+                             int32_t vend, gk_dptr d_mask, int32_t words, int32_t n_allele, int32_t keep_empty, gk_lut* lut,
+                             const int32_t* table_cols, int32_t n_table_cols, gk_dptr d_log, gk_dptr d_miss8, int64_t ldm,
+                             gk_dptr d_flags, GkClassOf* owner);

@@ -716,7 +716,8 @@ template <bool kLog>
 int launch_compat(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag, int vbeg, int vend,
                   gk_dptr d_mask, int words, int n_allele, double* out, uint8_t* miss, uint16_t* nvar, LutView view,
                   int keep_empty, uint8_t* miss8 = nullptr, int64_t ldm = 0, uint32_t* bound_flags = nullptr,
-                  uint16_t* lidx = nullptr, const int32_t* table_cols = nullptr, int n_table_cols = 0) {
+                  uint16_t* lidx = nullptr, const int32_t* table_cols = nullptr, int n_table_cols = 0,
+                  GkClassOf* owner = nullptr) {
   const double empty_p = keep_empty ? 0.999 : 1.0;
   const int words_in = words;
   GkBlocks temps(ctx);
@@ -797,6 +798,13 @@ int launch_compat(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_d
     if (rc) return rc;
   }
   GK_HIP(hipGetLastError());
+  if (by_class && owner) {      // the classes outlive the call: their block changes hands, the scratch around it goes back
+    owner->blocks.begin(ctx);
+    classes.blocks.keep(classes.class_of);
+    owner->blocks.adopt(classes.class_of);
+    owner->class_of = classes.class_of;
+    owner->n_rows = n_rows;
+  }
   return GK_OK;
 }
 
@@ -1249,17 +1257,8 @@ int gk_compat_log(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_d
 int gk_compat_log_miss(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag, int32_t vbeg,
                        int32_t vend, gk_dptr d_mask, int32_t words, int32_t n_allele, int32_t keep_empty, gk_lut* lut,
                        gk_dptr d_log, gk_dptr d_miss8, int64_t ldm, gk_dptr d_flags) {
-  gk_bind(ctx);
-  GK_REQUIRE(ctx && tab && lut, "null pointer");
-  GK_REQUIRE(words >= 1 && n_allele >= 0 && n_allele <= words * 32 && vend >= vbeg, "bad mask geometry");
-  if (n_rows == 0 || n_allele == 0) return GK_OK;
-  GK_REQUIRE(d_log && d_miss8 && d_flags, "null output");
-  GK_REQUIRE(ldm >= n_rows && ldm % 64 == 0, "mismatch table stride must be a multiple of 64 rows");
-  // rows past the end of every column are zero (the workgroup of the last tile writes them), and so is the flag word
-  // before the kernel raises bits in it (launch_compat)
-  return launch_compat<true>(ctx, tab, d_rows, n_rows, d_vflag, vbeg, vend, d_mask, words, n_allele,
-                             gk_ptr<double>(d_log), nullptr, nullptr, gk_lut_view(lut), keep_empty,
-                             gk_ptr<uint8_t>(d_miss8), ldm, gk_ptr<uint32_t>(d_flags));
+  return gk_compat_log_miss_owned(ctx, tab, d_rows, n_rows, d_vflag, vbeg, vend, d_mask, words, n_allele, keep_empty, lut,
+                                  nullptr, 0, d_log, d_miss8, ldm, d_flags, nullptr);
 }
 
 /* gk_compat_log_miss for a LIST of the gene's alleles (exon-first: the candidates' columns of the full model,
@@ -1270,19 +1269,9 @@ int gk_compat_log_miss_cols(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_
                             int32_t vend, gk_dptr d_mask, int32_t words, int32_t n_allele, int32_t keep_empty, gk_lut* lut,
                             const int32_t* table_cols, int32_t n_table_cols, gk_dptr d_log, gk_dptr d_miss8, int64_t ldm,
                             gk_dptr d_flags) {
-  gk_bind(ctx);
-  GK_REQUIRE(ctx && tab && lut, "null pointer");
-  GK_REQUIRE(words >= 1 && n_allele >= 0 && n_allele <= words * 32 && vend >= vbeg, "bad mask geometry");
-  GK_REQUIRE(table_cols && n_table_cols >= 1 && n_table_cols <= n_allele, "bad column list");
-  for (int c = 0; c < n_table_cols; ++c)
-    GK_REQUIRE(table_cols[c] >= 0 && table_cols[c] < n_allele && (c == 0 || table_cols[c] > table_cols[c - 1]),
-               "table columns must be allele ordinals, ascending and unique");
-  if (n_rows == 0) return GK_OK;
-  GK_REQUIRE(d_log && d_miss8 && d_flags, "null output");
-  GK_REQUIRE(ldm >= n_rows && ldm % 64 == 0, "mismatch table stride must be a multiple of 64 rows");
-  return launch_compat<true>(ctx, tab, d_rows, n_rows, d_vflag, vbeg, vend, d_mask, words, n_allele,
-                             gk_ptr<double>(d_log), nullptr, nullptr, gk_lut_view(lut), keep_empty,
-                             gk_ptr<uint8_t>(d_miss8), ldm, gk_ptr<uint32_t>(d_flags), nullptr, table_cols, n_table_cols);
+  GK_REQUIRE(table_cols && n_table_cols >= 1, "bad column list");
+  return gk_compat_log_miss_owned(ctx, tab, d_rows, n_rows, d_vflag, vbeg, vend, d_mask, words, n_allele, keep_empty, lut,
+                                  table_cols, n_table_cols, d_log, d_miss8, ldm, d_flags, nullptr);
 }
 
 /* After gk_compat_log_miss raised bit 2 of *d_flags (and not bit 3) and the value table has been resolved: the entries
@@ -1324,3 +1313,32 @@ int gk_compat_index(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk
 }
 
 }  // extern "C"
+
+// gk_compat_log_miss (table_cols == nullptr) / gk_compat_log_miss_cols with an owner for the class record: when the table
+// was written through its row classes, `owner` (may be null) holds class_of of its rows afterwards -- nothing otherwise
+int gk_compat_log_miss_owned(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows, gk_dptr d_vflag, int32_t vbeg,
+                             int32_t vend, gk_dptr d_mask, int32_t words, int32_t n_allele, int32_t keep_empty, gk_lut* lut,
+                             const int32_t* table_cols, int32_t n_table_cols, gk_dptr d_log, gk_dptr d_miss8, int64_t ldm,
+                             gk_dptr d_flags, GkClassOf* owner) {
+  gk_bind(ctx);
+  if (owner) *owner = GkClassOf();
+  GK_REQUIRE(ctx && tab && lut, "null pointer");
+  GK_REQUIRE(words >= 1 && n_allele >= 0 && n_allele <= words * 32 && vend >= vbeg, "bad mask geometry");
+  if (table_cols) {
+    GK_REQUIRE(n_table_cols >= 1 && n_table_cols <= n_allele, "bad column list");
+    for (int c = 0; c < n_table_cols; ++c)
+      GK_REQUIRE(table_cols[c] >= 0 && table_cols[c] < n_allele && (c == 0 || table_cols[c] > table_cols[c - 1]),
+                 "table columns must be allele ordinals, ascending and unique");
+    if (n_rows == 0) return GK_OK;
+  } else if (n_rows == 0 || n_allele == 0) {
+    return GK_OK;
+  }
+  GK_REQUIRE(d_log && d_miss8 && d_flags, "null output");
+  GK_REQUIRE(ldm >= n_rows && ldm % 64 == 0, "mismatch table stride must be a multiple of 64 rows");
+  // rows past the end of every column are zero (the workgroup of the last tile writes them), and so is the flag word
+  // before the kernel raises bits in it (launch_compat)
+  return launch_compat<true>(ctx, tab, d_rows, n_rows, d_vflag, vbeg, vend, d_mask, words, n_allele,
+                             gk_ptr<double>(d_log), nullptr, nullptr, gk_lut_view(lut), keep_empty,
+                             gk_ptr<uint8_t>(d_miss8), ldm, gk_ptr<uint32_t>(d_flags), nullptr, table_cols,
+                             table_cols ? n_table_cols : 0, owner);
+}
