@@ -610,6 +610,26 @@ int gk_call_swap(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int3
                  uint64_t* gain_out /* [n_table_cols] */, uint64_t* against_out /* [n_table_cols] */, uint64_t* m_out /* [1] */,
                  uint64_t* out_of_range_out /* [1] */, gk_dptr d_state);
 
+/* Copy dosage of a likelihood call (no reference counterpart; extends typing_mulit_allele.py:540-542, 569, whose value
+ * max_{a in S} cannot see copies): the rows of the u8 mismatch table the search left in HBM, collapsed over the called
+ * columns into (pattern, count) pairs in exact integers -- no search runs again.  d_miss8, ldm, n_rows, n_table_cols, cols,
+ * n_cols: as for gk_call_fit.  n_slots: the patterns the call can hold, a power of two in 16 .. 2^24.
+ * Per row r < n_rows, with b_k = d_miss8[cols[k]][r], bytes as stored, and m1 = min_k b_k: m1 == 255 counts the row in
+ *   out_of_range_out[0] (gk_call_fit's bin 17) and in no pattern; otherwise the row's pattern is the bytes d_k = b_k - m1
+ *   (255 where b_k == 255), k < n_cols, zero-extended to 16 -- at least one of them is 0.
+ * patterns_out[i][16], counts_out[i], i < n_out[0] <= n_slots: the distinct patterns and their rows, in any order, no
+ *   pattern twice (equality is decided on the bytes, never on a hash); entries from n_out[0] on are not written.
+ *   unplaced_out[0]: the rows whose pattern found no room; when it is 0 the list is complete.  Always
+ *   sum counts_out + unplaced_out[0] + out_of_range_out[0] == n_rows.  Rows from n_rows to ldm and columns not listed may
+ *   hold anything.
+ * Waits for its result.  GK_ERR_ARG, and nothing launched: n_rows < 1 or >= 2^31, ldm < n_rows or ldm % 64 != 0,
+ * n_table_cols < 1, n_cols outside 1 .. 16, a column outside 0 .. n_table_cols - 1 or listed twice, n_slots no power of two
+ * in 16 .. 2^24, a null pointer, a table that is not 16-byte aligned. */
+int gk_call_patterns(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32_t n_table_cols, const int32_t* cols,
+                     int32_t n_cols, int64_t n_slots, uint8_t* patterns_out /* [n_slots][16] */,
+                     uint64_t* counts_out /* [n_slots] */, int64_t* n_out /* [1] */, uint64_t* out_of_range_out /* [1] */,
+                     uint64_t* unplaced_out /* [1] */);
+
 /* Per-allele coverage of a likelihood call (no reference counterpart; serves what the reference's --plot would draw, "not
  * supported in this build"): WHERE along backbone `gene` the reads lie that the called set explains, in exact integers,
  * from the u8 mismatch table the search left in HBM joined with the sample's records -- no search runs again.

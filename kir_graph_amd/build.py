@@ -12,7 +12,7 @@ SOURCES = ["gk_runtime.hip", "gk_scan.hip", "gk_tabulate.hip", "gk_typing.hip", 
            "gk_search.hip", "gk_bound.hip", "gk_em.hip", "gk_cn.hip", "gk_depth.hip", "gk_sampack.cpp", "gk_bamread.cpp", "gk_textout.cpp",
            "gk_comm.cpp", "gk_hostsearch.cpp", "gk_novel.hip", "gk_boot.hip", "gk_callboot.hip", "gk_compat_narrow.hip",
            "gk_callfit.hip", "gk_callcov.hip", "gk_depthboot.hip", "gk_setsum_few.hip", "gk_rowclass.hip",
-           "gk_callswap.hip", "gk_classrows.hip"]
+           "gk_callswap.hip", "gk_classrows.hip", "gk_calldosage.hip"]
 
 
 def hipcc() -> str:
@@ -71,6 +71,7 @@ KERNEL_SOURCES = {
     "callfit_extra": ["gk_callfit.hip", "gk_common.h"],
     "callswap_rows": ["gk_callswap.hip", "gk_common.h"],
     "callswap_sums": ["gk_callswap.hip", "gk_common.h"],
+    "calldosage_patterns": ["gk_calldosage.hip", "gk_common.h"],
     "callcov_mark": ["gk_callcov.hip", "gk_common.h"],
     "callcov_mark_lds": ["gk_callcov.hip", "gk_common.h"],
     "callcov_finish": ["gk_callcov.hip", "gk_common.h"],

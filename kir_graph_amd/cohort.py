@@ -197,7 +197,7 @@ class SampleTyper:
         self.lanes = sampleLanes() if lanes is None else max(1, lanes)
         self.top_n, self.variant_correction = top_n, variant_correction
         self.finish = finish
-        self.typer_kwargs = typer_kwargs      # further keywords of the strategy (the EM's bootstrap / bootstrap_seed, the likelihood's call_bootstrap*, call_fit*, call_coverage*, call_alternatives*)
+        self.typer_kwargs = typer_kwargs      # further keywords of the strategy (the EM's bootstrap / bootstrap_seed, the likelihood's call_bootstrap*, call_fit*, call_coverage*, call_alternatives*, call_dosage)
         self._pool = ThreadPoolExecutor(max_workers=self.lanes, thread_name_prefix="gk-sample") if self.lanes > 1 else None
         self._free = queue.SimpleQueue()
         for lane in range(self.lanes):

@@ -11,7 +11,8 @@
 //                  instead of compat_rows8), depthw_budget=BYTES (gk_depth_weighted: the bytes a slice of replicates may take,
 //                  so that a few replicates already make several slices), row_classes=on|off (gk_compat_log_miss(_cols):
 //                  the table through the row classes of gk_rowclass.hip, or never), rowclass_hashbits=N (their hash cut to
-//                  N bits: rows of different sequences meet in one slot), class_bound=on|off|nomem (read per call: the integer bound
+//                  N bits: rows of different sequences meet in one slot), calldosage_hashbits=N (gk_call_patterns: the hash
+//                  cut to N bits, so that different keys start their probes in one slot), class_bound=on|off|nomem (read per call: the integer bound
 //                  over the pseudo-rows of the row classes wherever a class record exists, or never; nomem: taken, and the
 //                  pool refuses the pseudo-row table, gk_classrows.h); read by the Python side only:
 //                  bam_reader=samtools, ingest_ahead=N

@@ -24,6 +24,7 @@ from . import _lib
 from ._lib import Device
 from .call_bootstrap import MAX_BOOT, MAX_TOP, CallBootstrap, bootstrapCall, homoFactor
 from .call_coverage import CallCoverage, coverCall
+from .call_dosage import CallDosage, dosageOfCall
 from .call_alternatives import MAX_LISTED, MAX_WITHIN, CallAlternatives, alternativesOfCall
 from .call_fit import MAX_EXTRA, CallFit, fitCall
 from .engine import PreparedGene, PreparedSample, searchMode
@@ -222,7 +223,8 @@ class TypingWithPosNegAllele(_OnLane):
                  device: Device | None = None, call_bootstrap: int = 0, call_bootstrap_seed: int = 2022,
                  call_bootstrap_top: int = 32, call_fit: bool = False, call_fit_extra: int = 3,
                  call_coverage: bool = False, call_coverage_len: dict[str, int] | None = None,
-                 call_alternatives: bool = False, call_alternatives_within: int = 1, call_alternatives_max: int = 20):
+                 call_alternatives: bool = False, call_alternatives_within: int = 1, call_alternatives_max: int = 20,
+                 call_dosage: bool = False):
         """``call_bootstrap`` > 0: every gene's adopted result is rescored in that many read-bootstrap replicates
         (``call_bootstrap.bootstrapCall`` on its first ``call_bootstrap_top`` candidate sets; ``self.call_bootstrap``:
         gene -> ``CallBootstrap``); 0: nothing but the point result, and nothing more is launched.
@@ -235,8 +237,12 @@ class TypingWithPosNegAllele(_OnLane):
         ``call_alternatives``: every gene's adopted result gets the alternatives of each called allele
         (``call_alternatives.alternativesOfCall``: swaps up to ``call_alternatives_within`` mismatches worse count as near,
         ``call_alternatives_max`` are listed per called allele; ``self.call_alternatives``: gene -> ``CallAlternatives``);
-        False: nothing more is launched."""
+        False: nothing more is launched.
+        ``call_dosage``: every gene's adopted result gets the copy dosage of each called allele
+        (``call_dosage.dosageOfCall``; ``self.call_dosage``: gene -> ``CallDosage``); False: nothing more is launched."""
         super().__init__()
+        self._call_dosage = bool(call_dosage)
+        self.call_dosage: dict[str, CallDosage] = {}
         if not 0 <= int(call_alternatives_within) <= MAX_WITHIN:
             raise ValueError(f"call_alternatives_within: the largest delta listed must lie in 0 .. {MAX_WITHIN}")
         if not 1 <= int(call_alternatives_max) <= MAX_LISTED:
@@ -406,6 +412,7 @@ class TypingWithPosNegAllele(_OnLane):
                 self._bootstrapCall(gene, cn, final)
                 self._fitCall(gene, cn, final)
                 self._alternativesCall(gene, cn, final)
+                self._dosageCall(gene, cn, final)
                 self._coverCall(gene, cn, final)
                 yield gene, _calls(gene, final), p["typ_e"].getReadsNum()
         calls = self._collect(entries(), min_reads_num)
@@ -462,6 +469,7 @@ class TypingWithPosNegAllele(_OnLane):
                 self._bootstrapCall(gene, cn, res)
                 self._fitCall(gene, cn, res)
                 self._alternativesCall(gene, cn, res)
+                self._dosageCall(gene, cn, res)
                 self._coverCall(gene, cn, res)
                 yield gene, _calls(gene, res), typ.getReadsNum()
         return self._collect(calls(), min_reads_num)
@@ -528,6 +536,7 @@ class TypingWithPosNegAllele(_OnLane):
         self._bootstrapCall(gene, cn, res)
         self._fitCall(gene, cn, res)
         self._alternativesCall(gene, cn, res)
+        self._dosageCall(gene, cn, res)
         self._coverCall(gene, cn, res)
         return _calls(gene, res), typ.getReadsNum()
 
@@ -559,6 +568,19 @@ class TypingWithPosNegAllele(_OnLane):
         found = alternativesOfCall(result, within, listed, names=self._data.index.tables[g].alleles)
         if found is not None:
             self.call_alternatives[gene] = found
+
+    def _dosageCall(self, gene: str, cn: int, result) -> None:
+        """With ``call_dosage``: the copy dosage of each called allele of the result just adopted for ``gene`` (while the
+        sample's tables are in HBM).  A gene without rows, with a failed result or with ``cn == 0`` gets no entry."""
+        if not self._call_dosage:
+            return
+        self.call_dosage.pop(gene, None)
+        g = self._data.index.gene_id.get(gene)
+        if cn <= 0 or g is None or result is None or result.isFail():
+            return
+        found = dosageOfCall(result, names=self._data.index.tables[g].alleles)
+        if found is not None:
+            self.call_dosage[gene] = found
 
     def _coverCall(self, gene: str, cn: int, result) -> None:
         """With ``call_coverage``: the per-allele coverage of the result just adopted for ``gene`` (while the sample's
@@ -740,6 +762,8 @@ def selectKirTypingModel(method: str, filename_variant_json, **kwargs: Any) -> T
         kwargs.pop("call_alternatives_max", None)
         if kwargs.pop("call_alternatives", False):
             raise ValueError(f"call_alternatives: only the likelihood strategies report the alternatives of a call, not {method!r}")
+        if kwargs.pop("call_dosage", False):
+            raise ValueError(f"call_dosage: only the likelihood strategies report the dosage of a call, not {method!r}")
         kwargs.pop("call_coverage_len", None)
         if kwargs.pop("call_coverage", False):
             raise ValueError(f"call_coverage: only the likelihood strategies report the coverage of a call, not {method!r}")

@@ -294,6 +294,16 @@ def writeCallAlternatives(name: str, calls: dict) -> str:
     return name + ".alternatives.tsv"
 
 
+def writeCallDosage(name: str, dosages: dict) -> str:
+    """``{name}.dosage.tsv`` of one sample typed by a likelihood strategy with ``--call-dosage``: per gene and distinct
+    called allele the copies the reads support, and the best integer compositions at one copy fewer, the called number and
+    one more (``call_dosage.callDosageText``)."""
+    from .call_dosage import callDosageText
+    with open(name + ".dosage.tsv", "w") as f:
+        f.write(callDosageText(dosages))
+    return name + ".dosage.tsv"
+
+
 def writeCallCoverage(name: str, covers: dict, depth: bool = False) -> list[str]:
     """``{name}.coverage.tsv`` of one sample typed by a likelihood strategy with ``--call-coverage``: per gene, region and
     distinct called allele where the reads lie that the called set explains (``call_coverage.callCoverageText``), and with
@@ -329,7 +339,8 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
                 call_bootstrap_top: int = 32, call_fit: bool = False, call_fit_extra: int = 3,
                 call_coverage: bool = False, call_coverage_depth: bool = False,
                 gene_len: dict[str, int] | None = None, call_alternatives: bool = False,
-                call_alternatives_within: int = 1, call_alternatives_max: int = 20) -> "cohort.SampleTyper":
+                call_alternatives_within: int = 1, call_alternatives_max: int = 20,
+                call_dosage: bool = False) -> "cohort.SampleTyper":
     """The typing stage of this process (``cohort.SampleTyper``: the sample lanes, search slots, urgent preamble and
     blocking waits that ``bench.py`` measures), finishing every sample the reference's way: its two files written, its
     tabulation released.  Submit ``(SampleData or hand-off file, copy numbers, (name, cn_file))``.
@@ -347,7 +358,9 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
     ``call_coverage_depth`` (``--call-coverage-depth``) also ``{result}.coverage.depth.tsv``.
     ``call_alternatives`` (``--call-alternatives``, likelihood strategies): the typer reports the alternatives of every
     called allele (``call_alternatives_within``: the largest delta listed as near, ``call_alternatives_max``: alleles listed
-    per called allele), and the finish step writes ``{result}.alternatives.tsv``."""
+    per called allele), and the finish step writes ``{result}.alternatives.tsv``.
+    ``call_dosage`` (``--call-dosage``, likelihood strategies): the typer reports the copy dosage of every called allele,
+    and the finish step writes ``{result}.dosage.tsv``."""
     def finish(typer, called_alleles, warning_genes, item):
         name, cn_file, source = item
         result = name + typingSuffix(name, cn_file, method)
@@ -374,6 +387,8 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
                 writeCallCoverage(result, typer.call_coverage, depth=call_coverage_depth)
             if call_alternatives:
                 writeCallAlternatives(result, typer.call_alternatives)
+            if call_dosage:
+                writeCallDosage(result, typer.call_dosage)
         return written
 
     extra = {"bootstrap": bootstrap, "bootstrap_seed": bootstrap_seed} if bootstrap > 0 else {}
@@ -387,6 +402,8 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
     if call_alternatives:
         extra.update(call_alternatives=True, call_alternatives_within=call_alternatives_within,
                      call_alternatives_max=call_alternatives_max)
+    if call_dosage:
+        extra.update(call_dosage=True)
     return cohort.SampleTyper(method, finish=finish, **extra)
 
 
@@ -499,6 +516,10 @@ def createParser() -> argparse.ArgumentParser:
                    help="The largest number of mismatches a swap may cost and still be listed as near (0 .. 64)")
     p.add_argument("--call-alternatives-max", type=int, default=20,
                    help="Alternatives listed per called allele (1 .. 256); every class is always counted in full")
+    p.add_argument("--call-dosage", action="store_true",
+                   help="Likelihood strategies (full / pv / exonfirst) only: report how many copies of each called allele the "
+                        "reads support (a mixture fit the search's max cannot make) and the best integer compositions at one "
+                        "copy fewer, the called number and one more; writes {result}.dosage.tsv")
     p.add_argument("--call-coverage", action="store_true",
                    help="Likelihood strategies (full / pv / exonfirst) only: report where along every gene the reads lie that "
                         "its called set explains; writes {result}.coverage.tsv (per region -- upstream, exons, introns, "
@@ -559,6 +580,15 @@ def _callAlternativesArgs(args: argparse.Namespace) -> dict:
     return {"call_alternatives": True, "call_alternatives_within": within, "call_alternatives_max": listed}
 
 
+def _callDosageArgs(args: argparse.Namespace) -> dict:
+    """The ``sampleTyper`` keywords of ``--call-dosage`` (none when the flag is not given); the EM strategy is an error."""
+    if not getattr(args, "call_dosage", False):
+        return {}
+    if args.allele_strategy in ("em", "report"):
+        raise ValueError("--call-dosage needs a likelihood strategy (--allele-strategy full, pv or exonfirst)")
+    return {"call_dosage": True}
+
+
 def _callCoverageArgs(args: argparse.Namespace, index_ref: str | None = None) -> dict:
     """The ``sampleTyper`` keywords of ``--call-coverage`` / ``--call-coverage-depth`` (none when neither is given; the
     backbone lengths are read when ``index_ref`` is); the EM strategy is an error."""
@@ -601,6 +631,7 @@ def main(args: argparse.Namespace) -> None:
     _callBootstrapArgs(args)
     _callFitArgs(args)
     _callAlternativesArgs(args)
+    _callDosageArgs(args)
     _callCoverageArgs(args)
     _cnBootstrapArgs(args)
 
@@ -676,7 +707,8 @@ def _runCohort(args, names, reads, cn_files, index, index_ref, cohort_name, comm
     novel = getattr(args, "novel_discovery", False)
     lanes = sampleTyper(method, novel_index=index_ref if novel else None, bootstrap=int(getattr(args, "em_bootstrap", 0) or 0),
                         bootstrap_seed=int(getattr(args, "em_bootstrap_seed", 2022)), **_callBootstrapArgs(args),
-                        **_callFitArgs(args), **_callCoverageArgs(args, index_ref), **_callAlternativesArgs(args))
+                        **_callFitArgs(args), **_callCoverageArgs(args, index_ref), **_callAlternativesArgs(args),
+                        **_callDosageArgs(args))
     try:
         confidence: list | None = [] if _cnBootstrapArgs(args) else None
         allele_files, my_cn = _typeShare(args, lanes, pick(names), pick(reads), my_cn, pick, index, index_ref, cohort_name,
