@@ -67,14 +67,14 @@ KERNEL_SOURCES = {
     "callboot_draw": ["gk_callboot.hip", "gk_common.h"],
     "callboot_sums": ["gk_callboot.hip", "gk_common.h"],
     "callboot_fold": ["gk_callboot.hip", "gk_common.h"],
-    "callfit_profile": ["gk_callfit.hip", "gk_common.h"],
-    "callfit_extra": ["gk_callfit.hip", "gk_common.h"],
-    "callswap_rows": ["gk_callswap.hip", "gk_common.h"],
-    "callswap_sums": ["gk_callswap.hip", "gk_common.h"],
-    "calldosage_patterns": ["gk_calldosage.hip", "gk_common.h"],
-    "callcov_mark": ["gk_callcov.hip", "gk_common.h"],
-    "callcov_mark_lds": ["gk_callcov.hip", "gk_common.h"],
-    "callcov_finish": ["gk_callcov.hip", "gk_common.h"],
+    "callfit_profile": ["gk_callfit.hip", "gk_called.h", "gk_common.h"],
+    "callfit_extra": ["gk_callfit.hip", "gk_called.h", "gk_common.h"],
+    "callswap_rows": ["gk_callswap.hip", "gk_called.h", "gk_common.h"],
+    "callswap_sums": ["gk_callswap.hip", "gk_called.h", "gk_common.h"],
+    "calldosage_patterns": ["gk_calldosage.hip", "gk_called.h", "gk_common.h"],
+    "callcov_mark": ["gk_callcov.hip", "gk_called.h", "gk_common.h"],
+    "callcov_mark_lds": ["gk_callcov.hip", "gk_called.h", "gk_common.h"],
+    "callcov_finish": ["gk_callcov.hip", "gk_called.h", "gk_common.h"],
     "depthw_mark": ["gk_depthboot.hip", "gk_common.h"],
     "depthw_finish": ["gk_depthboot.hip", "gk_common.h"],
     "depthw_select": ["gk_depthboot.hip", "gk_common.h"],

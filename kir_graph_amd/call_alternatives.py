@@ -7,7 +7,7 @@ reads resolve the call -- in exact integers, from the ``u8`` mismatch table ``mi
 (``DeviceModel.missFor``).  With ``M(S) = sum_r min_{a in S} miss[r, a]`` the search's value of a set is
 ``c N - (3 + c) M(S)`` (call_fit.py): one unit of ``delta`` below is about 2.9996 of ``value``.
 
-1. the called row is ``TypingResult.bestRank()``; its distinct alleles, ascending, with their copies;
+1. the called set and its columns of the table (``call_report.calledSet``);
 2. ``gk_call_swap`` (``callswap_rows``, ``callswap_sums``): for every called allele ``k`` and every column ``a`` of the
    table the swap ``S(k -> a)`` that replaces every copy of ``k`` by ``a``: ``loss[k][a]`` / ``rows_for[k][a]`` = the
    mismatches added on, and the number of, the reads that prefer ``k``; ``gain[a]`` / ``rows_against[a]`` = the mismatches
@@ -23,10 +23,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import check, lib
-from .call_bootstrap import modelOf
 from .utils import logger
 
-MAX_CALLED = 16                  # distinct alleles of one gk_call_swap call (include/graphkir_hip.h)
 MAX_WITHIN = 64                  # the largest delta still listed as near
 MAX_LISTED = 256                 # alternatives listed per called allele
 CLASSES = ("better", "identical", "balanced", "near")
@@ -183,33 +181,17 @@ def alternativesOfCall(result, within: int = 1, max_listed: int = 20, names=None
         raise ValueError(f"call alternatives: within must lie in 0 .. {MAX_WITHIN}, got {within}")
     if not 1 <= int(max_listed) <= MAX_LISTED:
         raise ValueError(f"call alternatives: max_listed must lie in 1 .. {MAX_LISTED}, got {max_listed}")
-    model = modelOf(result)
-    if model is None or not model.n_rows:
-        logger.warning("[Allele] call alternatives: the result's sets are not on one device table; skipped")
+    called = calledSet(result, "call alternatives", names)
+    if called is None:
         return None
-    row = int(result.bestRank())
-    called_ids = np.asarray(result.allele_id, dtype=np.int64)[row]
-    called_names = list(result.allele_name[row])
-    ids, first, copies = np.unique(called_ids, return_index=True, return_counts=True)
-    if len(ids) > MAX_CALLED:
-        logger.warning(f"[Allele] call alternatives: {len(ids)} distinct alleles called, more than {MAX_CALLED}; skipped")
-        return None
-    held = model.missFor(ids)
-    if held is None:
-        logger.warning("[Allele] call alternatives: the model has no mismatch table (exact search or 16 M reads or more); "
-                       "skipped")
-        return None
-    name_map = getattr(result.allele_name, "names", None) or names
-    if name_map is None:
+    if called.names is None:
         logger.warning("[Allele] call alternatives: no allele names for the table's columns; skipped")
         return None
-    miss8, ldm, n_table_cols, cols = held
-    n = int(model.n_rows)
-    table_cols = model.tableColumns
-    loss, rows_for, gain, against, m, beyond = swapSums(model.dev, miss8, ldm, n, n_table_cols, cols)
-    return alternativesFromSums(loss, rows_for, gain, against, cols.tolist(), [called_names[int(f)] for f in first], copies,
-                                lambda a: name_map[a if table_cols is None else int(table_cols[a])], int(result.n), n, m,
-                                beyond, "all" if table_cols is None else "candidates", int(within), int(max_listed))
+    cols = called.cols
+    loss, rows_for, gain, against, m, beyond = swapSums(called.model.dev, called.miss8, called.ldm, called.reads,
+                                                        called.n_table_cols, cols)
+    return alternativesFromSums(loss, rows_for, gain, against, cols.tolist(), called.labels, called.copies, called.nameOf,
+                                called.cn, called.reads, m, beyond, called.scope, int(within), int(max_listed))
 
 
 def callAlternativesText(calls: dict[str, CallAlternatives]) -> str:
@@ -224,3 +206,8 @@ def callAlternativesText(calls: dict[str, CallAlternatives]) -> str:
             tails = [[x.allele, x.cls, x.delta, x.loss, x.gain, x.rows_for, x.rows_against] for x in a.listed] or [[""] * 7]
             lines += ["\t".join(str(v) for v in mine + t) for t in tails]
     return CALL_ALTERNATIVES_HEADER + "\n".join(lines) + "\n"
+
+
+# at the end, not at the top: call_report's table of reports names this module, and whichever of the two is imported first
+# finds what it needs of the other already defined
+from .call_report import calledSet  # noqa: E402

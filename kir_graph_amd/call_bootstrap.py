@@ -92,15 +92,6 @@ def homoFactor(result) -> int:
     return 1
 
 
-def modelOf(result):
-    """The one ``DeviceModel`` all parts of ``result.allele_prob`` name (forks of one model do), or None."""
-    parts = getattr(result.allele_prob, "parts", None)
-    if not parts:
-        return None
-    model = parts[0][0]
-    return model if all(m is model for m, _ in parts) else None
-
-
 def weightedScores(model, ids: np.ndarray, n_boot: int, seed: int, stream: int) -> np.ndarray:
     """``sum_r W[b][r] * max_j L[r, ids[t][j]]`` [n_boot, len(ids)] on ``model``'s table: per-read values of a slice of the
     sets (at most 256 sets and ``V_BYTES``), weights of a slice of the replicates (``W_BYTES``), one library call per pair
@@ -167,3 +158,8 @@ def callConfidenceText(bootstrap: dict[str, CallBootstrap]) -> str:
             names = list(boot.alleles[t])
             lines.append("\t".join(cells + names + [""] * (width - len(names))))
     return "\n".join(lines) + "\n"
+
+
+# at the end, not at the top: call_report's table of reports names this module, and whichever of the two is imported first
+# finds what it needs of the other already defined
+from .call_report import modelOf  # noqa: E402

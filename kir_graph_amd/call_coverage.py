@@ -7,7 +7,7 @@ copy with no reads of its own anywhere (one copy too many), the unexplained read
 index does not list) -- in exact integers, from the ``u8`` mismatch table ``miss8[column][read]`` the search left in HBM
 (``DeviceModel.missFor``) joined with the sample's records, which stay in HBM for it.
 
-1. the called row is ``TypingResult.bestRank()``; its distinct alleles, ascending, with their copies;
+1. the called set and its columns of the table (``call_report.calledSet``);
 2. ``gk_call_coverage`` (``callcov_mark``, one scan, ``callcov_finish``): per read ``m1`` = the smallest byte over the
    called columns and ``A`` = the columns that hold it (``--call-fit``'s rule); the read's pair counts, with the M runs of
    both mates as in the depth of the sample, in the tracks ``informative`` (always), ``mismatch`` (``m1 > 0``), ``best_k``
@@ -23,11 +23,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import check, lib
-from .call_bootstrap import modelOf
 from .index import KEY_POS_SHIFT
 from .utils import logger
-
-MAX_CALLED = 16                  # distinct alleles of one gk_call_coverage call (include/graphkir_hip.h)
 
 CALL_COVERAGE_COLUMNS = ["gene", "cn", "reads", "region", "start", "end", "length", "informative_bases", "mismatch_bases",
                          "mismatch_covered", "allele", "copies", "best_bases", "unique_bases", "best_covered",
@@ -141,36 +138,26 @@ def coverCall(result, gene_len: int, exons, table, names=None) -> CallCoverage |
     needed here).  None -- with one warning --
     when the result's sets do not sit on one device table, the model has no mismatch table, more than 16 distinct alleles
     are called, or the sample has no records in HBM (a ``.json`` / CSR hand-off)."""
-    model = modelOf(result)
-    if model is None or not model.n_rows:
-        logger.warning("[Allele] call coverage: the result's sets are not on one device table; skipped")
+    called = calledSet(result, "call coverage", names, table=False)
+    if called is None:
         return None
-    row = int(result.bestRank())
-    called_ids = np.asarray(result.allele_id, dtype=np.int64)[row]
-    called_names = list(result.allele_name[row])
-    ids, first, copies = np.unique(called_ids, return_index=True, return_counts=True)
-    if len(ids) > MAX_CALLED:
-        logger.warning(f"[Allele] call coverage: {len(ids)} distinct alleles called, more than {MAX_CALLED}; skipped")
-        return None
-    tab = model.tab
+    tab = called.model.tab
     mates = getattr(getattr(tab, "_root", tab), "mates", None)
     host = getattr(getattr(tab, "dindex", None), "host", None)
     if mates is None or host is None or not tab.info.d_pair_src:
         logger.warning("[Allele] call coverage: the sample's records are not in HBM (a hand-off file, or released); skipped")
         return None
-    held = model.missFor(ids)
-    if held is None:
-        logger.warning("[Allele] call coverage: the model has no mismatch table (exact search or 16 M reads or more); skipped")
+    called = called.withTable()
+    if called is None:
         return None
-    miss8, ldm, n_table_cols, cols = held
-    n, length = int(model.n_rows), int(gene_len)
-    depth = coverageTracks(tab, mates, model.rows, n, miss8, ldm, n_table_cols, cols, host.gene_id[table.name], length)
+    n, length = called.reads, int(gene_len)
+    depth = coverageTracks(tab, mates, called.model.rows, n, called.miss8, called.ldm, called.n_table_cols, called.cols,
+                           host.gene_id[table.name], length)
     regions = regionsOf(exons, length)
     pos = (host.key[table.vbeg:table.vend] >> np.uint64(KEY_POS_SHIFT)).astype(np.int64) & 0xFFFFFF
-    sites = [np.minimum(pos[rows_k], length - 1) for rows_k in privateSites(table.mask, ids)]
+    sites = [np.minimum(pos[rows_k], length - 1) for rows_k in privateSites(table.mask, called.ids)]
     bases, covered, n_sites, unsupported = summarise(depth, regions, sites)
-    return CallCoverage(cn=int(result.n), reads=n, length=length,
-                        alleles=[(called_names[int(first[j])], int(copies[j])) for j in range(len(ids))], depth=depth,
+    return CallCoverage(cn=called.cn, reads=n, length=length, alleles=list(zip(called.labels, called.copies)), depth=depth,
                         regions=regions, bases=bases, covered=covered, private_sites=n_sites, private_unsupported=unsupported)
 
 
@@ -212,3 +199,8 @@ def callCoverageDepthText(covers: dict[str, CallCoverage]) -> str:
             for a, b, x in depthRuns(d):
                 lines.append(f"{gene}\t{track}\t{allele}\t{a}\t{b}\t{x}")
     return "\n".join(lines) + "\n"
+
+
+# at the end, not at the top: call_report's table of reports names this module, and whichever of the two is imported first
+# finds what it needs of the other already defined
+from .call_report import calledSet  # noqa: E402

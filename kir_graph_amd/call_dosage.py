@@ -11,7 +11,7 @@ mixture model "a read comes from called allele k with share theta_k":
 with ``b_k = miss8[k][r]`` the row's bytes of the ``u8`` mismatch table the search left in HBM (``DeviceModel.missFor``;
 ``p = .999^(n - m) .001^m``) and ``m1`` their minimum.
 
-1. the called row is ``TypingResult.bestRank()``; its distinct alleles, ascending, with their copies;
+1. the called set and its columns of the table (``call_report.calledSet``);
 2. ``gk_call_patterns`` (``calldosage_patterns``, csrc/gk_calldosage.hip) collapses the rows over the called columns into
    (pattern ``d = b - m1``, count) pairs in exact integers; the patterns are sorted, so every float sum below has one order;
 3. ``solveDosage``: plain EM on the patterns from the called shares ``copies / cn`` -- monotone, and it stays on the simplex --
@@ -24,10 +24,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import check, lib
-from .call_bootstrap import modelOf
 from .utils import logger
 
-MAX_CALLED = 16                  # distinct alleles of one gk_call_patterns call (include/graphkir_hip.h)
 FIRST_SLOTS = 4096               # patterns the first call can hold
 MAX_SLOTS = 1 << 21              # ... and the last: 8 times as many per retry
 ITER_MAX = 5000
@@ -237,37 +235,23 @@ def dosageOfCall(result, names=None) -> CallDosage | None:
     accepts it (the called names come from the result itself).  None -- with a warning -- when the result's sets do not sit
     on one device table, the model has no mismatch table, the called set has more than 16 distinct alleles, or the rows take
     more than 2^21 patterns."""
-    model = modelOf(result)
-    if model is None or not model.n_rows:
-        logger.warning("[Allele] call dosage: the result's sets are not on one device table; skipped")
+    called = calledSet(result, "call dosage", names)
+    if called is None:
         return None
-    row = int(result.bestRank())
-    called_ids = np.asarray(result.allele_id, dtype=np.int64)[row]
-    called_names = list(result.allele_name[row])
-    ids, first, copies = np.unique(called_ids, return_index=True, return_counts=True)
-    if len(ids) > MAX_CALLED:
-        logger.warning(f"[Allele] call dosage: {len(ids)} distinct alleles called, more than {MAX_CALLED}; skipped")
-        return None
-    held = model.missFor(ids)
-    if held is None:
-        logger.warning("[Allele] call dosage: the model has no mismatch table (exact search or 16 M reads or more); skipped")
-        return None
-    miss8, ldm, n_table_cols, cols = held
-    n, k, cn = int(model.n_rows), len(ids), int(result.n)
-    found = patternsOfColumns(model.dev, miss8, ldm, n, n_table_cols, cols)
+    n, k, cn, copies = called.reads, len(called.ids), called.cn, called.copies
+    found = patternsOfColumns(called.model.dev, called.miss8, called.ldm, n, called.n_table_cols, called.cols)
     if found is None:
         logger.warning(f"[Allele] call dosage: the reads take more than {MAX_SLOTS} patterns over the called alleles; skipped")
         return None
     patterns, counts, out_of_range = found
-    labels = [called_names[int(first[j])] for j in range(k)]
-    scope = "all" if model.tableColumns is None else "candidates"
+    labels, scope = called.labels, called.scope
     if len(counts) == 0:      # every read out of range: nothing to estimate
-        alleles = [DosageAllele(labels[j], int(copies[j]), None, None) for j in range(k)]
+        alleles = [DosageAllele(labels[j], copies[j], None, None) for j in range(k)]
         return CallDosage(cn=cn, reads=n, out_of_range=out_of_range, patterns=patterns, counts=counts, iterations=None,
                           converged=None, kkt=None, loglik_called=None, loglik_free=None, alleles=alleles, scope=scope)
     sol = solveDosage(patterns, counts, copies)
     tied = tiedColumns(patterns, k)
-    alleles = [DosageAllele(labels[j], int(copies[j]), float(sol.theta[j]), float(sol.theta[j]) * cn,
+    alleles = [DosageAllele(labels[j], copies[j], float(sol.theta[j]), float(sol.theta[j]) * cn,
                             [labels[i] for i in tied[j]]) for j in range(k)]
 
     def named(total):
@@ -311,3 +295,8 @@ def callDosageText(dosages: dict[str, CallDosage]) -> str:
             cells = [_cell(x) for x in head + [a.allele, a.copies, a.share, a.dosage, ",".join(a.tied_with)]] + tail
             lines.append("\t".join(cells))
     return "\n".join(lines) + "\n"
+
+
+# at the end, not at the top: call_report's table of reports names this module, and whichever of the two is imported first
+# finds what it needs of the other already defined
+from .call_report import calledSet  # noqa: E402

@@ -7,7 +7,7 @@ mismatch table ``miss8[column][read]`` the search left in HBM (``DeviceModel.mis
 ``c N - (3 + c) M(S)`` with ``c = log10(.999)``, ``N`` the reads' listed variants and ``M(S) = sum_r min_{a in S} miss[r, a]``
 (csrc/gk_bound.hip; typing_mulit_allele.py:540-542, 569): one mismatching observation is worth about 2.9996 of ``value``.
 
-1. the called row is ``TypingResult.bestRank()``; its distinct alleles, ascending, with their copies;
+1. the called set and its columns of the table (``call_report.calledSet``);
 2. ``gk_call_fit`` (``callfit_profile``): the histogram of the reads' smallest mismatch count ``m1`` over the called
    columns, ``M = sum m1``, per called allele the reads it explains best (ties included), the reads it alone explains best
    and how much ``M`` grows without it; ``d_min[r] = m1``;
@@ -21,10 +21,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import check, lib
-from .call_bootstrap import modelOf
 from .utils import logger
 
-MAX_CALLED = 16                  # distinct alleles of one gk_call_fit call (include/graphkir_hip.h)
 MAX_EXTRA = 64                   # extra alleles listed per gene
 N_BINS = 18                      # m1 == 0 .. 15, 16 .. 254, 255 (out of range)
 
@@ -104,46 +102,30 @@ def fitCall(result, extra: int = 3, names=None) -> CallFit | None:
     sit on one device table, the model has no mismatch table, or the called set has more than 16 distinct alleles."""
     if not 0 <= int(extra) <= MAX_EXTRA:
         raise ValueError(f"call fit: extra must lie in 0 .. {MAX_EXTRA}, got {extra}")
-    model = modelOf(result)
-    if model is None or not model.n_rows:
-        logger.warning("[Allele] call fit: the result's sets are not on one device table; skipped")
+    called = calledSet(result, "call fit", names)
+    if called is None:
         return None
-    row = int(result.bestRank())
-    called_ids = np.asarray(result.allele_id, dtype=np.int64)[row]
-    called_names = list(result.allele_name[row])
-    ids, first, copies = np.unique(called_ids, return_index=True, return_counts=True)
-    if len(ids) > MAX_CALLED:
-        logger.warning(f"[Allele] call fit: {len(ids)} distinct alleles called, more than {MAX_CALLED}; skipped")
-        return None
-    held = model.missFor(ids)
-    if held is None:
-        logger.warning("[Allele] call fit: the model has no mismatch table (exact search or 16 M reads or more); skipped")
-        return None
-    miss8, ldm, n_table_cols, cols = held
-    dev, n = model.dev, int(model.n_rows)
-    extra = int(extra)
-    hist, per_col, m, d_min = profileColumns(dev, miss8, ldm, n, n_table_cols, cols, want_min=extra > 0)
+    dev, n, extra = called.model.dev, called.reads, int(extra)
+    table = (called.miss8, called.ldm, n, called.n_table_cols)
+    hist, per_col, m, d_min = profileColumns(dev, *table, called.cols, want_min=extra > 0)
     listed: list[tuple[str, int]] = []
-    table_cols = model.tableColumns
     try:
         if extra > 0:
-            name_of = getattr(result.allele_name, "names", None) or names
-            with_a = extraSums(dev, miss8, ldm, n, n_table_cols, d_min)
-            for col, gain in largestGains(m - with_a, cols, extra):
-                ordinal = col if table_cols is None else int(table_cols[col])
-                if name_of is None:
+            with_a = extraSums(dev, *table, d_min)
+            for col, gain in largestGains(m - with_a, called.cols, extra):
+                if called.names is None:
                     logger.warning("[Allele] call fit: no allele names for the table's columns; extra alleles not listed")
                     break
-                listed.append((name_of[ordinal], gain))
+                listed.append((called.nameOf(col), gain))
     finally:
         if d_min is not None:
             d_min.free()
-    k = len(ids)
-    alleles = [CalledAllele(allele=called_names[int(first[j])], copies=int(copies[j]), best=int(per_col[j, 0]),
+    k = len(called.ids)
+    alleles = [CalledAllele(allele=called.labels[j], copies=called.copies[j], best=int(per_col[j, 0]),
                             unique=int(per_col[j, 1]), only_explains=int(per_col[j, 2]) if k > 1 else None)
                for j in range(k)]
-    return CallFit(cn=int(result.n), reads=n, hist=hist, mismatches=m, out_of_range=int(hist[17]), alleles=alleles,
-                   extra=listed, extra_scope="all" if table_cols is None else "candidates")
+    return CallFit(cn=called.cn, reads=n, hist=hist, mismatches=m, out_of_range=int(hist[17]), alleles=alleles,
+                   extra=listed, extra_scope=called.scope)
 
 
 def callFitText(fits: dict[str, CallFit]) -> str:
@@ -161,3 +143,8 @@ def callFitText(fits: dict[str, CallFit]) -> str:
             cells = head + [a.allele, a.copies, a.best, a.unique, "" if a.only_explains is None else a.only_explains] + tail
             lines.append("\t".join(str(c) for c in cells))
     return "\n".join(lines) + "\n"
+
+
+# at the end, not at the top: call_report's table of reports names this module, and whichever of the two is imported first
+# finds what it needs of the other already defined
+from .call_report import calledSet  # noqa: E402

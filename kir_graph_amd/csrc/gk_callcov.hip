@@ -40,20 +40,17 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "gk_blocks.h"
+#include "gk_called.h"
 
 namespace {
 
 constexpr int kCovThreads = 256;
-constexpr int kCovMaxCols = 16;
 constexpr int64_t kCovMaxLen = 1ll << 24;                    // a backbone position has 24 bits in a variant key
 constexpr size_t kCovLdsBytes = 144 * 1024;                  // a track's difference array in LDS: gene_len <= 36863
 constexpr int64_t kCovLdsTurns = 16;                         // turns of 256 mates a workgroup of the LDS form takes at least
 constexpr int64_t kCovLdsGroups = 1024;                      // workgroups of the LDS form over all tracks, about
 constexpr int kCovInsWord = offsetof(gk_mate, ins) / 4;      // ins[0] of a record whose pair is in the wide array: its place there
 static_assert(offsetof(gk_mate, cig) == 12 && offsetof(gk_mate, pos0) == 0 && sizeof(gk_mate) == 128, "gk_mate layout");
-
-struct CovCols { int32_t c[kCovMaxCols]; };
 
 struct CovSample {
   const gk_mate* mates;              // the 128-byte records, or
@@ -133,7 +130,7 @@ __device__ inline void cov_walk(const CovSample& s, int64_t row, int side, int g
 // The direct form: one thread per mate marks every track of its row in HBM.
 template <bool kCompact, int KT>
 __global__ __launch_bounds__(kCovThreads) void callcov_mark(CovSample s, const int32_t* __restrict__ rows, int64_t n_rows,
-                                                            const uint8_t* __restrict__ miss8, int64_t ldm, CovCols cols, int K,
+                                                            const uint8_t* __restrict__ miss8, int64_t ldm, GkCalledCols cols, int K,
                                                             int gene, int64_t len, uint32_t* __restrict__ diff) {
   const int64_t t = (int64_t)blockIdx.x * kCovThreads + threadIdx.x;
   if (t >= 2 * n_rows) return;
@@ -161,13 +158,13 @@ __global__ __launch_bounds__(kCovThreads) void callcov_mark(CovSample s, const i
 // of a row are read once per track it counts in.
 template <bool kCompact, int KT>
 __global__ __launch_bounds__(kCovThreads) void callcov_mark_lds(CovSample s, const int32_t* __restrict__ rows, int64_t n_rows,
-                                                                const uint8_t* __restrict__ miss8, int64_t ldm, CovCols cols,
+                                                                const uint8_t* __restrict__ miss8, int64_t ldm, GkCalledCols cols,
                                                                 int K, int gene, int64_t len, uint32_t* __restrict__ diff) {
   extern __shared__ uint32_t lds_diff[];
-  __shared__ int64_t col_off[kCovMaxCols];      // in LDS, not in 32 scalar registers across the loop (they spilled at KT = 16)
+  __shared__ int64_t col_off[kCalledMaxCols];      // in LDS, not in 32 scalar registers across the loop (they spilled at KT = 16)
   const int ld = (int)len + 1;
   const int trk = blockIdx.y;
-  if (threadIdx.x < kCovMaxCols) col_off[threadIdx.x] = (int64_t)cols.c[min((int)threadIdx.x, K - 1)] * ldm;
+  if (threadIdx.x < kCalledMaxCols) col_off[threadIdx.x] = (int64_t)cols.c[min((int)threadIdx.x, K - 1)] * ldm;
   for (int i = threadIdx.x; i < ld; i += kCovThreads) lds_diff[i] = 0;
   __syncthreads();
   const int64_t stride = (int64_t)gridDim.x * kCovThreads;
@@ -218,19 +215,13 @@ int gk_call_coverage(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compac
   GK_REQUIRE(ctx && tab && cols && depth_out && d_rows, "null pointer");
   GK_REQUIRE(tab->d_pair_src, "call coverage needs a tabulation made from packed records");
   GK_REQUIRE((d_mates != 0) != (d_compact != 0), "call coverage needs the sample's records in exactly one form");
-  GK_REQUIRE(d_miss8 && d_miss8 % 16 == 0 && n_rows >= 1 && n_rows < (1ll << 31) && ldm >= n_rows && ldm % 64 == 0 &&
-                 n_table_cols >= 1,
-             "call coverage: needs a 16-byte aligned table, 1 <= n_rows < 2^31 and n_rows <= ldm, a multiple of 64");
-  GK_REQUIRE(n_cols >= 1 && n_cols <= kCovMaxCols, "call coverage: the number of called columns must lie in 1 .. 16");
-  GK_REQUIRE(gene_len >= 1 && gene_len <= kCovMaxLen, "call coverage: gene_len must lie in 1 .. 2^24");
-  GK_REQUIRE(gene >= 0 && gene < 256 && (!tab->idx || gene < tab->idx->n_gene), "call coverage: no such backbone");
-  CovCols cc;
-  for (int k = 0; k < kCovMaxCols; ++k) cc.c[k] = 0;
-  for (int k = 0; k < n_cols; ++k) {
-    GK_REQUIRE(cols[k] >= 0 && cols[k] < n_table_cols, "call coverage: a called column is not in the table");
-    for (int j = 0; j < k; ++j) GK_REQUIRE(cols[j] != cols[k], "call coverage: a called column is listed twice");
-    cc.c[k] = cols[k];
-  }
+  GkCalledCols cc;
+  const int bad = gk_called_cols("call coverage", d_miss8, ldm, n_rows, n_table_cols, cols, n_cols, &cc, [&]() -> int {
+    GK_REQUIRE(gene_len >= 1 && gene_len <= kCovMaxLen, "call coverage: gene_len must lie in 1 .. 2^24");
+    GK_REQUIRE(gene >= 0 && gene < 256 && (!tab->idx || gene < tab->idx->n_gene), "call coverage: no such backbone");
+    return GK_OK;
+  });
+  if (bad) return bad;
   const int64_t n_tracks = 2 + 2 * (int64_t)n_cols;
   const int64_t slots = n_tracks * (gene_len + 1), total = n_tracks * gene_len;
   hipStream_t st = ctx->stream;
@@ -286,11 +277,7 @@ int gk_call_coverage(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compac
     else                      \
       GK_COV_LDS(false, KT);  \
   } while (0)
-      if (n_cols == 1) GK_COV_LAUNCH(1);
-      else if (n_cols == 2) GK_COV_LAUNCH(2);
-      else if (n_cols <= 4) GK_COV_LAUNCH(4);
-      else if (n_cols <= 8) GK_COV_LAUNCH(8);
-      else GK_COV_LAUNCH(16);
+      GK_CALLED_LAUNCH(n_cols, GK_COV_LAUNCH)
 #undef GK_COV_LAUNCH
 #undef GK_COV_LDS
     } else {
@@ -304,11 +291,7 @@ int gk_call_coverage(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compac
       GK_PROF(ctx, "callcov_mark", GK_KERNEL((callcov_mark<false, KT>), grid, block, 0, st, s, rows, n_rows, m, ldm, cc, \
                                              (int)n_cols, (int)gene, gene_len, diff));                                  \
   } while (0)
-      if (n_cols == 1) GK_COV_LAUNCH(1);
-      else if (n_cols == 2) GK_COV_LAUNCH(2);
-      else if (n_cols <= 4) GK_COV_LAUNCH(4);
-      else if (n_cols <= 8) GK_COV_LAUNCH(8);
-      else GK_COV_LAUNCH(16);
+      GK_CALLED_LAUNCH(n_cols, GK_COV_LAUNCH)
 #undef GK_COV_LAUNCH
     }
     if (e == hipSuccess) e = hipGetLastError();

@@ -38,7 +38,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "gk_blocks.h"
+#include "gk_called.h"
 #include "gk_env.h"
 
 namespace {
@@ -47,7 +47,6 @@ constexpr int kPatThreads = 256;
 constexpr int kPatLaneRows = 16;                          // rows of a 16-byte load
 constexpr int kPatChunk = kPatThreads * kPatLaneRows;     // rows of a workgroup per turn (4096)
 constexpr int64_t kPatMaxGroups = 1024;                   // workgroups; they stride over the chunks beyond
-constexpr int kPatMaxCols = 16;
 constexpr int kPatLdsSlots = 1024;                        // patterns (K <= 8) or pairs (K > 8) of a workgroup in LDS
 constexpr uint32_t kPatLdsProbes = 16;                    // slots a key may lie from its start in LDS: a full table costs no more
 constexpr int kPatLdsHalf = 256;                          // low / high halves of a workgroup in LDS (K > 8)
@@ -55,19 +54,11 @@ constexpr unsigned long long kPatEmpty = ~0ull;
 constexpr int kAllFF = 0x7FFFFFFF;                        // the number of a half of eight bytes 255: no slot
 constexpr int64_t kPatMinSlots = 16, kPatMaxSlots = 1ll << 24;
 
-struct PatCols { int32_t c[kPatMaxCols]; };
-
 // the HBM tables: fin[n], lo[n], hi[n] (lo, hi: K > 8 only), counts[n]; counters[0] = unplaced, [1] = out of range
 struct PatGlobal {
   unsigned long long *fin, *lo, *hi, *counts, *counters;
   uint32_t mask;
 };
-
-__device__ inline uint32_t pat_wave_sum(uint32_t x) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-  return x;
-}
 
 __device__ inline uint64_t pat_mix64(uint64_t x) {
   x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
@@ -119,7 +110,7 @@ __device__ inline void pat_add_global(const PatGlobal& g, unsigned long long lo,
 // KT: the columns a lane loads per turn, K <= KT of them listed
 template <int KT>
 __global__ __launch_bounds__(kPatThreads) void calldosage_patterns(const uint8_t* __restrict__ miss8, int64_t ldm,
-                                                                   int64_t n_rows, PatCols cols, int K, uint64_t hash_mask,
+                                                                   int64_t n_rows, GkCalledCols cols, int K, uint64_t hash_mask,
                                                                    PatGlobal g) {
   constexpr bool WIDE = KT > 8;
   constexpr int kWords = KT <= 4 ? 1 : KT / 4;
@@ -206,8 +197,8 @@ __global__ __launch_bounds__(kPatThreads) void calldosage_patterns(const uint8_t
     }
   }
   if (run_n != 0) add(run_lo, run_hi, run_n);
-  zero = pat_wave_sum(zero);
-  oor = pat_wave_sum(oor);
+  zero = wave_sum(zero);
+  oor = wave_sum(oor);
   if ((tid & 63) == 0) {
     if (zero != 0) add(0ull, 0ull, zero);
     if (oor != 0) atomicAdd(&g.counters[1], (unsigned long long)oor);
@@ -239,19 +230,13 @@ int gk_call_patterns(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, 
                      uint64_t* out_of_range_out, uint64_t* unplaced_out) {
   gk_bind(ctx);
   GK_REQUIRE(ctx && cols && patterns_out && counts_out && n_out && out_of_range_out && unplaced_out, "null pointer");
-  GK_REQUIRE(d_miss8 && d_miss8 % 16 == 0 && n_rows >= 1 && n_rows < (1ll << 31) && ldm >= n_rows && ldm % 64 == 0 &&
-                 n_table_cols >= 1,
-             "call patterns: needs a 16-byte aligned table, 1 <= n_rows < 2^31 and n_rows <= ldm, a multiple of 64");
-  GK_REQUIRE(n_cols >= 1 && n_cols <= kPatMaxCols, "call patterns: the number of called columns must lie in 1 .. 16");
-  GK_REQUIRE(n_slots >= kPatMinSlots && n_slots <= kPatMaxSlots && (n_slots & (n_slots - 1)) == 0,
-             "call patterns: the slots must be a power of two in 16 .. 2^24");
-  PatCols pc;
-  for (int k = 0; k < kPatMaxCols; ++k) pc.c[k] = 0;
-  for (int k = 0; k < n_cols; ++k) {
-    GK_REQUIRE(cols[k] >= 0 && cols[k] < n_table_cols, "call patterns: a called column is not in the table");
-    for (int j = 0; j < k; ++j) GK_REQUIRE(cols[j] != cols[k], "call patterns: a called column is listed twice");
-    pc.c[k] = cols[k];
-  }
+  GkCalledCols pc;
+  const int bad = gk_called_cols("call patterns", d_miss8, ldm, n_rows, n_table_cols, cols, n_cols, &pc, [&]() -> int {
+    GK_REQUIRE(n_slots >= kPatMinSlots && n_slots <= kPatMaxSlots && (n_slots & (n_slots - 1)) == 0,
+               "call patterns: the slots must be a power of two in 16 .. 2^24");
+    return GK_OK;
+  });
+  if (bad) return bad;
   // GK_TEST_HOOKS=calldosage_hashbits=N: the hash cut to N bits, so that different keys start their probes in one slot
   const long bits = gk_test_hook_value("calldosage_hashbits", 64);
   const uint64_t hash_mask = bits >= 64 ? ~0ull : bits <= 0 ? 0ull : (1ull << bits) - 1ull;
@@ -276,11 +261,7 @@ int gk_call_patterns(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, 
     const uint8_t* m = gk_ptr<const uint8_t>(d_miss8);
 #define GK_PAT_LAUNCH(KT) \
   GK_PROF(ctx, "calldosage_patterns", GK_KERNEL(calldosage_patterns<KT>, grid, block, 0, st, m, ldm, n_rows, pc, (int)n_cols, hash_mask, g))
-    if (n_cols == 1) GK_PAT_LAUNCH(1);
-    else if (n_cols == 2) GK_PAT_LAUNCH(2);
-    else if (n_cols <= 4) GK_PAT_LAUNCH(4);
-    else if (n_cols <= 8) GK_PAT_LAUNCH(8);
-    else GK_PAT_LAUNCH(16);
+    GK_CALLED_LAUNCH(n_cols, GK_PAT_LAUNCH)
 #undef GK_PAT_LAUNCH
     e = hipGetLastError();
   }

@@ -27,7 +27,7 @@
 // move them together.
 #include <algorithm>
 
-#include "gk_blocks.h"
+#include "gk_called.h"
 
 namespace {
 
@@ -37,30 +37,13 @@ constexpr int kFitLaneRows = 16;                          // rows of a 16-byte l
 constexpr int kFitChunk = kFitThreads * kFitLaneRows;     // rows of a workgroup per turn (4096)
 constexpr int64_t kFitMaxGroups = 2048;                   // workgroups; they stride over the chunks beyond
 constexpr int kFitBins = 18;
-constexpr int kFitMaxCols = 16;
-constexpr int kFitCounters = kFitBins + 1 + 3 * kFitMaxCols;      // hist, M, [column][best, unique, only]
+constexpr int kFitCounters = kFitBins + 1 + 3 * kCalledMaxCols;      // hist, M, [column][best, unique, only]
 constexpr int kExtraCols = 16;                            // columns of a workgroup of callfit_extra
-
-struct FitCols { int32_t c[kFitMaxCols]; };
-
-__device__ inline uint32_t fit_sad4(uint32_t a, uint32_t b, uint32_t acc) { return __builtin_amdgcn_sad_u8(a, b, acc); }
-
-__device__ inline uint32_t wave_sum(uint32_t x) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-  return x;
-}
-
-// the first `n` bytes (rows) of the 16 a lane holds, as masks of its four words
-__device__ inline uint32_t row_mask(int n, int word) {
-  const int k = n - 4 * word;
-  return k >= 4 ? 0xFFFFFFFFu : k <= 0 ? 0u : (1u << (8 * k)) - 1u;
-}
 
 // KT: the columns a lane loads per turn, K <= KT of them listed
 template <int KT>
 __global__ __launch_bounds__(kFitThreads) void callfit_profile(const uint8_t* __restrict__ miss8, int64_t ldm, int64_t n_rows,
-                                                               FitCols cols, int K, unsigned long long* __restrict__ out,
+                                                               GkCalledCols cols, int K, unsigned long long* __restrict__ out,
                                                                uint8_t* __restrict__ d_min) {
   constexpr int kLane = 2 + 3 * KT;      // a lane's counters: bin 0, M, best / unique / only of KT columns
   __shared__ uint32_t lds_hist[kFitBins];
@@ -218,7 +201,7 @@ __global__ __launch_bounds__(kFitThreads) void callfit_extra(const uint8_t* __re
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       keep[q] = row_mask(nv, q);
-      dsum = fit_sad4(d[q], 0, dsum);
+      dsum = sad4(d[q], 0, dsum);
     }
 #pragma unroll
     for (int j = 0; j < kExtraCols; ++j) {
@@ -226,8 +209,8 @@ __global__ __launch_bounds__(kFitThreads) void callfit_extra(const uint8_t* __re
       uint32_t plus = dsum, minus = 0;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        plus = fit_sad4(xw[q], 0, plus);
-        minus = fit_sad4(xw[q], d[q], minus);
+        plus = sad4(xw[q], 0, plus);
+        minus = sad4(xw[q], d[q], minus);
       }
       twice[j] += plus - minus;
     }
@@ -248,11 +231,6 @@ __global__ __launch_bounds__(kFitThreads) void callfit_extra(const uint8_t* __re
   }
 }
 
-bool fit_table_ok(gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32_t n_table_cols) {
-  return d_miss8 && d_miss8 % 16 == 0 && n_rows >= 1 && n_rows < (1ll << 31) && ldm >= n_rows && ldm % 64 == 0 &&
-         n_table_cols >= 1;
-}
-
 }  // namespace
 
 extern "C" {
@@ -262,17 +240,12 @@ int gk_call_fit(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32
                 int32_t n_cols, uint64_t* hist_out, uint64_t* col_out, uint64_t* m_out, gk_dptr d_min) {
   gk_bind(ctx);
   GK_REQUIRE(ctx && cols && hist_out && col_out && m_out, "null pointer");
-  GK_REQUIRE(fit_table_ok(d_miss8, ldm, n_rows, n_table_cols),
-             "call fit: needs a 16-byte aligned table, 1 <= n_rows < 2^31 and n_rows <= ldm, a multiple of 64");
-  GK_REQUIRE(n_cols >= 1 && n_cols <= kFitMaxCols, "call fit: the number of called columns must lie in 1 .. 16");
-  GK_REQUIRE(d_min % 16 == 0, "call fit: d_min must be 16-byte aligned");
-  FitCols fc;
-  for (int k = 0; k < kFitMaxCols; ++k) fc.c[k] = 0;
-  for (int k = 0; k < n_cols; ++k) {
-    GK_REQUIRE(cols[k] >= 0 && cols[k] < n_table_cols, "call fit: a called column is not in the table");
-    for (int j = 0; j < k; ++j) GK_REQUIRE(cols[j] != cols[k], "call fit: a called column is listed twice");
-    fc.c[k] = cols[k];
-  }
+  GkCalledCols fc;
+  const int bad = gk_called_cols("call fit", d_miss8, ldm, n_rows, n_table_cols, cols, n_cols, &fc, [&]() -> int {
+    GK_REQUIRE(d_min % 16 == 0, "call fit: d_min must be 16-byte aligned");
+    return GK_OK;
+  });
+  if (bad) return bad;
   hipStream_t st = ctx->stream;
   GkBlocks temps(ctx);
   unsigned long long* d_out = nullptr;
@@ -288,11 +261,7 @@ int gk_call_fit(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32
     uint8_t* dm = gk_ptr<uint8_t>(d_min);
 #define GK_FIT_LAUNCH(KT) \
   GK_PROF(ctx, "callfit_profile", GK_KERNEL(callfit_profile<KT>, grid, block, 0, st, m, ldm, n_rows, fc, (int)n_cols, d_out, dm))
-    if (n_cols == 1) GK_FIT_LAUNCH(1);
-    else if (n_cols == 2) GK_FIT_LAUNCH(2);
-    else if (n_cols <= 4) GK_FIT_LAUNCH(4);
-    else if (n_cols <= 8) GK_FIT_LAUNCH(8);
-    else GK_FIT_LAUNCH(16);
+    GK_CALLED_LAUNCH(n_cols, GK_FIT_LAUNCH)
 #undef GK_FIT_LAUNCH
     e = hipGetLastError();
   }
@@ -314,7 +283,7 @@ int gk_call_fit_extra(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows,
                       uint64_t* with_out) {
   gk_bind(ctx);
   GK_REQUIRE(ctx && d_min && with_out, "null pointer");
-  GK_REQUIRE(fit_table_ok(d_miss8, ldm, n_rows, n_table_cols),
+  GK_REQUIRE(gk_called_table_ok(d_miss8, ldm, n_rows, n_table_cols),
              "call fit: needs a 16-byte aligned table, 1 <= n_rows < 2^31 and n_rows <= ldm, a multiple of 64");
   GK_REQUIRE(d_min % 16 == 0, "call fit: d_min must be 16-byte aligned");
   const int64_t chunks = (n_rows + kFitChunk - 1) / kFitChunk;

@@ -36,7 +36,7 @@
 // tiles 32 / KT (16, 16, 8, 4, 2 columns for KT = 1, 2, 4, 8, 16): move them together.
 #include <algorithm>
 
-#include "gk_blocks.h"
+#include "gk_called.h"
 
 namespace {
 
@@ -46,35 +46,19 @@ constexpr int kSwapLaneRows = 16;                          // rows of a 16-byte 
 constexpr int kSwapChunk = kSwapThreads * kSwapLaneRows;   // rows of a workgroup per turn (4096)
 constexpr int64_t kSwapMaxGroups = 2048;                   // workgroups; they stride over the chunks beyond
 constexpr int64_t kSwapMaxTurns = (1ll << 31) / kSwapChunk / kSwapMaxGroups;      // 256: the turns of a lane
-constexpr int kSwapMaxCols = 16;
 constexpr int kSwapNone = 255;                             // own: no unique holder
-
-struct SwapCols { int32_t c[kSwapMaxCols]; };
 
 // columns of a workgroup of callswap_sums
 constexpr int swapTile(int KT) { return 32 / KT < 16 ? 32 / KT : 16; }
 
 typedef unsigned short swap_u16x2 __attribute__((ext_vector_type(2)));
 
-__device__ inline uint32_t swap_sad4(uint32_t a, uint32_t b, uint32_t acc) { return __builtin_amdgcn_sad_u8(a, b, acc); }
 // per 16-bit half: max(0, a - b) and min(a, b)
 __device__ inline uint32_t swap_subsat(uint32_t a, uint32_t b) {
   return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(swap_u16x2, a), __builtin_bit_cast(swap_u16x2, b)));
 }
 __device__ inline uint32_t swap_min(uint32_t a, uint32_t b) {
   return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(swap_u16x2, a), __builtin_bit_cast(swap_u16x2, b)));
-}
-
-__device__ inline uint32_t swap_wave_sum(uint32_t x) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-  return x;
-}
-
-// the first `n` bytes (rows) of the 16 a lane holds, as masks of its four words
-__device__ inline uint32_t swap_row_mask(int n, int word) {
-  const int k = n - 4 * word;
-  return k >= 4 ? 0xFFFFFFFFu : k <= 0 ? 0u : (1u << (8 * k)) - 1u;
 }
 
 // 0xFF in every byte of `w` that equals `k`
@@ -87,7 +71,7 @@ __device__ inline uint32_t swap_bytes_equal(uint32_t w, uint32_t k) {
 // KT: the columns a lane loads per turn, K <= KT of them listed.  state: m1 [ld], m2 [ld], own [ld]
 template <int KT>
 __global__ __launch_bounds__(kSwapThreads) void callswap_rows(const uint8_t* __restrict__ miss8, int64_t ldm, int64_t n_rows,
-                                                              SwapCols cols, int K, uint8_t* __restrict__ state, int64_t ld,
+                                                              GkCalledCols cols, int K, uint8_t* __restrict__ state, int64_t ld,
                                                               unsigned long long* __restrict__ out) {
   __shared__ uint32_t wave_part[kSwapWaves][2];
   __shared__ int64_t col_at[KT];      // in LDS: as 32 scalar registers live across the loop they spilled at 16 columns
@@ -164,8 +148,8 @@ __global__ __launch_bounds__(kSwapThreads) void callswap_rows(const uint8_t* __r
   }
 
   const int wave = tid >> 6, lane = tid & 63;
-  msum = swap_wave_sum(msum);
-  beyond = swap_wave_sum(beyond);
+  msum = wave_sum(msum);
+  beyond = wave_sum(beyond);
   if (lane == 0) {
     wave_part[wave][0] = msum;
     wave_part[wave][1] = beyond;
@@ -221,7 +205,7 @@ __global__ __launch_bounds__(kSwapThreads) void callswap_sums(const uint8_t* __r
     uint32_t m1e[4], m1o[4], m2e[4], m2o[4], mine[KT][4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const uint32_t keep = swap_row_mask(nv, q);
+      const uint32_t keep = row_mask(nv, q);
       m1e[q] = m1w[q] & keep & 0x00FF00FFu;
       m1o[q] = m1w[q] & keep & 0xFF00FF00u;
       m2e[q] = m2w[q] & keep & 0x00FF00FFu;
@@ -238,14 +222,14 @@ __global__ __launch_bounds__(kSwapThreads) void callswap_sums(const uint8_t* __r
         const uint32_t xe = xw[q] & 0x00FF00FFu, xo = xw[q] & 0xFF00FF00u;
         const uint32_t ge = swap_subsat(m1e[q], xe), go = swap_subsat(m1o[q], xo);                       // m1 -sat x
         const uint32_t ce = swap_subsat(swap_min(xe, m2e[q]), m1e[q]), co = swap_subsat(swap_min(xo, m2o[q]), m1o[q]);
-        gain[j] = swap_sad4(ge | go, 0, gain[j]);
-        against[j] = swap_sad4(swap_min(ge, 0x00010001u) | swap_min(go, 0x01000100u), 0, against[j]);
+        gain[j] = sad4(ge | go, 0, gain[j]);
+        against[j] = sad4(swap_min(ge, 0x00010001u) | swap_min(go, 0x01000100u), 0, against[j]);
         const uint32_t c = ce | co;                                                                      // min(x, m2) -sat m1
         const uint32_t g = swap_min(ce, 0x00010001u) | swap_min(co, 0x01000100u);
 #pragma unroll
         for (int k = 0; k < KT; ++k) {
-          loss[k][j] = swap_sad4(c & mine[k][q], 0, loss[k][j]);
-          rows_for[k][j] = swap_sad4(g & mine[k][q], 0, rows_for[k][j]);
+          loss[k][j] = sad4(c & mine[k][q], 0, loss[k][j]);
+          rows_for[k][j] = sad4(g & mine[k][q], 0, rows_for[k][j]);
         }
       }
     }
@@ -254,14 +238,14 @@ __global__ __launch_bounds__(kSwapThreads) void callswap_sums(const uint8_t* __r
   const int wave = tid >> 6, lane = tid & 63;
 #pragma unroll
   for (int j = 0; j < T; ++j) {
-    const uint32_t a = swap_wave_sum(gain[j]), b = swap_wave_sum(against[j]);
+    const uint32_t a = wave_sum(gain[j]), b = wave_sum(against[j]);
     if (lane == 0) {
       wave_part[wave][j] = a;
       wave_part[wave][T + j] = b;
     }
 #pragma unroll
     for (int k = 0; k < KT; ++k) {
-      const uint32_t c = swap_wave_sum(loss[k][j]), d = swap_wave_sum(rows_for[k][j]);
+      const uint32_t c = wave_sum(loss[k][j]), d = wave_sum(rows_for[k][j]);
       if (lane == 0) {
         wave_part[wave][2 * T + k * T + j] = c;
         wave_part[wave][2 * T + KT * T + k * T + j] = d;
@@ -291,19 +275,13 @@ int gk_call_swap(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int3
                  uint64_t* m_out, uint64_t* out_of_range_out, gk_dptr d_state) {
   gk_bind(ctx);
   GK_REQUIRE(ctx && cols && loss_out && for_out && gain_out && against_out && m_out && out_of_range_out, "null pointer");
-  GK_REQUIRE(d_miss8 && d_miss8 % 16 == 0 && n_rows >= 1 && n_rows < (1ll << 31) && ldm >= n_rows && ldm % 64 == 0 &&
-                 n_table_cols >= 1,
-             "call swap: needs a 16-byte aligned table, 1 <= n_rows < 2^31 and n_rows <= ldm, a multiple of 64");
-  GK_REQUIRE(n_cols >= 1 && n_cols <= kSwapMaxCols, "call swap: the number of called columns must lie in 1 .. 16");
-  GK_REQUIRE(d_state % 16 == 0, "call swap: d_state must be 16-byte aligned");
-  SwapCols sc;
-  for (int k = 0; k < kSwapMaxCols; ++k) sc.c[k] = 0;
-  for (int k = 0; k < n_cols; ++k) {
-    GK_REQUIRE(cols[k] >= 0 && cols[k] < n_table_cols, "call swap: a called column is not in the table");
-    for (int j = 0; j < k; ++j) GK_REQUIRE(cols[j] != cols[k], "call swap: a called column is listed twice");
-    sc.c[k] = cols[k];
-  }
-  const int kt = n_cols == 1 ? 1 : n_cols == 2 ? 2 : n_cols <= 4 ? 4 : n_cols <= 8 ? 8 : 16;
+  GkCalledCols sc;
+  const int bad = gk_called_cols("call swap", d_miss8, ldm, n_rows, n_table_cols, cols, n_cols, &sc, [&]() -> int {
+    GK_REQUIRE(d_state % 16 == 0, "call swap: d_state must be 16-byte aligned");
+    return GK_OK;
+  });
+  if (bad) return bad;
+  const int kt = calledKT(n_cols);
   const int64_t chunks = (n_rows + kSwapChunk - 1) / kSwapChunk;
   const int64_t n_tiles = ((int64_t)n_table_cols + swapTile(kt) - 1) / swapTile(kt);
   // enough slices to fill the GPU, and never more than kSwapMaxTurns turns for a lane
@@ -337,11 +315,7 @@ int gk_call_swap(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int3
             GK_KERNEL(callswap_sums<KT>, grid_sums, block, 0, st, m, ldm, n_rows, (int)n_table_cols, (const uint8_t*)state, \
                       ldm, (int)n_cols, (int)n_tiles, (int)n_slices, d_out + 2));                                            \
   } while (0)
-    if (kt == 1) GK_SWAP_LAUNCH(1);
-    else if (kt == 2) GK_SWAP_LAUNCH(2);
-    else if (kt == 4) GK_SWAP_LAUNCH(4);
-    else if (kt == 8) GK_SWAP_LAUNCH(8);
-    else GK_SWAP_LAUNCH(16);
+    GK_CALLED_LAUNCH(n_cols, GK_SWAP_LAUNCH)
 #undef GK_SWAP_LAUNCH
     e = hipGetLastError();
   }

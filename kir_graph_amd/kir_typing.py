@@ -22,11 +22,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Device
-from .call_bootstrap import MAX_BOOT, MAX_TOP, CallBootstrap, bootstrapCall, homoFactor
-from .call_coverage import CallCoverage, coverCall
-from .call_dosage import CallDosage, dosageOfCall
-from .call_alternatives import MAX_LISTED, MAX_WITHIN, CallAlternatives, alternativesOfCall
-from .call_fit import MAX_EXTRA, CallFit, fitCall
+from .call_report import CALL_REPORTS
 from .engine import PreparedGene, PreparedSample, searchMode
 from .hisat2 import SampleData, loadCompact, loadReadsAndVariantsData
 from .typing_em import (EmBootstrap, Hisat2AlleleResult, bootstrapEM, callsByAbundance, candidateSetsDistinct,
@@ -220,49 +216,20 @@ class TypingWithPosNegAllele(_OnLane):
 
     def __init__(self, filename_variant_json, top_n: int = 300, multiple: bool = False, exon_first: bool = False,
                  exon_only: bool = False, exon_candidate_threshold: float = .9, variant_correction: bool = False,
-                 device: Device | None = None, call_bootstrap: int = 0, call_bootstrap_seed: int = 2022,
-                 call_bootstrap_top: int = 32, call_fit: bool = False, call_fit_extra: int = 3,
-                 call_coverage: bool = False, call_coverage_len: dict[str, int] | None = None,
-                 call_alternatives: bool = False, call_alternatives_within: int = 1, call_alternatives_max: int = 20,
-                 call_dosage: bool = False):
-        """``call_bootstrap`` > 0: every gene's adopted result is rescored in that many read-bootstrap replicates
-        (``call_bootstrap.bootstrapCall`` on its first ``call_bootstrap_top`` candidate sets; ``self.call_bootstrap``:
-        gene -> ``CallBootstrap``); 0: nothing but the point result, and nothing more is launched.
-        ``call_fit``: every gene's adopted result gets its fit report (``call_fit.fitCall`` with ``call_fit_extra`` extra
-        alleles listed; ``self.call_fit``: gene -> ``CallFit``); False: nothing more is launched.
-        ``call_coverage``: every gene's adopted result gets its per-allele coverage (``call_coverage.coverCall``;
-        ``self.call_coverage``: gene -> ``CallCoverage``, None for a gene whose report could not be made);
-        ``call_coverage_len``: gene -> backbone length, needed with it.  The sample's records must still be in HBM
-        (``tab.mates``).  False: nothing more is launched.
-        ``call_alternatives``: every gene's adopted result gets the alternatives of each called allele
-        (``call_alternatives.alternativesOfCall``: swaps up to ``call_alternatives_within`` mismatches worse count as near,
-        ``call_alternatives_max`` are listed per called allele; ``self.call_alternatives``: gene -> ``CallAlternatives``);
-        False: nothing more is launched.
-        ``call_dosage``: every gene's adopted result gets the copy dosage of each called allele
-        (``call_dosage.dosageOfCall``; ``self.call_dosage``: gene -> ``CallDosage``); False: nothing more is launched."""
+                 device: Device | None = None, **call_options):
+        """``call_options``: the keywords of the per-call reports (``call_report.CALL_REPORTS``: ``call_bootstrap`` > 0,
+        ``call_fit``, ``call_alternatives``, ``call_dosage``, ``call_coverage`` and their options).  A report that is
+        switched on is made of every gene's adopted result while the sample's tables are in HBM, and kept in the
+        attribute of its name: ``self.call_fit``: gene -> ``CallFit``, and so on; a gene without rows, with a failed
+        result or with ``cn == 0`` gets no entry.  Switched off: nothing more is launched.  ``call_coverage`` needs
+        ``call_coverage_len``, gene -> backbone length, and the sample's records still in HBM (``tab.mates``); a gene
+        whose coverage could not be made gets None."""
         super().__init__()
-        self._call_dosage = bool(call_dosage)
-        self.call_dosage: dict[str, CallDosage] = {}
-        if not 0 <= int(call_alternatives_within) <= MAX_WITHIN:
-            raise ValueError(f"call_alternatives_within: the largest delta listed must lie in 0 .. {MAX_WITHIN}")
-        if not 1 <= int(call_alternatives_max) <= MAX_LISTED:
-            raise ValueError(f"call_alternatives_max: the alternatives listed per allele must lie in 1 .. {MAX_LISTED}")
-        self._call_alternatives = (bool(call_alternatives), int(call_alternatives_within), int(call_alternatives_max))
-        self.call_alternatives: dict[str, CallAlternatives] = {}
-        if call_coverage and not call_coverage_len:
-            raise ValueError("call_coverage: needs call_coverage_len, the backbone length of every gene")
-        self._call_coverage = (bool(call_coverage), dict(call_coverage_len or {}))
-        self.call_coverage: dict[str, CallCoverage | None] = {}
-        if not 0 <= int(call_fit_extra) <= MAX_EXTRA:
-            raise ValueError(f"call_fit_extra: the extra alleles listed must lie in 0 .. {MAX_EXTRA}")
-        self._call_fit = (bool(call_fit), int(call_fit_extra))
-        self.call_fit: dict[str, CallFit] = {}
-        if not 0 <= int(call_bootstrap) <= MAX_BOOT:
-            raise ValueError(f"call_bootstrap: the number of replicates must lie in 0 .. {MAX_BOOT}")
-        if not 1 <= int(call_bootstrap_top) <= MAX_TOP:
-            raise ValueError(f"call_bootstrap_top: the candidate sets kept must lie in 1 .. {MAX_TOP}")
-        self._call_boot = (int(call_bootstrap), int(call_bootstrap_seed), int(call_bootstrap_top))
-        self.call_bootstrap: dict[str, CallBootstrap] = {}
+        self._call_options = {report.key: report.typerOptions(call_options) for report in CALL_REPORTS}
+        if call_options:
+            raise TypeError(f"TypingWithPosNegAllele() got an unexpected keyword argument {next(iter(call_options))!r}")
+        for report in CALL_REPORTS:
+            setattr(self, report.key, {})
         self._data = _sample(filename_variant_json, device)
         self._multiple = multiple
         self._top_n = top_n
@@ -409,11 +376,7 @@ class TypingWithPosNegAllele(_OnLane):
                     self._result[gene] = p["typ_e"].result
                 else:
                     self._result[gene], final = p["results"], p["final"]
-                self._bootstrapCall(gene, cn, final)
-                self._fitCall(gene, cn, final)
-                self._alternativesCall(gene, cn, final)
-                self._dosageCall(gene, cn, final)
-                self._coverCall(gene, cn, final)
+                self._reportCall(gene, cn, final)
                 yield gene, _calls(gene, final), p["typ_e"].getReadsNum()
         calls = self._collect(entries(), min_reads_num)
         self._result = {gene: self._result[gene] for gene, _ in todo if gene in self._result}
@@ -466,11 +429,7 @@ class TypingWithPosNegAllele(_OnLane):
                     continue
                 res = typ.result[-1] if job is not None else typ.typing(cn)     # no rows: the reference's empty results
                 self._result[gene] = typ.result
-                self._bootstrapCall(gene, cn, res)
-                self._fitCall(gene, cn, res)
-                self._alternativesCall(gene, cn, res)
-                self._dosageCall(gene, cn, res)
-                self._coverCall(gene, cn, res)
+                self._reportCall(gene, cn, res)
                 yield gene, _calls(gene, res), typ.getReadsNum()
         return self._collect(calls(), min_reads_num)
 
@@ -533,94 +492,23 @@ class TypingWithPosNegAllele(_OnLane):
                              _exon_flags=view.exonFlags(), _group_cache=view.groupCache())
         res = typ.typing(cn)
         self._result[gene] = typ.result
-        self._bootstrapCall(gene, cn, res)
-        self._fitCall(gene, cn, res)
-        self._alternativesCall(gene, cn, res)
-        self._dosageCall(gene, cn, res)
-        self._coverCall(gene, cn, res)
+        self._reportCall(gene, cn, res)
         return _calls(gene, res), typ.getReadsNum()
 
-    def _fitCall(self, gene: str, cn: int, result) -> None:
-        """With ``call_fit``: the fit report of the result just adopted for ``gene`` (while the sample's tables are in
-        HBM).  A gene without rows, with a failed result or with ``cn == 0`` gets no entry."""
-        on, extra = self._call_fit
-        if not on:
-            return
-        self.call_fit.pop(gene, None)
-        g = self._data.index.gene_id.get(gene)
-        if cn <= 0 or g is None or result is None or result.isFail():
-            return
-        fit = fitCall(result, extra, names=self._data.index.tables[g].alleles)
-        if fit is not None:
-            self.call_fit[gene] = fit
-
-    def _alternativesCall(self, gene: str, cn: int, result) -> None:
-        """With ``call_alternatives``: the alternatives of each called allele of the result just adopted for ``gene``
-        (while the sample's tables are in HBM).  A gene without rows, with a failed result or with ``cn == 0`` gets no
-        entry."""
-        on, within, listed = self._call_alternatives
-        if not on:
-            return
-        self.call_alternatives.pop(gene, None)
-        g = self._data.index.gene_id.get(gene)
-        if cn <= 0 or g is None or result is None or result.isFail():
-            return
-        found = alternativesOfCall(result, within, listed, names=self._data.index.tables[g].alleles)
-        if found is not None:
-            self.call_alternatives[gene] = found
-
-    def _dosageCall(self, gene: str, cn: int, result) -> None:
-        """With ``call_dosage``: the copy dosage of each called allele of the result just adopted for ``gene`` (while the
-        sample's tables are in HBM).  A gene without rows, with a failed result or with ``cn == 0`` gets no entry."""
-        if not self._call_dosage:
-            return
-        self.call_dosage.pop(gene, None)
-        g = self._data.index.gene_id.get(gene)
-        if cn <= 0 or g is None or result is None or result.isFail():
-            return
-        found = dosageOfCall(result, names=self._data.index.tables[g].alleles)
-        if found is not None:
-            self.call_dosage[gene] = found
-
-    def _coverCall(self, gene: str, cn: int, result) -> None:
-        """With ``call_coverage``: the per-allele coverage of the result just adopted for ``gene`` (while the sample's
-        tables and records are in HBM).  A gene without rows, with a failed result or with ``cn == 0`` gets no entry; one
-        whose report could not be made (no records in HBM, ...) gets None."""
-        on, lengths = self._call_coverage
-        if not on:
-            return
-        self.call_coverage.pop(gene, None)
-        index = self._data.index
-        g = index.gene_id.get(gene)
-        if cn <= 0 or g is None or result is None or result.isFail():
-            return
-        if gene not in lengths:
-            raise ValueError(f"call_coverage: no backbone length for {gene}")
-        if getattr(self._data.tab, "mates", None) is None:      # a hand-off file, or released: said once per sample
-            if not getattr(self, "_coverage_warned", False):
-                self._coverage_warned = True
-                logger.warning("[Allele] call coverage: the sample's records are not in HBM (a hand-off file, or released); "
-                               "no gene of it is reported")
-            self.call_coverage[gene] = None
-            return
-        self.call_coverage[gene] = coverCall(result, lengths[gene], index.exons.get(gene, []), index.tables[g],
-                                             names=index.tables[g].alleles)
-
-    def _bootstrapCall(self, gene: str, cn: int, result) -> None:
-        """With ``call_bootstrap`` > 0: the read bootstrap of the result just adopted for ``gene`` (while the sample's
-        tables are in HBM), its replicates drawn on the stream numbered like the gene in the index -- so they are the
-        same whichever genes are typed with it, and whichever driver path typed it.  A gene without rows, with a failed
-        result or with ``cn == 0`` gets no entry."""
-        n_boot, seed, top = self._call_boot
-        if n_boot <= 0:
-            return
-        self.call_bootstrap.pop(gene, None)
-        g = self._data.index.gene_id.get(gene)
-        if cn <= 0 or g is None or result is None or result.isFail():
-            return
-        boot = bootstrapCall(result, homoFactor(result), n_boot, seed, g, top)
-        if boot is not None:
-            self.call_bootstrap[gene] = boot
+    def _reportCall(self, gene: str, cn: int, result) -> None:
+        """Every report that is switched on, of the result just adopted for ``gene``, in the order of ``CALL_REPORTS``."""
+        for report in CALL_REPORTS:
+            options = self._call_options[report.key]
+            if not report.switchedOn(options):
+                continue
+            found = getattr(self, report.key)
+            found.pop(gene, None)
+            g = self._data.index.gene_id.get(gene)
+            if cn <= 0 or g is None or result is None or result.isFail():
+                continue
+            entry = report.make(self, gene, g, cn, result, options)
+            if entry is not None or report.keeps_none:
+                found[gene] = entry
 
     def getAllPossibleTyping(self) -> list[dict[Any, Any]]:
         rows = []
@@ -751,22 +639,10 @@ def selectKirTypingModel(method: str, filename_variant_json, **kwargs: Any) -> T
             raise ValueError(f"bootstrap: only the em / report strategy has a read bootstrap, not {method!r}")
     else:
         # ... and the rescoring of candidate sets to the likelihood strategies (the EM has its --em-bootstrap)
-        kwargs.pop("call_bootstrap_seed", None)
-        kwargs.pop("call_bootstrap_top", None)
-        if kwargs.pop("call_bootstrap", 0):
-            raise ValueError(f"call_bootstrap: only the likelihood strategies rescore candidate sets, not {method!r}")
-        kwargs.pop("call_fit_extra", None)
-        if kwargs.pop("call_fit", False):
-            raise ValueError(f"call_fit: only the likelihood strategies report the fit of a call, not {method!r}")
-        kwargs.pop("call_alternatives_within", None)
-        kwargs.pop("call_alternatives_max", None)
-        if kwargs.pop("call_alternatives", False):
-            raise ValueError(f"call_alternatives: only the likelihood strategies report the alternatives of a call, not {method!r}")
-        if kwargs.pop("call_dosage", False):
-            raise ValueError(f"call_dosage: only the likelihood strategies report the dosage of a call, not {method!r}")
-        kwargs.pop("call_coverage_len", None)
-        if kwargs.pop("call_coverage", False):
-            raise ValueError(f"call_coverage: only the likelihood strategies report the coverage of a call, not {method!r}")
+        for report in CALL_REPORTS:
+            given = [kwargs.pop(o.typerName, None) for o in report.options if o.typerName is not None]
+            if given[0]:
+                raise ValueError(f"{report.key}: only the likelihood strategies {report.does}, not {method!r}")
     if method in ("full", "pv"):
         return TypingWithPosNegAllele(filename_variant_json, **kwargs)
     if method.startswith("pv_exonfirst"):

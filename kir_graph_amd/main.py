@@ -28,6 +28,7 @@ import numpy as np
 import pandas as pd
 
 from . import cohort
+from .call_report import CALL_REPORTS, callReport
 from .external_tools import setEngine
 from .hisat2 import (ParkedRecords, SampleData, extractVariant, extractVariantFromPacked, extractVariantFromText,  # noqa: F401
                      packAlignments, readExons, readPair,
@@ -264,60 +265,18 @@ def writeConfidence(name: str, bootstrap: dict) -> str:
     return name + ".confidence.tsv"
 
 
-def writeCallConfidence(name: str, bootstrap: dict) -> str:
-    """``{name}.call_confidence.tsv`` of one sample typed by a likelihood strategy with ``--call-bootstrap``: per
-    candidate set of every gene its point value, the share of replicates it wins and the replicates' mean / 2.5 % /
-    97.5 % distance to the called set (``call_bootstrap.callConfidenceText``)."""
-    from .call_bootstrap import callConfidenceText
-    with open(name + ".call_confidence.tsv", "w") as f:
-        f.write(callConfidenceText(bootstrap))
-    return name + ".call_confidence.tsv"
-
-
-def writeCallFit(name: str, fits: dict) -> str:
-    """``{name}.fit.tsv`` of one sample typed by a likelihood strategy with ``--call-fit``: per gene and distinct called
-    allele how the called set explains the reads, what the allele contributes, and the alleles that would explain the
-    most as one more copy (``call_fit.callFitText``)."""
-    from .call_fit import callFitText
-    with open(name + ".fit.tsv", "w") as f:
-        f.write(callFitText(fits))
-    return name + ".fit.tsv"
-
-
-def writeCallAlternatives(name: str, calls: dict) -> str:
-    """``{name}.alternatives.tsv`` of one sample typed by a likelihood strategy with ``--call-alternatives``: per gene and
-    distinct called allele the alleles that could stand in for it, and the field of its name the reads resolve
-    (``call_alternatives.callAlternativesText``)."""
-    from .call_alternatives import callAlternativesText
-    with open(name + ".alternatives.tsv", "w") as f:
-        f.write(callAlternativesText(calls))
-    return name + ".alternatives.tsv"
-
-
-def writeCallDosage(name: str, dosages: dict) -> str:
-    """``{name}.dosage.tsv`` of one sample typed by a likelihood strategy with ``--call-dosage``: per gene and distinct
-    called allele the copies the reads support, and the best integer compositions at one copy fewer, the called number and
-    one more (``call_dosage.callDosageText``)."""
-    from .call_dosage import callDosageText
-    with open(name + ".dosage.tsv", "w") as f:
-        f.write(callDosageText(dosages))
-    return name + ".dosage.tsv"
-
-
-def writeCallCoverage(name: str, covers: dict, depth: bool = False) -> list[str]:
-    """``{name}.coverage.tsv`` of one sample typed by a likelihood strategy with ``--call-coverage``: per gene, region and
-    distinct called allele where the reads lie that the called set explains (``call_coverage.callCoverageText``), and with
-    ``depth`` (``--call-coverage-depth``) ``{name}.coverage.depth.tsv``: every track as runs of equal depth.  A gene
-    whose report could not be made (None) is left out: a sample without records in HBM gets the headers alone."""
-    from .call_coverage import callCoverageDepthText, callCoverageText
-    covers = {gene: c for gene, c in covers.items() if c is not None}
-    files = [name + ".coverage.tsv"]
-    with open(files[0], "w") as f:
-        f.write(callCoverageText(covers))
-    if depth:
-        files.append(name + ".coverage.depth.tsv")
-        with open(files[1], "w") as f:
-            f.write(callCoverageDepthText(covers))
+def writeCallReport(key: str, name: str, entries: dict, **options) -> list[str]:
+    """The files of the per-call report ``key`` (``call_report.CALL_REPORTS``: ``"call_fit"`` writes ``{name}.fit.tsv``, ...)
+    of one sample typed by a likelihood strategy, from the typer's ``{gene: entry}``; ``options``: the report's keywords
+    (``call_coverage_depth`` asks for ``{name}.coverage.depth.tsv`` as well).  A gene whose report could not be made (None)
+    is left out: a sample without records in HBM gets the headers alone."""
+    entries = {gene: e for gene, e in entries.items() if e is not None}
+    files = []
+    for suffix, text, asked in callReport(key).files:
+        if asked is None or options.get(asked):
+            files.append(name + suffix)
+            with open(files[-1], "w") as f:
+                f.write(text(entries))
     return files
 
 
@@ -335,12 +294,7 @@ def discoverAfterTyping(typer, called_alleles: list[str], name: str, result: str
 
 
 def sampleTyper(method: str, release: bool = True, novel_index: str | None = None, bootstrap: int = 0,
-                bootstrap_seed: int = 2022, call_bootstrap: int = 0, call_bootstrap_seed: int = 2022,
-                call_bootstrap_top: int = 32, call_fit: bool = False, call_fit_extra: int = 3,
-                call_coverage: bool = False, call_coverage_depth: bool = False,
-                gene_len: dict[str, int] | None = None, call_alternatives: bool = False,
-                call_alternatives_within: int = 1, call_alternatives_max: int = 20,
-                call_dosage: bool = False) -> "cohort.SampleTyper":
+                bootstrap_seed: int = 2022, **call_options) -> "cohort.SampleTyper":
     """The typing stage of this process (``cohort.SampleTyper``: the sample lanes, search slots, urgent preamble and
     blocking waits that ``bench.py`` measures), finishing every sample the reference's way: its two files written, its
     tabulation released.  Submit ``(SampleData or hand-off file, copy numbers, (name, cn_file))``.
@@ -348,19 +302,17 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
     (``{result}.novel.*``, typingNovelWrap of the reference's research/kg_main.py) before its tabulation is released.
     ``bootstrap`` > 0 (``--em-bootstrap``, EM strategy): the typer also runs that many read-bootstrap replicates and the
     finish step writes ``{result}.confidence.tsv``.
-    ``call_bootstrap`` > 0 (``--call-bootstrap``, likelihood strategies): the typer rescores every gene's candidate sets
-    in that many read-bootstrap replicates and the finish step writes ``{result}.call_confidence.tsv``.
-    ``call_fit`` (``--call-fit``, likelihood strategies): the typer reports the fit of every gene's called set, with
-    ``call_fit_extra`` extra alleles listed, and the finish step writes ``{result}.fit.tsv``.
-    ``call_coverage`` (``--call-coverage``, likelihood strategies; ``gene_len``: backbone lengths, needed with it): the
-    typer reports the per-allele coverage of every gene's called set from the sample's records, which must still be in
-    HBM (``mapSamples(keep_records=True)``), and the finish step writes ``{result}.coverage.tsv`` -- with
-    ``call_coverage_depth`` (``--call-coverage-depth``) also ``{result}.coverage.depth.tsv``.
-    ``call_alternatives`` (``--call-alternatives``, likelihood strategies): the typer reports the alternatives of every
-    called allele (``call_alternatives_within``: the largest delta listed as near, ``call_alternatives_max``: alleles listed
-    per called allele), and the finish step writes ``{result}.alternatives.tsv``.
-    ``call_dosage`` (``--call-dosage``, likelihood strategies): the typer reports the copy dosage of every called allele,
-    and the finish step writes ``{result}.dosage.tsv``."""
+    ``call_options``: the keywords of the per-call reports of the likelihood strategies (``call_report.CALL_REPORTS``;
+    ``callReportArgs`` makes them from the command line): ``call_bootstrap`` > 0, ``call_fit``, ``call_alternatives``,
+    ``call_dosage``, ``call_coverage`` and their options.  The typer gets the keywords of the reports that are switched
+    on, and the finish step writes their files: ``{result}.call_confidence.tsv``, ``.fit.tsv``, ``.alternatives.tsv``,
+    ``.dosage.tsv``, ``.coverage.tsv`` (with ``call_coverage_depth`` also ``.coverage.depth.tsv``).  ``call_coverage``
+    needs ``gene_len``, the backbone lengths, and the sample's records still in HBM (``mapSamples(keep_records=True)``)."""
+    unknown = set(call_options) - {o.name for report in CALL_REPORTS for o in report.options}
+    if unknown:
+        raise TypeError(f"sampleTyper() got an unexpected keyword argument {sorted(unknown)[0]!r}")
+    reports = [report for report in CALL_REPORTS if report.switchedOn(call_options)]
+
     def finish(typer, called_alleles, warning_genes, item):
         name, cn_file, source = item
         result = name + typingSuffix(name, cn_file, method)
@@ -379,31 +331,13 @@ def sampleTyper(method: str, release: bool = True, novel_index: str | None = Non
             written = writeTyping(result, typer, called_alleles, warning_genes)
             if bootstrap > 0:
                 writeConfidence(result, typer.bootstrap)
-            if call_bootstrap > 0:
-                writeCallConfidence(result, typer.call_bootstrap)
-            if call_fit:
-                writeCallFit(result, typer.call_fit)
-            if call_coverage:
-                writeCallCoverage(result, typer.call_coverage, depth=call_coverage_depth)
-            if call_alternatives:
-                writeCallAlternatives(result, typer.call_alternatives)
-            if call_dosage:
-                writeCallDosage(result, typer.call_dosage)
+            for report in reports:
+                writeCallReport(report.key, result, getattr(typer, report.key), **call_options)
         return written
 
     extra = {"bootstrap": bootstrap, "bootstrap_seed": bootstrap_seed} if bootstrap > 0 else {}
-    if call_bootstrap > 0:
-        extra.update(call_bootstrap=call_bootstrap, call_bootstrap_seed=call_bootstrap_seed,
-                     call_bootstrap_top=call_bootstrap_top)
-    if call_fit:
-        extra.update(call_fit=True, call_fit_extra=call_fit_extra)
-    if call_coverage:
-        extra.update(call_coverage=True, call_coverage_len=gene_len)
-    if call_alternatives:
-        extra.update(call_alternatives=True, call_alternatives_within=call_alternatives_within,
-                     call_alternatives_max=call_alternatives_max)
-    if call_dosage:
-        extra.update(call_dosage=True)
+    for report in reports:
+        extra.update(report.typerKeywords(call_options))
     return cohort.SampleTyper(method, finish=finish, **extra)
 
 
@@ -540,66 +474,14 @@ def createParser() -> argparse.ArgumentParser:
     return p
 
 
-def _callBootstrapArgs(args: argparse.Namespace) -> dict:
-    """The ``sampleTyper`` keywords of ``--call-bootstrap`` (none when the flag is not given); a count that is not
-    positive, a ``--call-bootstrap-top`` outside 1 .. 256 or the EM strategy is an error."""
-    n = getattr(args, "call_bootstrap", None)
-    if n is None:
-        return {}
-    top = int(getattr(args, "call_bootstrap_top", 32))
-    if int(n) <= 0 or int(n) > 10000 or not 1 <= top <= 256 or args.allele_strategy in ("em", "report"):
-        raise ValueError("--call-bootstrap needs a count in 1 .. 10000, a --call-bootstrap-top in 1 .. 256 and a likelihood "
-                         "strategy (--allele-strategy full, pv or exonfirst)")
-    return {"call_bootstrap": int(n), "call_bootstrap_seed": int(getattr(args, "call_bootstrap_seed", 2022)),
-            "call_bootstrap_top": top}
-
-
-def _callFitArgs(args: argparse.Namespace) -> dict:
-    """The ``sampleTyper`` keywords of ``--call-fit`` (none when the flag is not given); a ``--call-fit-extra`` outside
-    0 .. 64 or the EM strategy is an error."""
-    if not getattr(args, "call_fit", False):
-        return {}
-    extra = int(getattr(args, "call_fit_extra", 3))
-    if not 0 <= extra <= 64 or args.allele_strategy in ("em", "report"):
-        raise ValueError("--call-fit needs a --call-fit-extra in 0 .. 64 and a likelihood strategy (--allele-strategy full, "
-                         "pv or exonfirst)")
-    return {"call_fit": True, "call_fit_extra": extra}
-
-
-def _callAlternativesArgs(args: argparse.Namespace) -> dict:
-    """The ``sampleTyper`` keywords of ``--call-alternatives`` (none when the flag is not given); a
-    ``--call-alternatives-within`` outside 0 .. 64, a ``--call-alternatives-max`` outside 1 .. 256 or the EM strategy is an
-    error."""
-    if not getattr(args, "call_alternatives", False):
-        return {}
-    within = int(getattr(args, "call_alternatives_within", 1))
-    listed = int(getattr(args, "call_alternatives_max", 20))
-    if not 0 <= within <= 64 or not 1 <= listed <= 256 or args.allele_strategy in ("em", "report"):
-        raise ValueError("--call-alternatives needs a --call-alternatives-within in 0 .. 64, a --call-alternatives-max in "
-                         "1 .. 256 and a likelihood strategy (--allele-strategy full, pv or exonfirst)")
-    return {"call_alternatives": True, "call_alternatives_within": within, "call_alternatives_max": listed}
-
-
-def _callDosageArgs(args: argparse.Namespace) -> dict:
-    """The ``sampleTyper`` keywords of ``--call-dosage`` (none when the flag is not given); the EM strategy is an error."""
-    if not getattr(args, "call_dosage", False):
-        return {}
-    if args.allele_strategy in ("em", "report"):
-        raise ValueError("--call-dosage needs a likelihood strategy (--allele-strategy full, pv or exonfirst)")
-    return {"call_dosage": True}
-
-
-def _callCoverageArgs(args: argparse.Namespace, index_ref: str | None = None) -> dict:
-    """The ``sampleTyper`` keywords of ``--call-coverage`` / ``--call-coverage-depth`` (none when neither is given; the
-    backbone lengths are read when ``index_ref`` is); the EM strategy is an error."""
-    depth = bool(getattr(args, "call_coverage_depth", False))
-    if not (depth or getattr(args, "call_coverage", False)):
-        return {}
-    if args.allele_strategy in ("em", "report"):
-        raise ValueError("--call-coverage needs a likelihood strategy (--allele-strategy full, pv or exonfirst)")
-    out = {"call_coverage": True, "call_coverage_depth": depth}
-    if index_ref is not None:
-        out["gene_len"] = readLocusLengths(index_ref)
+def callReportArgs(args: argparse.Namespace, index_ref: str | None = None, report: str | None = None) -> dict:
+    """The ``sampleTyper`` keywords of the per-call reports the command line asks for (of the one with the key ``report``,
+    when given); nothing for a report whose flag is not given, whatever its options say.  An option out of its range or the
+    EM strategy is an error.  ``index_ref``: what a report needs of the index is read (``gene_len`` for ``--call-coverage``)."""
+    out: dict = {}
+    for entry in CALL_REPORTS:
+        if report in (None, entry.key):
+            out.update(entry.fromArgs(args, index_ref))
     return out
 
 
@@ -628,11 +510,7 @@ def main(args: argparse.Namespace) -> None:
     n_boot = int(getattr(args, "em_bootstrap", 0) or 0)
     if n_boot < 0 or (n_boot > 0 and args.allele_strategy not in ("em", "report")):
         raise ValueError("--em-bootstrap needs a positive count and --allele-strategy em (or report)")
-    _callBootstrapArgs(args)
-    _callFitArgs(args)
-    _callAlternativesArgs(args)
-    _callDosageArgs(args)
-    _callCoverageArgs(args)
+    callReportArgs(args)
     _cnBootstrapArgs(args)
 
     if not args.input_csv:
@@ -706,13 +584,11 @@ def _runCohort(args, names, reads, cn_files, index, index_ref, cohort_name, comm
     pooled_fit = args.cn_cohort and not all(cn_files)
     novel = getattr(args, "novel_discovery", False)
     lanes = sampleTyper(method, novel_index=index_ref if novel else None, bootstrap=int(getattr(args, "em_bootstrap", 0) or 0),
-                        bootstrap_seed=int(getattr(args, "em_bootstrap_seed", 2022)), **_callBootstrapArgs(args),
-                        **_callFitArgs(args), **_callCoverageArgs(args, index_ref), **_callAlternativesArgs(args),
-                        **_callDosageArgs(args))
+                        bootstrap_seed=int(getattr(args, "em_bootstrap_seed", 2022)), **callReportArgs(args, index_ref))
     try:
         confidence: list | None = [] if _cnBootstrapArgs(args) else None
         allele_files, my_cn = _typeShare(args, lanes, pick(names), pick(reads), my_cn, pick, index, index_ref, cohort_name,
-                                         comm, kwargs, pooled_fit, keep_records=bool(_callCoverageArgs(args)),
+                                         comm, kwargs, pooled_fit, keep_records=bool(callReportArgs(args, report="call_coverage")),
                                          confidence=confidence)
     finally:
         lanes.close()

@@ -137,7 +137,7 @@ def calls():
 
 
 def test_alternatives_file_bytes(tmp_path):
-    path = cli.writeCallAlternatives(str(tmp_path / "s.pv"), calls())
+    [path] = cli.writeCallReport("call_alternatives", str(tmp_path / "s.pv"), calls())
     assert path.endswith("s.pv.alternatives.tsv")
     want = (CALL_ALTERNATIVES_HEADER +
             "gene\tcn\treads\tmismatches\tout_of_range\tscope\tallele\tcopies\tresolved\tn_better\tn_identical\tn_balanced\tn_near\t"
@@ -177,18 +177,18 @@ def test_parser_takes_the_call_alternatives_flags():
     base = ["--step-skip-extraction", "--alignment", "s.sam"]
     args = cli.createParser().parse_args(base)
     assert args.call_alternatives is False and args.call_alternatives_within == 1 and args.call_alternatives_max == 20
-    assert cli._callAlternativesArgs(args) == {}
+    assert cli.callReportArgs(args, report="call_alternatives") == {}
     args = cli.createParser().parse_args(base + ["--allele-strategy", "exonfirst", "--call-alternatives",
                                                  "--call-alternatives-within", "0", "--call-alternatives-max", "256"])
-    assert cli._callAlternativesArgs(args) == {"call_alternatives": True, "call_alternatives_within": 0,
+    assert cli.callReportArgs(args, report="call_alternatives") == {"call_alternatives": True, "call_alternatives_within": 0,
                                                "call_alternatives_max": 256}
     # it combines with the fit report
     args = cli.createParser().parse_args(base + ["--call-alternatives", "--call-fit"])
-    assert cli._callAlternativesArgs(args) == {"call_alternatives": True, "call_alternatives_within": 1, "call_alternatives_max": 20}
-    assert cli._callFitArgs(args) == {"call_fit": True, "call_fit_extra": 3}
+    assert cli.callReportArgs(args, report="call_alternatives") == {"call_alternatives": True, "call_alternatives_within": 1, "call_alternatives_max": 20}
+    assert cli.callReportArgs(args, report="call_fit") == {"call_fit": True, "call_fit_extra": 3}
     # without the flag the ranges alone ask for nothing
     args = cli.createParser().parse_args(base + ["--call-alternatives-within", "65", "--call-alternatives-max", "0"])
-    assert cli._callAlternativesArgs(args) == {}
+    assert cli.callReportArgs(args, report="call_alternatives") == {}
 
 
 @pytest.mark.parametrize("extra", [["--allele-strategy", "em", "--call-alternatives"],

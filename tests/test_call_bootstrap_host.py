@@ -64,7 +64,7 @@ def test_call_confidence_file_bytes(tmp_path):
                                  alleles=[["KIR3DL3*001", "KIR3DL3*001", "KIR3DL3*002"], ["KIR3DL3*001", "KIR3DL3*002", "KIR3DL3*003"],
                                           ["KIR3DL3*004", "KIR3DL3*004", "KIR3DL3*004"]]),
     }
-    path = cli.writeCallConfidence(str(tmp_path / "s.pv"), boot)
+    [path] = cli.writeCallReport("call_bootstrap", str(tmp_path / "s.pv"), boot)
     assert path.endswith("s.pv.call_confidence.tsv")
     want = ("gene\tcn\trank\tcalled\tvalue\tsupport\tdelta_mean\tdelta_q025\tdelta_q975\t1\t2\t3\n"
             "KIR2DL1\t1\t0\t1\t-120.5\t0.75\t0.0\t0.0\t0.0\tKIR2DL1*001\t\t\n"
@@ -82,11 +82,11 @@ def test_parser_takes_the_call_bootstrap_flags():
     base = ["--step-skip-extraction", "--alignment", "s.sam"]
     args = cli.createParser().parse_args(base)
     assert not args.call_bootstrap and args.call_bootstrap_seed == 2022 and args.call_bootstrap_top == 32
-    assert cli._callBootstrapArgs(args) == {}
+    assert cli.callReportArgs(args, report="call_bootstrap") == {}
     args = cli.createParser().parse_args(base + ["--allele-strategy", "exonfirst", "--call-bootstrap", "100",
                                                  "--call-bootstrap-seed", "5", "--call-bootstrap-top", "8"])
     assert (args.call_bootstrap, args.call_bootstrap_seed, args.call_bootstrap_top) == (100, 5, 8)
-    assert cli._callBootstrapArgs(args) == {"call_bootstrap": 100, "call_bootstrap_seed": 5, "call_bootstrap_top": 8}
+    assert cli.callReportArgs(args, report="call_bootstrap") == {"call_bootstrap": 100, "call_bootstrap_seed": 5, "call_bootstrap_top": 8}
 
 
 @pytest.mark.parametrize("extra", [["--allele-strategy", "em", "--call-bootstrap", "8"],

@@ -140,7 +140,7 @@ def covers():
 
 
 def test_coverage_file_bytes(tmp_path):
-    files = cli.writeCallCoverage(str(tmp_path / "s.pv"), covers())
+    files = cli.writeCallReport("call_coverage", str(tmp_path / "s.pv"), covers())
     assert [os.path.basename(f) for f in files] == ["s.pv.coverage.tsv"] and not (tmp_path / "s.pv.coverage.depth.tsv").exists()
     want = ("gene\tcn\treads\tregion\tstart\tend\tlength\tinformative_bases\tmismatch_bases\tmismatch_covered\tallele\tcopies\t"
             "best_bases\tunique_bases\tbest_covered\tunique_covered\tprivate_sites\tprivate_unsupported\n"
@@ -166,13 +166,13 @@ def test_coverage_file_bytes(tmp_path):
     assert cr.coverageText(entries) == want
     # a gene whose report could not be made is left out; nothing at all: the header alone
     assert callCoverageText({}) == "\t".join(CALL_COVERAGE_COLUMNS) + "\n"
-    files = cli.writeCallCoverage(str(tmp_path / "t.pv"), {"KIR2DL2": None, "KIR3DL3": None}, depth=True)
+    files = cli.writeCallReport("call_coverage", str(tmp_path / "t.pv"), {"KIR2DL2": None, "KIR3DL3": None}, call_coverage_depth=True)
     assert open(files[0]).read() == "\t".join(CALL_COVERAGE_COLUMNS) + "\n"
     assert open(files[1]).read() == "\t".join(CALL_COVERAGE_DEPTH_COLUMNS) + "\n"
 
 
 def test_depth_file_runs_tile_the_gene(tmp_path):
-    files = cli.writeCallCoverage(str(tmp_path / "s.pv"), covers(), depth=True)
+    files = cli.writeCallReport("call_coverage", str(tmp_path / "s.pv"), covers(), call_coverage_depth=True)
     assert [os.path.basename(f) for f in files] == ["s.pv.coverage.tsv", "s.pv.coverage.depth.tsv"]
     text = open(files[1]).read()
     assert text == callCoverageDepthText(covers())
@@ -206,16 +206,16 @@ def test_depth_file_runs_tile_the_gene(tmp_path):
 def test_parser_takes_the_call_coverage_flags():
     base = ["--step-skip-extraction", "--alignment", "s.sam"]
     args = cli.createParser().parse_args(base)
-    assert args.call_coverage is False and args.call_coverage_depth is False and cli._callCoverageArgs(args) == {}
+    assert args.call_coverage is False and args.call_coverage_depth is False and cli.callReportArgs(args, report="call_coverage") == {}
     args = cli.createParser().parse_args(base + ["--allele-strategy", "exonfirst", "--call-coverage"])
-    assert cli._callCoverageArgs(args) == {"call_coverage": True, "call_coverage_depth": False}
+    assert cli.callReportArgs(args, report="call_coverage") == {"call_coverage": True, "call_coverage_depth": False}
     # the depth file implies the report
     args = cli.createParser().parse_args(base + ["--call-coverage-depth"])
-    assert cli._callCoverageArgs(args) == {"call_coverage": True, "call_coverage_depth": True}
+    assert cli.callReportArgs(args, report="call_coverage") == {"call_coverage": True, "call_coverage_depth": True}
     # it combines with the fit report and the call bootstrap
     args = cli.createParser().parse_args(base + ["--call-coverage", "--call-fit", "--call-bootstrap", "8"])
-    assert cli._callCoverageArgs(args)["call_coverage"] and cli._callFitArgs(args)["call_fit"]
-    assert cli._callBootstrapArgs(args)["call_bootstrap"] == 8
+    assert cli.callReportArgs(args, report="call_coverage")["call_coverage"] and cli.callReportArgs(args, report="call_fit")["call_fit"]
+    assert cli.callReportArgs(args, report="call_bootstrap")["call_bootstrap"] == 8
 
 
 @pytest.mark.parametrize("extra", [["--allele-strategy", "em", "--call-coverage"],

@@ -216,13 +216,13 @@ def test_sorted_patterns_have_one_order():
 def test_parser_takes_the_call_dosage_flag():
     base = ["--step-skip-extraction", "--alignment", "s.sam"]
     args = cli.createParser().parse_args(base)
-    assert args.call_dosage is False and cli._callDosageArgs(args) == {}
+    assert args.call_dosage is False and cli.callReportArgs(args, report="call_dosage") == {}
     args = cli.createParser().parse_args(base + ["--allele-strategy", "exonfirst", "--call-dosage"])
-    assert cli._callDosageArgs(args) == {"call_dosage": True}
+    assert cli.callReportArgs(args, report="call_dosage") == {"call_dosage": True}
     # it combines with the fit report and the copy-number bootstrap's sibling flags
     args = cli.createParser().parse_args(base + ["--call-dosage", "--call-fit", "--call-alternatives"])
-    assert cli._callDosageArgs(args) == {"call_dosage": True}
-    assert cli._callFitArgs(args) == {"call_fit": True, "call_fit_extra": 3}
+    assert cli.callReportArgs(args, report="call_dosage") == {"call_dosage": True}
+    assert cli.callReportArgs(args, report="call_fit") == {"call_fit": True, "call_fit_extra": 3}
 
 
 @pytest.mark.parametrize("strategy", ["em", "report"])
@@ -247,6 +247,6 @@ def test_factory_refusals():
 def test_write_call_dosage(tmp_path):
     pats = np.array([[0, 255], [255, 0]], dtype=np.uint8)
     entry = entryOf(pats, np.array([20, 10]), [1, 1], ["G*001", "G*002"])
-    path = cli.writeCallDosage(str(tmp_path / "s"), {"G": entry})
+    [path] = cli.writeCallReport("call_dosage", str(tmp_path / "s"), {"G": entry})
     assert path == str(tmp_path / "s") + ".dosage.tsv"
     assert open(path).read() == cd.callDosageText({"G": entry})

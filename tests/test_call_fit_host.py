@@ -73,7 +73,7 @@ def fits():
 
 
 def test_fit_file_bytes(tmp_path):
-    path = cli.writeCallFit(str(tmp_path / "s.pv"), fits())
+    [path] = cli.writeCallReport("call_fit", str(tmp_path / "s.pv"), fits())
     assert path.endswith("s.pv.fit.tsv")
     want = ("gene\tcn\treads\texplained\tmiss1\tmiss2\tmiss3plus\tout_of_range\tmismatches\tallele\tcopies\tbest\tunique\t"
             "only_explains\textra_scope\textra_1\tgain_1\textra_2\tgain_2\n"
@@ -98,16 +98,16 @@ def test_fit_file_of_one_allele_and_without_extras():
 def test_parser_takes_the_call_fit_flags():
     base = ["--step-skip-extraction", "--alignment", "s.sam"]
     args = cli.createParser().parse_args(base)
-    assert args.call_fit is False and args.call_fit_extra == 3 and cli._callFitArgs(args) == {}
+    assert args.call_fit is False and args.call_fit_extra == 3 and cli.callReportArgs(args, report="call_fit") == {}
     args = cli.createParser().parse_args(base + ["--allele-strategy", "exonfirst", "--call-fit", "--call-fit-extra", "0"])
-    assert cli._callFitArgs(args) == {"call_fit": True, "call_fit_extra": 0}
+    assert cli.callReportArgs(args, report="call_fit") == {"call_fit": True, "call_fit_extra": 0}
     # it combines with the call bootstrap
     args = cli.createParser().parse_args(base + ["--call-fit", "--call-bootstrap", "8"])
-    assert cli._callFitArgs(args) == {"call_fit": True, "call_fit_extra": 3}
-    assert cli._callBootstrapArgs(args)["call_bootstrap"] == 8
+    assert cli.callReportArgs(args, report="call_fit") == {"call_fit": True, "call_fit_extra": 3}
+    assert cli.callReportArgs(args, report="call_bootstrap")["call_bootstrap"] == 8
     # without the flag the count alone asks for nothing
     args = cli.createParser().parse_args(base + ["--call-fit-extra", "65"])
-    assert cli._callFitArgs(args) == {}
+    assert cli.callReportArgs(args, report="call_fit") == {}
 
 
 @pytest.mark.parametrize("extra", [["--allele-strategy", "em", "--call-fit"],

@@ -16,7 +16,7 @@ import callswap_reference as sr  # noqa: E402
 
 from kir_graph_amd import _lib, packed, synth  # noqa: E402
 from kir_graph_amd.call_alternatives import CALL_ALTERNATIVES_COLUMNS, CLASSES, alternativesOfCall  # noqa: E402
-from kir_graph_amd.call_bootstrap import modelOf  # noqa: E402
+from kir_graph_amd.call_report import modelOf  # noqa: E402
 from kir_graph_amd.engine import DeviceIndex, Tabulation  # noqa: E402
 from kir_graph_amd.hisat2 import SampleData  # noqa: E402
 from kir_graph_amd.index import GkIndex  # noqa: E402

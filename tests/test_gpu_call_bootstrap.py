@@ -18,8 +18,9 @@ sys.path.insert(0, os.path.dirname(__file__))
 import callboot_reference as cr  # noqa: E402
 
 from kir_graph_amd import _lib, packed, synth  # noqa: E402
-from kir_graph_amd.call_bootstrap import (CALL_CONFIDENCE_COLUMNS, bootstrapCall, homoFactor, modelOf,  # noqa: E402
+from kir_graph_amd.call_bootstrap import (CALL_CONFIDENCE_COLUMNS, bootstrapCall, homoFactor,  # noqa: E402
                                           summariseCall)
+from kir_graph_amd.call_report import modelOf  # noqa: E402
 from kir_graph_amd.engine import DeviceIndex, Tabulation  # noqa: E402
 from kir_graph_amd.hisat2 import SampleData  # noqa: E402
 from kir_graph_amd.kir_typing import TypingWithPosNegAllele, _GeneView  # noqa: E402

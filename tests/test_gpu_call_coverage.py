@@ -18,7 +18,7 @@ import callcov_reference as cr  # noqa: E402
 from test_gpu_call_fit import KINDS, makeTable  # noqa: E402
 
 from kir_graph_amd import _lib, packed, synth  # noqa: E402
-from kir_graph_amd.call_bootstrap import modelOf  # noqa: E402
+from kir_graph_amd.call_report import modelOf  # noqa: E402
 from kir_graph_amd.call_coverage import (CALL_COVERAGE_COLUMNS, CALL_COVERAGE_DEPTH_COLUMNS, callCoverageDepthText,  # noqa: E402
                                          callCoverageText, coverCall, regionsOf)
 from kir_graph_amd.engine import DeviceIndex, Tabulation  # noqa: E402

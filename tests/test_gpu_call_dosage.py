@@ -20,7 +20,7 @@ sys.path.insert(0, os.path.dirname(__file__))
 import dosage_reference as dr  # noqa: E402
 
 from kir_graph_amd import _lib, packed, synth  # noqa: E402
-from kir_graph_amd.call_bootstrap import modelOf  # noqa: E402
+from kir_graph_amd.call_report import modelOf  # noqa: E402
 from kir_graph_amd.call_dosage import (CALL_DOSAGE_COLUMNS, callDosageText, dosageOfCall, patternsOfColumns,  # noqa: E402
                                        sortedPatterns)
 from kir_graph_amd.engine import DeviceIndex, Tabulation  # noqa: E402

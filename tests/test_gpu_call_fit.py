@@ -14,7 +14,8 @@ sys.path.insert(0, os.path.dirname(__file__))
 import callfit_reference as fr  # noqa: E402
 
 from kir_graph_amd import _lib, packed, synth  # noqa: E402
-from kir_graph_amd.call_bootstrap import homoFactor, modelOf  # noqa: E402
+from kir_graph_amd.call_bootstrap import homoFactor  # noqa: E402
+from kir_graph_amd.call_report import modelOf  # noqa: E402
 from kir_graph_amd.call_fit import CALL_FIT_COLUMNS, fitCall  # noqa: E402
 from kir_graph_amd.engine import DeviceIndex, Tabulation  # noqa: E402
 from kir_graph_amd.hisat2 import SampleData  # noqa: E402

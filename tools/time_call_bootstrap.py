@@ -94,7 +94,7 @@ def main() -> None:
 
 
 def modelRows(result) -> int:
-    from kir_graph_amd.call_bootstrap import modelOf
+    from kir_graph_amd.call_report import modelOf
     model = modelOf(result)
     return model.n_rows if model is not None else 0
 

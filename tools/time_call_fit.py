@@ -40,7 +40,7 @@ def main() -> None:
 
     import bench
     from kir_graph_amd import _lib
-    from kir_graph_amd.call_bootstrap import modelOf
+    from kir_graph_amd.call_report import modelOf
     from kir_graph_amd.call_fit import fitCall
     from kir_graph_amd.engine import DeviceIndex, Tabulation
     from kir_graph_amd.hisat2 import SampleData
