@@ -871,16 +871,22 @@ static int bam_open_impl(const char* path, int32_t name_sorted, gk_bam** out) {
   return GK_OK;
 }
 
-// The records, in output order, straight into a packer: same pairing, checks and records as feeding
-// the rendered text to gk_packer_feed, without rendering or re-parsing it.  Only what the packer reads
-// is converted (CIGAR and SEQ to text; NM / MD / Zs / NH from the optional fields).
-static int bam_pack_impl(gk_bam* b, gk_packer* pk) {
-  if (!b || !pk) { gk_set_error("null handle"); return GK_ERR_ARG; }
+}  // extern "C"
+
+// The records of an open file as the packer reads them (gk_ingest.h: GkBamRecords).  Only what the packer reads
+// is converted (CIGAR and SEQ to text where they do not go over as they are; NM / MD / Zs / NH from the optional fields).
+void gk_bam_records(gk_bam* b, gk_packer* pk, GkBamRecords& out) {
+  static_assert(sizeof(gk_bam::Rec) == 16, "the layout GkBamRecords promises");
   const uint8_t* base = b->data.data();
-  auto ref_name = [&](int32_t id) -> std::string_view {
+  out.data = base;
+  out.data_bytes = b->data.size();
+  out.recs = b->recs.data();
+  out.n_recs = (int64_t)b->recs.size();
+  out.names_contiguous = b->name_sorted;
+  auto ref_name = [b](int32_t id) -> std::string_view {
     return (id >= 0 && (size_t)id < b->ref_names.size()) ? std::string_view(b->ref_names[(size_t)id]) : std::string_view("*");
   };
-  auto key = [&](int64_t i, GkAlnKey& k) {
+  auto key = [=](int64_t i, GkAlnKey& k) {
     const uint8_t* p = base + b->recs[(size_t)i].off;
     const int32_t ref_id = rds32(p), next_ref = rds32(p + 20);
     k.name = std::string_view((const char*)p + 32, strnlen((const char*)p + 32, p[8]));
@@ -890,9 +896,10 @@ static int bam_pack_impl(gk_bam* b, gk_packer* pk) {
     k.next_pos = (long)rds32(p + 24) + 1;
     k.mate_same_ref = next_ref >= 0 && next_ref == ref_id;
   };
-  std::vector<int> gene_of_ref(b->ref_names.size());   // reference id of the file -> backbone ordinal of the index
-  for (size_t i = 0; i < gene_of_ref.size(); ++i) gene_of_ref[i] = gk_packer_gene_of(pk, b->ref_names[i]);
-  auto soon = [&](int64_t i, bool head_only) {   // in name order the records are scattered over the inflated stream
+  out.gene_of_ref.resize(b->ref_names.size());         // reference id of the file -> backbone ordinal of the index
+  for (size_t i = 0; i < out.gene_of_ref.size(); ++i) out.gene_of_ref[i] = gk_packer_gene_of(pk, b->ref_names[i]);
+  const std::vector<int32_t>& gene_of_ref = out.gene_of_ref;
+  auto soon = [=](int64_t i, bool head_only) {   // in name order the records are scattered over the inflated stream
     const gk_bam::Rec& rec = b->recs[(size_t)i];
     const uint8_t* p = base + rec.off;
     if (head_only || rec.size <= 320) {
@@ -906,7 +913,7 @@ static int bam_pack_impl(gk_bam* b, gk_packer* pk) {
     __builtin_prefetch(p + 128);
     for (uint32_t o = rec.size - 192; o < rec.size; o += 64) __builtin_prefetch(p + o);
   };
-  auto full = [&](int64_t i, GkAlnRecord& r) {
+  auto full = [=, &gene_of_ref](int64_t i, GkAlnRecord& r) {
     const gk_bam::Rec& rec = b->recs[(size_t)i];
     const uint8_t* p = base + rec.off;
     const uint32_t l_name = p[8], n_cig = rd16(p + 12), l_seq = rd32(p + 16);
@@ -984,10 +991,21 @@ static int bam_pack_impl(gk_bam* b, gk_packer* pk) {
       tags = v + used;
     }
   };
-  // collated records are read front to back: the hardware prefetcher does what `soon` is for
-  if (b->name_sorted && b->collated) return gk_packer_feed_records(pk, (int64_t)b->recs.size(), true, key, full, nullptr);
-  if (b->name_sorted) return gk_packer_feed_records(pk, (int64_t)b->recs.size(), true, key, full, soon);
-  return gk_packer_feed_records(pk, (int64_t)b->recs.size(), false, key, full);
+  out.key = key;
+  out.full = full;
+  // collated records are read front to back: the hardware prefetcher does what `soon` is for; in file order nothing asks
+  if (b->name_sorted && !b->collated) out.soon = soon; else out.soon = nullptr;
+}
+
+extern "C" {
+
+// The records, in output order, straight into a packer: same pairing, checks and records as feeding
+// the rendered text to gk_packer_feed, without rendering or re-parsing it.
+static int bam_pack_impl(gk_bam* b, gk_packer* pk) {
+  if (!b || !pk) { gk_set_error("null handle"); return GK_ERR_ARG; }
+  GkBamRecords r;
+  gk_bam_records(b, pk, r);
+  return gk_packer_feed_records(pk, r.n_recs, r.names_contiguous, r.key, r.full, r.soon);
 }
 
 int gk_bam_close(gk_bam* b) {

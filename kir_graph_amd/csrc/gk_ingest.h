@@ -91,6 +91,37 @@ int gk_packer_feed_records(gk_packer* pk, int64_t n, bool names_contiguous,
                            const std::function<void(int64_t, GkAlnRecord&)>& full,
                            const std::function<void(int64_t, bool)>& soon = nullptr);
 
+// The two halves of gk_packer_feed_records, which is the two in sequence: a later device ingest decodes most pairs of
+// the list itself and must be able to sit between them.
+// gk_packer_pair_records: the pairing alone -- pairs[2p], pairs[2p + 1] = left (later) and right (earlier) record of
+// emitted pair p, *first_line = line number of record 0; the packer's read / pair / strange counts are updated.
+// gk_packer_decode_pairs: decodes the pairs of the list into the packer, in list order.
+using GkPairList = std::vector<int64_t, GkRawInit<int64_t>>;
+int gk_packer_pair_records(gk_packer* pk, int64_t n, bool names_contiguous,
+                           const std::function<void(int64_t, GkAlnKey&)>& key,
+                           const std::function<void(int64_t, bool)>& soon, GkPairList& pairs, int64_t* first_line);
+int gk_packer_decode_pairs(gk_packer* pk, int64_t first_line, const GkPairList& pairs,
+                           const std::function<void(int64_t, GkAlnRecord&)>& full,
+                           const std::function<void(int64_t, bool)>& soon);
+
+// An open BAM file as the packer's callers see it: the inflated stream, the record table in output order ({uint64
+// offset, uint32 size, 4 bytes unused} per record), the file's reference id -> backbone ordinal table for the packer's
+// index (-1: no backbone) and the three callbacks of gk_packer_feed_records.  The callbacks point into this object and
+// into the file handle: neither may move or go away while they are in use.
+struct gk_bam;
+struct GkBamRecords {
+  const uint8_t* data = nullptr;
+  size_t data_bytes = 0;
+  const void* recs = nullptr;
+  int64_t n_recs = 0;
+  bool names_contiguous = false;
+  std::vector<int32_t> gene_of_ref;
+  std::function<void(int64_t, GkAlnKey&)> key;
+  std::function<void(int64_t, GkAlnRecord&)> full;
+  std::function<void(int64_t, bool)> soon;      // empty when the records lie in reading order
+};
+void gk_bam_records(gk_bam* b, gk_packer* pk, GkBamRecords& out);
+
 // start offset of every line of a text (a final line without '\n' counts), plus the end as sentinel
 inline std::vector<int64_t> gk_line_starts(std::string_view text) {
   std::vector<int64_t> starts;

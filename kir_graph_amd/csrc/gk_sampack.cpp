@@ -706,14 +706,14 @@ int gk_packer_gene_of(const gk_packer* pk, std::string_view ref) {
   return g == pk->gene_id.end() ? -1 : (int)g->second;
 }
 
-int gk_packer_feed_records(gk_packer* pk, int64_t n, bool names_contiguous,
+// The two halves of gk_packer_feed_records: "pair -> list of (left, right) record numbers" and "decode the list".
+int gk_packer_pair_records(gk_packer* pk, int64_t n, bool names_contiguous,
                            const std::function<void(int64_t, GkAlnKey&)>& key,
-                           const std::function<void(int64_t, GkAlnRecord&)>& full,
-                           const std::function<void(int64_t, bool)>& soon) {
+                           const std::function<void(int64_t, bool)>& soon, GkPairList& pairs, int64_t* first_line) {
   if (!pk || n < 0) { gk_set_error("bad packer arguments"); return GK_ERR_ARG; }
   if (pk->err_kind) return GK_ERR_ASSERT;
   if (!pk->waiting.empty() || !pk->carry.empty()) { gk_set_error("text and record input cannot be mixed"); return GK_ERR_ARG; }
-  const int64_t base = pk->n_lines;
+  *first_line = pk->n_lines;
   pk->n_lines += n;
   GkPhaseClock clock("feed_records");
   // (1) pairing in stream order (hisat2.py:248-270).  Only records with the same name can pair, so
@@ -817,7 +817,6 @@ int gk_packer_feed_records(gk_packer* pk, int64_t n, bool names_contiguous,
   }
   // left (later) and right (earlier) record of every emitted pair: the lists of the pieces one after the other, each
   // copied by a thread of its own into a block that nobody zero-fills first (8 MB per million records, first touched here)
-  std::vector<int64_t, GkRawInit<int64_t>> pairs;
   {
     std::vector<size_t> at(pieces.size() + 1, 0);
     for (size_t t = 0; t < pieces.size(); ++t) {
@@ -843,6 +842,13 @@ int gk_packer_feed_records(gk_packer* pk, int64_t n, bool names_contiguous,
     }
   }
   clock.lap("pairing");
+  return GK_OK;
+}
+
+int gk_packer_decode_pairs(gk_packer* pk, int64_t base, const GkPairList& pairs,
+                           const std::function<void(int64_t, GkAlnRecord&)>& full,
+                           const std::function<void(int64_t, bool)>& soon) {
+  GkPhaseClock clock("feed_records");
   constexpr size_t kAhead = 6;
   // (2) decode on threads, (3) ordered pass over the pairs with inserted strings
   const bool merged = decode_all(
@@ -865,6 +871,17 @@ int gk_packer_feed_records(gk_packer* pk, int64_t n, bool names_contiguous,
     return GK_ERR_ASSERT;
   }
   return GK_OK;
+}
+
+int gk_packer_feed_records(gk_packer* pk, int64_t n, bool names_contiguous,
+                           const std::function<void(int64_t, GkAlnKey&)>& key,
+                           const std::function<void(int64_t, GkAlnRecord&)>& full,
+                           const std::function<void(int64_t, bool)>& soon) {
+  GkPairList pairs;
+  int64_t base = 0;
+  const int rc = gk_packer_pair_records(pk, n, names_contiguous, key, soon, pairs, &base);
+  if (rc != GK_OK) return rc;
+  return gk_packer_decode_pairs(pk, base, pairs, full, soon);
 }
 
 // helpers of gk_mates_compact_size / gk_mates_compact_host (below)
