@@ -62,9 +62,9 @@ KERNEL_SOURCES = {
     "novel_assign": ["gk_novel.hip", "gk_common.h"],
     "novel_confusion": ["gk_novel.hip", "gk_common.h"],
     "novel_compact": ["gk_novel.hip", "gk_common.h"],
-    "boot_resample": ["gk_boot.hip", "gk_common.h"],
+    "boot_resample": ["gk_boot.hip", "gk_draw.h", "gk_common.h"],
     "boot_em_batch": ["gk_boot.hip", "gk_squarem.h", "gk_common.h"],
-    "callboot_draw": ["gk_callboot.hip", "gk_common.h"],
+    "callboot_draw": ["gk_callboot.hip", "gk_draw.h", "gk_common.h"],
     "callboot_sums": ["gk_callboot.hip", "gk_common.h"],
     "callboot_fold": ["gk_callboot.hip", "gk_common.h"],
     "callfit_profile": ["gk_callfit.hip", "gk_called.h", "gk_common.h"],
@@ -72,12 +72,14 @@ KERNEL_SOURCES = {
     "callswap_rows": ["gk_callswap.hip", "gk_called.h", "gk_common.h"],
     "callswap_sums": ["gk_callswap.hip", "gk_called.h", "gk_common.h"],
     "calldosage_patterns": ["gk_calldosage.hip", "gk_called.h", "gk_common.h"],
-    "callcov_mark": ["gk_callcov.hip", "gk_called.h", "gk_common.h"],
-    "callcov_mark_lds": ["gk_callcov.hip", "gk_called.h", "gk_common.h"],
-    "callcov_finish": ["gk_callcov.hip", "gk_called.h", "gk_common.h"],
-    "depthw_mark": ["gk_depthboot.hip", "gk_common.h"],
-    "depthw_finish": ["gk_depthboot.hip", "gk_common.h"],
-    "depthw_select": ["gk_depthboot.hip", "gk_common.h"],
+    "callcov_mark": ["gk_callcov.hip", "gk_materuns.h", "gk_called.h", "gk_common.h"],
+    "callcov_mark_lds": ["gk_callcov.hip", "gk_materuns.h", "gk_called.h", "gk_common.h"],
+    "callcov_finish": ["gk_callcov.hip", "gk_materuns.h", "gk_called.h", "gk_common.h"],
+    "depthw_mark": ["gk_depthboot.hip", "gk_materuns.h", "gk_common.h"],
+    "depthw_finish": ["gk_depthboot.hip", "gk_materuns.h", "gk_common.h"],
+    "depthw_select": ["gk_depthboot.hip", "gk_materuns.h", "gk_common.h"],
+    "depth_mark": ["gk_depth.hip", "gk_materuns.h", "gk_common.h"],
+    "depth_finish": ["gk_depth.hip", "gk_materuns.h", "gk_common.h"],
     "setsum_few": ["gk_setsum_few.hip", "gk_common.h"],
     "rowclass_keys": ["gk_rowclass.hip", "gk_rowclass.h", "gk_common.h"],
     "rowclass_verify": ["gk_rowclass.hip", "gk_rowclass.h", "gk_common.h"],

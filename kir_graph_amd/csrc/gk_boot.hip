@@ -2,7 +2,7 @@
 //
 //   boot_resample    a replicate draws n reads with replacement from the gene's n reads (n = the sum of the multiplicities
 //                    of its distinct candidate sets, the empty set included) and keeps, per distinct set, how many of the
-//                    draws fell on it.  The draws are counter-based (a splitmix64 finish of seed, draw, replicate and the
+//                    draws fell on it.  The draws are counter-based (gk_draw.h: a splitmix64 finish of seed, draw, replicate and the
 //                    gene's stream number), so any thread makes any draw and a replicate depends on nothing but its own
 //                    four numbers; draw j belongs to the set u with cum[u] <= j < cum[u + 1] (a bisection of the inclusive
 //                    prefix sums).  A workgroup takes a chunk of the draws of one (gene, replicate): prefix sums and a
@@ -20,6 +20,7 @@
 
 #include "gk_common.h"
 #include "gk_blocks.h"
+#include "gk_draw.h"
 #include "gk_squarem.h"
 
 namespace {
@@ -36,14 +37,6 @@ struct BootDraw {      // one gene of boot_resample (blockIdx.z)
   int64_t cnt_off;     // the gene's counts within a replicate's row
   uint32_t n_sets, n, stream, chunk;
 };
-
-__device__ inline uint32_t boot_draw(uint64_t seed, uint64_t i, uint64_t b, uint64_t g, uint32_t n) {
-  uint64_t z = seed + (i + 1) * 0x9E3779B97F4A7C15ull + (b + 1) * 0xBF58476D1CE4E5B9ull + (g + 1) * 0x94D049BB133111EBull;
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (uint32_t)(((z >> 32) * (uint64_t)n) >> 32);      // < n
-}
 
 // the number of prefix sums <= j: the set the draw falls on (sets without reads are stepped over)
 __device__ inline uint32_t boot_find(const uint32_t* cum, uint32_t n_sets, uint32_t j) {
@@ -72,13 +65,13 @@ __global__ __launch_bounds__(kBootThreads) void boot_resample(const BootDraw* __
     for (uint32_t e = tid; e < J.n_sets; e += kBootThreads) { lcum[e] = cum[e]; hist[e] = 0u; }
     __syncthreads();
     for (uint64_t i = begin + tid; i < end; i += kBootThreads)
-      atomicAdd(&hist[boot_find(lcum, J.n_sets, boot_draw(seed, i, b, J.stream, J.n))], 1u);
+      atomicAdd(&hist[boot_find(lcum, J.n_sets, gk_boot_draw(seed, i, b, J.stream, J.n))], 1u);
     __syncthreads();
     for (uint32_t e = tid; e < J.n_sets; e += kBootThreads)
       if (hist[e]) atomicAdd(&cnt[e], hist[e]);
   } else {
     for (uint64_t i = begin + tid; i < end; i += kBootThreads)
-      atomicAdd(&cnt[boot_find(cum, J.n_sets, boot_draw(seed, i, b, J.stream, J.n))], 1u);
+      atomicAdd(&cnt[boot_find(cum, J.n_sets, gk_boot_draw(seed, i, b, J.stream, J.n))], 1u);
   }
 }
 

@@ -3,7 +3,7 @@
 // search runs again.
 //
 //   callboot_draw    replicate b draws n reads with replacement from the gene's n reads: a thread per draw (the counter
-//                    based generator of gk_boot.hip, DESIGN.md section 8c, unchanged), one integer atomicAdd into
+//                    based generator of gk_draw.h, DESIGN.md section 8c, shared with gk_boot.hip), one integer atomicAdd into
 //                    W[b][row].  Draws scatter over n rows, about one per row: there is nothing to privatise in LDS.
 //                    Integer adds only: exact, whatever the schedule.
 //   callboot_sums    S[b][t] = sum_r W[b][r] * V[t][r].  Lanes run across rows, so both tables are read as whole lines.
@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "gk_blocks.h"
+#include "gk_draw.h"
 
 namespace {
 
@@ -34,16 +35,6 @@ constexpr int kDrawThreads = 256;
 constexpr uint32_t kDrawChunk = 1u << 14;      // draws of a workgroup per turn
 constexpr uint32_t kDrawMaxGroups = 2048;      // workgroups per replicate; they stride over the chunks beyond
 
-// draw i of replicate b of stream g: boot_draw of gk_boot.hip, restated -- a shared header would change that file, whose
-// digest committed profiles are pinned to (build.KERNEL_SOURCES); tests/boot_reference.py holds both to the same numbers
-__device__ inline uint32_t callboot_row(uint64_t seed, uint64_t i, uint64_t b, uint64_t g, uint32_t n) {
-  uint64_t z = seed + (i + 1) * 0x9E3779B97F4A7C15ull + (b + 1) * 0xBF58476D1CE4E5B9ull + (g + 1) * 0x94D049BB133111EBull;
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (uint32_t)(((z >> 32) * (uint64_t)n) >> 32);      // < n
-}
-
 __global__ __launch_bounds__(kDrawThreads) void callboot_draw(uint32_t n, uint32_t boot_first, uint64_t seed, uint32_t stream,
                                                               uint32_t* __restrict__ W, int64_t ldw) {
   const uint32_t b = blockIdx.y;
@@ -52,7 +43,7 @@ __global__ __launch_bounds__(kDrawThreads) void callboot_draw(uint32_t n, uint32
   for (uint64_t begin = (uint64_t)blockIdx.x * kDrawChunk; begin < n; begin += stride) {
     const uint64_t end = min(begin + (uint64_t)kDrawChunk, (uint64_t)n);
     for (uint64_t i = begin + threadIdx.x; i < end; i += kDrawThreads)
-      atomicAdd(&row[callboot_row(seed, i, (uint64_t)boot_first + b, stream, n)], 1u);
+      atomicAdd(&row[gk_boot_draw(seed, i, (uint64_t)boot_first + b, stream, n)], 1u);
   }
 }
 

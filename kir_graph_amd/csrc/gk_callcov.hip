@@ -2,19 +2,18 @@
 // the u8 mismatch table the search left in HBM joined with the sample's records (gk_call_coverage).  No search runs again.
 //
 // For row r of the model, b_k = miss8[cols[k]][r] over the K distinct called columns (1 .. 16), m1 = min_k b_k and
-// A = {k : b_k == m1} -- callfit_profile's rule (gk_callfit.hip), bytes as stored, 255 included, restated here: that
-// file's digest pins committed profiles.  The row's pair then counts, with both mates, in the tracks
+// A = {k : b_k == m1} -- callfit_profile's rule (gk_callfit.hip), bytes as stored, 255 included; the row loops of the
+// call reports stay apart because their registers are counted per kernel.  The row's pair then
+// counts, with both mates, in the tracks
 //
 //   0          informative   always
 //   1          mismatch      m1 > 0
 //   2 + k      best_k        k in A
 //   2 + K + k  unique_k      A == {k}
 //
-// and a mate counts as in depth_mark (gk_depth.hip, restated for the same reason): every M run [cur, cur + n) of its
-// CIGAR, clipped to [0, gene_len), adds +1 at its start and -1 at its end into the difference array of every track the
-// row counts in; M and D advance cur, every other operation does not; mates are counted independently (no overlap
-// removal); a mate on another backbone marks nothing; a pair in the wide format takes its CIGAR from the tabulation's
-// wide records and is skipped when there are none.
+// and a mate counts as in depth_mark (gk_depth.hip; the walk of its M runs is gk_materuns.h, shared): every clipped M run
+// adds +1 at its start and -1 at its end into the difference array of every track the row counts in; mates are counted
+// independently (no overlap removal); a mate on another backbone marks nothing.
 //
 // Marking: one thread per mate, mate t of row t >> 1, 256 threads -- a wave holds 32 rows, a workgroup 128.  The thread
 // issues the K byte loads of its row together and unconditionally with clamped indices (a column beyond the list reads the
@@ -36,11 +35,11 @@
 // tests/test_gpu_call_coverage.py takes its row counts from the wave's 32 rows and the workgroup's 128, and its gene
 // lengths from kCovLdsBytes: move them together.
 #include <algorithm>
-#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 
 #include "gk_called.h"
+#include "gk_materuns.h"
 
 namespace {
 
@@ -49,17 +48,6 @@ constexpr int64_t kCovMaxLen = 1ll << 24;                    // a backbone posit
 constexpr size_t kCovLdsBytes = 144 * 1024;                  // a track's difference array in LDS: gene_len <= 36863
 constexpr int64_t kCovLdsTurns = 16;                         // turns of 256 mates a workgroup of the LDS form takes at least
 constexpr int64_t kCovLdsGroups = 1024;                      // workgroups of the LDS form over all tracks, about
-constexpr int kCovInsWord = offsetof(gk_mate, ins) / 4;      // ins[0] of a record whose pair is in the wide array: its place there
-static_assert(offsetof(gk_mate, cig) == 12 && offsetof(gk_mate, pos0) == 0 && sizeof(gk_mate) == 128, "gk_mate layout");
-
-struct CovSample {
-  const gk_mate* mates;              // the 128-byte records, or
-  const uint32_t* c_off;             // the compact form: word offsets [2 * n_pairs + 1] ...
-  const uint32_t* c_words;           // ... and the words
-  const gk_mate_wide* wide;
-  const int32_t* pair_src;
-  int64_t n_valid, n_pairs, n_spill;
-};
 
 // b_k of row r over the listed columns, loaded together and unconditionally: the tie set A as a mask, m1 in *m1_out.
 // KT: the columns a thread loads, K <= KT of them listed; off[k] = where column k starts (k >= K: the last listed one)
@@ -88,48 +76,18 @@ __device__ inline uint64_t cov_tracks(uint32_t ties, uint32_t m1, int K) {
   return tracks;
 }
 
-// Mate `side` of valid pair `row`: mark(a, e) for every M run of its CIGAR clipped to [0, len), when it lies on `gene`.
+// Mate `side` of valid pair `row`: mark(a, e) for every clipped M run of its CIGAR, when it lies on `gene`.
 template <bool kCompact, class Mark>
-__device__ inline void cov_walk(const CovSample& s, int64_t row, int side, int gene, int64_t len, Mark mark) {
+__device__ inline void cov_walk(const GkMateSample& s, int64_t row, int side, int gene, int64_t len, Mark mark) {
   if (row < 0 || row >= s.n_valid) return;      // not a valid pair of this tabulation
-  const int64_t src = s.pair_src[row];
-  if (src < 0 || src >= s.n_pairs) return;
-  const int64_t at = 2 * src + side;
-  // header words 0 - 2 (pos0, flag | ref | nh, nm | n_cig | n_mm | n_ins), then the words that hold the CIGAR / the wide index
-  const uint32_t* w = kCompact ? s.c_words + s.c_off[at] : reinterpret_cast<const uint32_t*>(s.mates + at);
-  const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-  const uint32_t ref = (w1 >> 16) & 0xFFu, n_ops = (w2 >> 8) & 0xFFu;
-  if ((int)ref != gene) return;
-  int64_t cur = w0;
-  auto run = [&](uint32_t op, uint32_t n) {
-    if (op == GK_CIG_M) {
-      const int64_t a = cur < 0 ? 0 : cur, e = cur + n > len ? len : cur + n;
-      if (e > a) mark(a, e);
-      cur += n;
-    } else if (op == GK_CIG_D) {
-      cur += n;
-    }
-  };
-  if (n_ops == GK_SPILLED) {      // the pair is in the wide array (gk_mate_wide): its CIGAR is there
-    if (!s.wide) return;
-    const int64_t slot = kCompact ? w[3] : w[kCovInsWord];
-    if (slot >= s.n_spill) return;
-    const gk_mate_wide& x = s.wide[2 * slot + side];
-    const int n_cig = x.n_cig < GK_WIDE_CIG ? x.n_cig : GK_WIDE_CIG;
-    for (int c = 0; c < n_cig; ++c) run(x.cig[c] & 15u, x.cig[c] >> 4);
-    return;
-  }
-  const int n_cig = n_ops < GK_MAX_CIG ? (int)n_ops : GK_MAX_CIG;
-  for (int c = 0; c < n_cig; ++c) {      // uint16 operations, two to a word, from word 3 in either form
-    const uint32_t x = w[3 + (c >> 1)];
-    const uint32_t cg = (c & 1) ? (x >> 16) : (x & 0xFFFFu);
-    run(cg & 15u, cg >> 4);
-  }
+  GkMateRuns m;
+  if (!gk_mate_find<kCompact>(s, row, side, [&](uint32_t ref) { return (int)ref == gene; }, m)) return;
+  gk_mate_walk<kCompact>(s, m, side, len, mark);
 }
 
 // The direct form: one thread per mate marks every track of its row in HBM.
 template <bool kCompact, int KT>
-__global__ __launch_bounds__(kCovThreads) void callcov_mark(CovSample s, const int32_t* __restrict__ rows, int64_t n_rows,
+__global__ __launch_bounds__(kCovThreads) void callcov_mark(GkMateSample s, const int32_t* __restrict__ rows, int64_t n_rows,
                                                             const uint8_t* __restrict__ miss8, int64_t ldm, GkCalledCols cols, int K,
                                                             int gene, int64_t len, uint32_t* __restrict__ diff) {
   const int64_t t = (int64_t)blockIdx.x * kCovThreads + threadIdx.x;
@@ -157,7 +115,7 @@ __global__ __launch_bounds__(kCovThreads) void callcov_mark(CovSample s, const i
 // HBM at the end, contiguously.  A row that does not count in the track costs its K bytes and nothing else; the records
 // of a row are read once per track it counts in.
 template <bool kCompact, int KT>
-__global__ __launch_bounds__(kCovThreads) void callcov_mark_lds(CovSample s, const int32_t* __restrict__ rows, int64_t n_rows,
+__global__ __launch_bounds__(kCovThreads) void callcov_mark_lds(GkMateSample s, const int32_t* __restrict__ rows, int64_t n_rows,
                                                                 const uint8_t* __restrict__ miss8, int64_t ldm, GkCalledCols cols,
                                                                 int K, int gene, int64_t len, uint32_t* __restrict__ diff) {
   extern __shared__ uint32_t lds_diff[];
@@ -242,16 +200,7 @@ int gk_call_coverage(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compac
   hipError_t e = hipMemsetAsync(diff, 0, (size_t)slots * sizeof(uint32_t), st);
   if (e != hipSuccess) return fail(e);
   {
-    CovSample s;
-    const uint32_t* c_off = gk_ptr<const uint32_t>(d_compact);
-    s.mates = gk_ptr<const gk_mate>(d_mates);
-    s.c_off = c_off;
-    s.c_words = c_off ? c_off + 2 * tab->n_pairs + 1 : nullptr;
-    s.wide = tab->d_wide;
-    s.pair_src = tab->d_pair_src;
-    s.n_valid = tab->n_valid;
-    s.n_pairs = tab->n_pairs;
-    s.n_spill = tab->n_spill;
+    const GkMateSample s = gk_mate_sample(tab, d_mates, d_compact);
     const dim3 block(kCovThreads);
     const int32_t* rows = gk_ptr<const int32_t>(d_rows);
     const uint8_t* m = gk_ptr<const uint8_t>(d_miss8);
@@ -272,7 +221,7 @@ int gk_call_coverage(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compac
   } while (0)
 #define GK_COV_LAUNCH(KT)     \
   do {                        \
-    if (c_off)                \
+    if (s.c_off)              \
       GK_COV_LDS(true, KT);   \
     else                      \
       GK_COV_LDS(false, KT);  \
@@ -284,7 +233,7 @@ int gk_call_coverage(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compac
       const dim3 grid((unsigned)mate_groups);
 #define GK_COV_LAUNCH(KT)                                                                                               \
   do {                                                                                                                  \
-    if (c_off)                                                                                                          \
+    if (s.c_off)                                                                                                        \
       GK_PROF(ctx, "callcov_mark", GK_KERNEL((callcov_mark<true, KT>), grid, block, 0, st, s, rows, n_rows, m, ldm, cc,  \
                                              (int)n_cols, (int)gene, gene_len, diff));                                  \
     else                                                                                                                \

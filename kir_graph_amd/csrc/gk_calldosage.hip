@@ -6,8 +6,8 @@
 // mixture likelihood of call_dosage.py needs of the row, and no more.  A gene's rows take few patterns (a read in shared
 // sequence is all-zero, a read private to one allele is zero there and 1 .. 3 elsewhere).
 //
-//   calldosage_patterns  one pass.  Lanes run across rows as in callfit_profile (gk_callfit.hip; restated here, that file's
-//                        digest pins committed profiles): a lane takes kPatLaneRows = 16 rows of a column per 16-byte load,
+//   calldosage_patterns  one pass.  Lanes run across rows as in callfit_profile (gk_callfit.hip; the row loops stay apart,
+//                        their registers are counted per kernel: DESIGN.md section 8j): a lane takes kPatLaneRows = 16 rows of a column per 16-byte load,
 //                        a workgroup kPatChunk = 4096 rows per turn, the grid strides over the chunks; the K loads of a
 //                        turn are issued together and unconditionally (a lane beyond the end reads row 0, a column beyond
 //                        the list the last listed one) and such rows and columns are masked, so the padding may hold

@@ -3,11 +3,9 @@
 // order statistics of the gene's selected positions -- what p75 / mean / median of a replicate's depth track are made of.
 // Only those numbers cross PCIe; the tracks stay in HBM (depth_out exists for the tests).
 //
-// A mate counts as in depth_mark (gk_depth.hip, restated here: that file's digest pins committed profiles): pairs with
-// NH != 1 are skipped unless `multiple`; every M run [cur, cur + n) of the CIGAR, clipped to [0, gene_len) of the mate's own
-// backbone, adds +w at its start and -w at its end into the replicate's difference array; M and D advance cur, every other
-// operation does not; a pair in the wide format takes its CIGAR from the tabulation's wide records and is skipped when
-// there are none.  With every weight 1 the result is gk_depth's integers.  All adds are integer atomics mod 2^32: exact
+// A mate counts as in depth_mark (gk_depth.hip; the walk of its M runs is gk_materuns.h, shared): pairs with NH != 1 are
+// skipped unless `multiple`; every clipped M run adds +w at its start and -w at its end into the replicate's difference
+// array.  With every weight 1 the result is gk_depth's integers.  All adds are integer atomics mod 2^32: exact
 // whatever the schedule.
 //
 //   depthw_mark    one thread per mate (a workgroup holds 128 pairs) and per group of kBootPerThread replicates of the
@@ -28,10 +26,10 @@
 // the slice it falls in.  tests/test_gpu_cn_bootstrap.py takes its pair counts from the workgroup's 128 pairs and its depth
 // values from the digit boundaries 2^10 and 2^21: move them together.
 #include <algorithm>
-#include <cstddef>
 #include <vector>
 
 #include "gk_blocks.h"
+#include "gk_materuns.h"
 
 namespace {
 
@@ -40,24 +38,10 @@ constexpr int kMaxBoot = 10000;
 constexpr int kBootPerThread = 8;                           // replicates a thread of depthw_mark takes
 constexpr size_t kDepthwBudget = (size_t)1 << 30;           // bytes of a slice's difference arrays + their scan copy
 constexpr int64_t kDwMaxLen = 1ll << 24;                    // a backbone position has 24 bits in a variant key
-constexpr int kCigWords = GK_MAX_CIG / 2;                   // uint16 operations, two to a word
-constexpr int kDwInsWord = offsetof(gk_mate, ins) / 4;      // ins[0] of a record whose pair is in the wide array: its place there
 constexpr int kSelBins = 2048;                              // 11 bits; the last pass uses the first 1024
-static_assert(offsetof(gk_mate, cig) == 12 && offsetof(gk_mate, pos0) == 0 && sizeof(gk_mate) == 128, "gk_mate layout");
-static_assert(GK_MAX_CIG % 2 == 0, "the CIGAR of a record is held as whole words");
-
-struct DwSample {
-  const gk_mate* mates;              // the 128-byte records, or
-  const uint32_t* c_off;             // the compact form: word offsets [2 * n_pairs + 1] ...
-  const uint32_t* c_words;           // ... and the words
-  const gk_mate_wide* wide;
-  const int32_t* pair_src;
-  const uint8_t* pair_nh;
-  int64_t n_valid, n_pairs, n_spill;
-};
 
 template <bool kCompact>
-__global__ __launch_bounds__(kDwThreads) void depthw_mark(DwSample s, int multiple, const int64_t* __restrict__ gene_off,
+__global__ __launch_bounds__(kDwThreads) void depthw_mark(GkMateSample s, int multiple, const int64_t* __restrict__ gene_off,
                                                           int n_gene, const uint32_t* __restrict__ W, int64_t ldw, int n_boot,
                                                           int64_t slots, uint32_t* __restrict__ diff) {
   const int64_t t = (int64_t)blockIdx.x * kDwThreads + threadIdx.x;
@@ -65,59 +49,21 @@ __global__ __launch_bounds__(kDwThreads) void depthw_mark(DwSample s, int multip
   const int64_t i = t >> 1;
   const int side = (int)(t & 1);
   if (!multiple && s.pair_nh[i] != 1) return;
-  const int64_t src = s.pair_src[i];
-  if (src < 0 || src >= s.n_pairs) return;
-  const int64_t at = 2 * src + side;
-  // header words 0 - 2 (pos0, flag | ref | nh, nm | n_cig | n_mm | n_ins), then the words that hold the CIGAR / the wide index
-  const uint32_t* w = kCompact ? s.c_words + s.c_off[at] : reinterpret_cast<const uint32_t*>(s.mates + at);
-  const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-  const uint32_t ref = (w1 >> 16) & 0xFFu, n_ops = (w2 >> 8) & 0xFFu;
-  if ((int)ref >= n_gene) return;
-  const int64_t base = gene_off[ref], len = gene_off[ref + 1] - base;
-  const gk_mate_wide* far = nullptr;
-  int n_cig = 0;
-  uint32_t cw[kCigWords];
-  if (n_ops == GK_SPILLED) {      // the pair is in the wide array (gk_mate_wide): its CIGAR is there
-    if (!s.wide) return;
-    const int64_t slot = kCompact ? w[3] : w[kDwInsWord];
-    if (slot >= s.n_spill) return;
-    far = s.wide + 2 * slot + side;
-    n_cig = far->n_cig < GK_WIDE_CIG ? far->n_cig : GK_WIDE_CIG;
-  } else {
-    n_cig = n_ops < GK_MAX_CIG ? (int)n_ops : GK_MAX_CIG;
-#pragma unroll
-    for (int k = 0; k < kCigWords; ++k) cw[k] = 2 * k < n_cig ? w[3 + k] : 0u;      // a compact mate ends with its last word
-  }
+  GkMateRuns m;
+  if (!gk_mate_find<kCompact>(s, i, side, [&](uint32_t ref) { return (int)ref < n_gene; }, m)) return;
+  const int64_t base = gene_off[m.ref], len = gene_off[m.ref + 1] - base;
+  GkMateCigar cig;
+  if (!gk_mate_stage<kCompact>(s, m, side, cig)) return;
   const int b0 = blockIdx.y * kBootPerThread;
   const int b1 = min(b0 + kBootPerThread, n_boot);
   for (int b = b0; b < b1; ++b) {
     const uint32_t wt = W[(int64_t)b * ldw + i];
     if (wt == 0) continue;
     uint32_t* d = diff + (int64_t)b * slots + base;
-    int64_t cur = w0;
-    auto run = [&](uint32_t op, uint32_t n) {
-      if (op == GK_CIG_M) {
-        const int64_t a = cur < 0 ? 0 : cur, e = cur + n > len ? len : cur + n;
-        if (e > a) {
-          atomicAdd(&d[a], wt);
-          atomicAdd(&d[e], 0u - wt);      // -w (mod 2^32); a replicate's array has one slot past the end
-        }
-        cur += n;
-      } else if (op == GK_CIG_D) {
-        cur += n;
-      }
-    };
-    if (far) {
-      for (int c = 0; c < n_cig; ++c) run(far->cig[c] & 15u, far->cig[c] >> 4);
-    } else {
-#pragma unroll
-      for (int c = 0; c < GK_MAX_CIG; ++c) {
-        if (c < n_cig) {
-          const uint32_t cg = (c & 1) ? (cw[c >> 1] >> 16) : (cw[c >> 1] & 0xFFFFu);
-          run(cg & 15u, cg >> 4);
-        }
-      }
-    }
+    gk_mate_walk_staged(m, cig, len, [&](int64_t a, int64_t e) {
+      atomicAdd(&d[a], wt);
+      atomicAdd(&d[e], 0u - wt);      // -w (mod 2^32); a replicate's array has one slot past the end
+    });
   }
 }
 
@@ -317,17 +263,7 @@ int gk_depth_weighted(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compa
   if (e == hipSuccess) e = gk_send(ctx, d_rank, rank, (size_t)2 * n_gene * sizeof(int64_t));
   if (e == hipSuccess && sel) e = gk_send(ctx, d_sel, sel, (size_t)total);      // once, for every slice
   if (e != hipSuccess) return fail(e);
-  DwSample s;
-  const uint32_t* c_off = gk_ptr<const uint32_t>(d_compact);
-  s.mates = gk_ptr<const gk_mate>(d_mates);
-  s.c_off = c_off;
-  s.c_words = c_off ? c_off + 2 * tab->n_pairs + 1 : nullptr;
-  s.wide = tab->d_wide;
-  s.pair_src = tab->d_pair_src;
-  s.pair_nh = tab->d_pair_nh;
-  s.n_valid = tab->n_valid;
-  s.n_pairs = tab->n_pairs;
-  s.n_spill = tab->n_spill;
+  const GkMateSample s = gk_mate_sample(tab, d_mates, d_compact);
   const uint32_t* W = gk_ptr<const uint32_t>(d_W);
   const unsigned mate_groups = (unsigned)((2 * tab->n_valid + kDwThreads - 1) / kDwThreads);
   for (int64_t b0 = 0; b0 < n_boot; b0 += slice) {
@@ -336,7 +272,7 @@ int gk_depth_weighted(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compa
     e = hipMemsetAsync(diff, 0, (size_t)n * sizeof(uint32_t), st);
     if (e != hipSuccess) return fail(e);
     const dim3 grid(mate_groups, (unsigned)((nb + kBootPerThread - 1) / kBootPerThread));
-    if (c_off)
+    if (s.c_off)
       GK_PROF(ctx, "depthw_mark", GK_KERNEL(depthw_mark<true>, grid, dim3(kDwThreads), 0, st, s, (int)multiple, d_off, (int)n_gene,
                                             W + b0 * ldw, ldw, nb, slots, diff));
     else
