@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "gk_common.h"
-#include "gk_blocks.h"
+#include "gk_calls.h"
 #include "gk_draw.h"
 #include "gk_squarem.h"
 
@@ -193,14 +193,7 @@ int gk_em_bootstrap(gk_ctx* ctx, const gk_boot_job* jobs, int32_t n_jobs, int32_
   if (draws.empty()) return GK_OK;
   // ---- device
   hipStream_t st = ctx->stream;
-  GkBlocks temps(ctx);
-  // a failure after the first queued copy: the stream still reads this call's vectors and may write its outputs
-  auto fail = [&](const char* what) {
-    const hipError_t e = hipGetLastError();
-    gk_fetch_cancel(ctx);
-    gk_set_error("EM bootstrap: %s: %s", what, hipGetErrorString(e));
-    return GK_ERR_HIP;
-  };
+  GkCall call(ctx);      // after draws, cum and h, which the stream reads (below)
   BootDraw* d_draws = nullptr;
   EmGene* d_genes = nullptr;
   uint32_t *d_cum = nullptr, *d_cnt = nullptr, *d_so = nullptr, *d_ao = nullptr, *d_as = nullptr;
@@ -210,17 +203,17 @@ int gk_em_bootstrap(gk_ctx* ctx, const gk_boot_job* jobs, int32_t n_jobs, int32_
   const size_t cnt_bytes = (size_t)n_boot * row_sets * sizeof(uint32_t);
   const size_t prob_bytes = (size_t)n_boot * row_prob * sizeof(double);
   const size_t it_bytes = (size_t)n_boot * n_jobs * sizeof(int);
-  if (temps.take(&d_draws, draws.size() * sizeof(BootDraw)) != hipSuccess ||
-      temps.take(&d_cum, cum.size() * sizeof(uint32_t)) != hipSuccess ||
-      temps.take(&d_cnt, cnt_bytes) != hipSuccess ||
-      temps.take(&d_genes, h.genes.size() * sizeof(EmGene)) != hipSuccess ||
-      temps.take(&d_so, h.set_off.size() * sizeof(uint32_t)) != hipSuccess ||
-      temps.take(&d_mem, h.members.size() * sizeof(uint16_t)) != hipSuccess ||
-      temps.take(&d_ao, h.al_off.size() * sizeof(uint32_t)) != hipSuccess ||
-      temps.take(&d_as, h.al_sets.size() * sizeof(uint32_t)) != hipSuccess ||
-      temps.take(&d_scale, (size_t)n_boot * row_scale * sizeof(double)) != hipSuccess ||
-      temps.take(&d_prob, prob_bytes) != hipSuccess ||
-      temps.take(&d_it, it_bytes) != hipSuccess) {
+  if (call.take(&d_draws, draws.size() * sizeof(BootDraw)) != hipSuccess ||
+      call.take(&d_cum, cum.size() * sizeof(uint32_t)) != hipSuccess ||
+      call.take(&d_cnt, cnt_bytes) != hipSuccess ||
+      call.take(&d_genes, h.genes.size() * sizeof(EmGene)) != hipSuccess ||
+      call.take(&d_so, h.set_off.size() * sizeof(uint32_t)) != hipSuccess ||
+      call.take(&d_mem, h.members.size() * sizeof(uint16_t)) != hipSuccess ||
+      call.take(&d_ao, h.al_off.size() * sizeof(uint32_t)) != hipSuccess ||
+      call.take(&d_as, h.al_sets.size() * sizeof(uint32_t)) != hipSuccess ||
+      call.take(&d_scale, (size_t)n_boot * row_scale * sizeof(double)) != hipSuccess ||
+      call.take(&d_prob, prob_bytes) != hipSuccess ||
+      call.take(&d_it, it_bytes) != hipSuccess) {
     gk_set_error("out of device memory for the EM bootstrap of a sample");
     return GK_ERR_HIP;
   }
@@ -232,32 +225,33 @@ int gk_em_bootstrap(gk_ctx* ctx, const gk_boot_job* jobs, int32_t n_jobs, int32_
     gk_set_error("EM bootstrap: %zu / %zu bytes of LDS refused", draw_lds, em_lds);
     return GK_ERR_HIP;
   }
-  // the sources of the large copies live until the stream is waited for below
-  if (gk_send(ctx, d_draws, draws.data(), draws.size() * sizeof(BootDraw)) != hipSuccess ||
-      gk_send(ctx, d_cum, cum.data(), cum.size() * sizeof(uint32_t)) != hipSuccess ||
-      hipMemsetAsync(d_cnt, 0, cnt_bytes, st) != hipSuccess)
-    return fail("queueing the draws");
+  // a copy too large for the ring is queued straight from its vector: no wait per copy -- the one at the end covers them
+  // all, and a way out before it drains the stream while the vectors (declared before the record) still live
+  call.expect();
+  GK_TRY("EM bootstrap: queueing the draws", gk_send(ctx, d_draws, draws.data(), draws.size() * sizeof(BootDraw)));
+  GK_TRY("EM bootstrap: queueing the draws", gk_send(ctx, d_cum, cum.data(), cum.size() * sizeof(uint32_t)));
+  GK_TRY("EM bootstrap: queueing the draws", hipMemsetAsync(d_cnt, 0, cnt_bytes, st));
   GK_PROF(ctx, "boot_resample", GK_KERNEL(boot_resample, dim3(max_chunks, (unsigned)n_boot, (unsigned)draws.size()),
                                           dim3(kBootThreads), draw_lds, st, d_draws, d_cum, seed, row_sets, d_cnt));
   if (!h.genes.empty()) {
-    if (gk_send(ctx, d_genes, h.genes.data(), h.genes.size() * sizeof(EmGene)) != hipSuccess ||
-        gk_send(ctx, d_so, h.set_off.data(), h.set_off.size() * sizeof(uint32_t)) != hipSuccess ||
-        gk_send(ctx, d_mem, h.members.data(), h.members.size() * sizeof(uint16_t)) != hipSuccess ||
-        gk_send(ctx, d_as, h.al_sets.data(), h.al_sets.size() * sizeof(uint32_t)) != hipSuccess ||
-        gk_send(ctx, d_ao, h.al_off.data(), h.al_off.size() * sizeof(uint32_t)) != hipSuccess ||
-        (prob_bytes && hipMemsetAsync(d_prob, 0, prob_bytes, st) != hipSuccess) ||
-        hipMemsetAsync(d_it, 0, it_bytes, st) != hipSuccess)
-      return fail("queueing the sparse forms");
+    const char* const what = "EM bootstrap: queueing the sparse forms";
+    GK_TRY(what, gk_send(ctx, d_genes, h.genes.data(), h.genes.size() * sizeof(EmGene)));
+    GK_TRY(what, gk_send(ctx, d_so, h.set_off.data(), h.set_off.size() * sizeof(uint32_t)));
+    GK_TRY(what, gk_send(ctx, d_mem, h.members.data(), h.members.size() * sizeof(uint16_t)));
+    GK_TRY(what, gk_send(ctx, d_as, h.al_sets.data(), h.al_sets.size() * sizeof(uint32_t)));
+    GK_TRY(what, gk_send(ctx, d_ao, h.al_off.data(), h.al_off.size() * sizeof(uint32_t)));
+    if (prob_bytes) GK_TRY(what, hipMemsetAsync(d_prob, 0, prob_bytes, st));
+    GK_TRY(what, hipMemsetAsync(d_it, 0, it_bytes, st));
     const BootArrays A{d_cnt, d_scale, d_so, d_mem, d_ao, d_as, row_sets, row_scale};
     GK_PROF(ctx, "boot_em_batch", GK_KERNEL(boot_em_batch, dim3((unsigned)n_boot, (unsigned)h.genes.size()), dim3(kEmThreads),
                                             em_lds, st, d_genes, A, (int)n_jobs, row_prob, (int)iter_max, diff_threshold, d_prob,
                                             d_it));
-    if (gk_fetch_queue(ctx, prob_out, d_prob, prob_bytes) != hipSuccess ||
-        gk_fetch_queue(ctx, iters_out, d_it, it_bytes) != hipSuccess)
-      return fail("queueing the results");
+    GK_TRY("EM bootstrap: queueing the results", call.fetch(prob_out, d_prob, prob_bytes));
+    GK_TRY("EM bootstrap: queueing the results", call.fetch(iters_out, d_it, it_bytes));
   }
-  if (counts_out && gk_fetch_queue(ctx, counts_out, d_cnt, cnt_bytes) != hipSuccess) return fail("queueing the counts");
-  if (hipGetLastError() != hipSuccess || gk_fetch_wait(ctx) != hipSuccess) return fail("launch");
+  if (counts_out) GK_TRY("EM bootstrap: queueing the counts", call.fetch(counts_out, d_cnt, cnt_bytes));
+  GK_TRY("EM bootstrap: launch", hipGetLastError());
+  GK_TRY("EM bootstrap: launch", call.wait());
   return GK_OK;
 }
 

@@ -22,7 +22,7 @@
 // (4 x 8): move them together.
 #include <algorithm>
 
-#include "gk_blocks.h"
+#include "gk_calls.h"
 #include "gk_draw.h"
 
 namespace {
@@ -168,13 +168,13 @@ int gk_weighted_sums(gk_ctx* ctx, gk_dptr d_V, int64_t ld, int64_t n_rows, int32
     return GK_ERR_CAPACITY;
   }
   hipStream_t st = ctx->stream;
-  GkBlocks temps(ctx);
+  GkCall call(ctx);
   double *d_partial = nullptr, *d_out = nullptr;
-  if (temps.take(&d_partial, (size_t)(n_chunks * n_cells) * sizeof(double)) != hipSuccess) {
+  if (call.take(&d_partial, (size_t)(n_chunks * n_cells) * sizeof(double)) != hipSuccess) {
     gk_set_error("out of device memory for the partial sums of a call bootstrap");
     return GK_ERR_HIP;
   }
-  if (temps.take(&d_out, (size_t)n_cells * sizeof(double)) != hipSuccess) {
+  if (call.take(&d_out, (size_t)n_cells * sizeof(double)) != hipSuccess) {
     gk_set_error("out of device memory for the sums of a call bootstrap");
     return GK_ERR_HIP;
   }
@@ -183,13 +183,9 @@ int gk_weighted_sums(gk_ctx* ctx, gk_dptr d_V, int64_t ld, int64_t n_rows, int32
                                           (int)n_boot, tiles_boot, tiles_sets, d_partial));
   GK_PROF(ctx, "callboot_fold", GK_KERNEL(callboot_fold, dim3((unsigned)((n_cells + kSumThreads - 1) / kSumThreads)),
                                           dim3(kSumThreads), 0, st, d_partial, n_chunks, n_cells, d_out));
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = gk_fetch(ctx, out, d_out, (size_t)n_cells * sizeof(double));
-  if (e != hipSuccess) {
-    gk_fetch_cancel(ctx);
-    gk_set_error("call bootstrap: weighted sums: %s", hipGetErrorString(e));
-    return GK_ERR_HIP;
-  }
+  GK_TRY("call bootstrap: weighted sums", hipGetLastError());
+  GK_TRY("call bootstrap: weighted sums", call.fetch(out, d_out, (size_t)n_cells * sizeof(double)));
+  GK_TRY("call bootstrap: weighted sums", call.wait());
   return GK_OK;
 }
 

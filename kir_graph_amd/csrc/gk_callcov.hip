@@ -39,6 +39,7 @@
 #include <cstring>
 
 #include "gk_called.h"
+#include "gk_calls.h"
 #include "gk_materuns.h"
 
 namespace {
@@ -183,23 +184,18 @@ int gk_call_coverage(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compac
   const int64_t n_tracks = 2 + 2 * (int64_t)n_cols;
   const int64_t slots = n_tracks * (gene_len + 1), total = n_tracks * gene_len;
   hipStream_t st = ctx->stream;
-  GkBlocks temps(ctx);
+  GkCall call(ctx);
   // the depths get a block of their own: written over the scan, word i would be gone before the thread that reads it
   // as slot i = at' of an earlier track's position runs
   uint32_t *diff = nullptr, *scan = nullptr, *depth = nullptr;
-  if (temps.take(&diff, (size_t)slots * sizeof(uint32_t)) != hipSuccess ||
-      temps.take(&scan, (size_t)slots * sizeof(uint32_t)) != hipSuccess) {
+  if (call.take(&diff, (size_t)slots * sizeof(uint32_t)) != hipSuccess ||
+      call.take(&scan, (size_t)slots * sizeof(uint32_t)) != hipSuccess) {
     gk_set_error("out of device memory for the tracks of a call coverage");
     return GK_ERR_HIP;
   }
-  auto fail = [&](hipError_t err) {
-    gk_fetch_cancel(ctx);
-    gk_set_error("call coverage: %s", hipGetErrorString(err));
-    return GK_ERR_HIP;
-  };
-  hipError_t e = hipMemsetAsync(diff, 0, (size_t)slots * sizeof(uint32_t), st);
-  if (e != hipSuccess) return fail(e);
+  GK_TRY("call coverage", hipMemsetAsync(diff, 0, (size_t)slots * sizeof(uint32_t), st));
   {
+    hipError_t e = hipSuccess;      // of the LDS attribute of a launch
     const GkMateSample s = gk_mate_sample(tab, d_mates, d_compact);
     const dim3 block(kCovThreads);
     const int32_t* rows = gk_ptr<const int32_t>(d_rows);
@@ -243,21 +239,21 @@ int gk_call_coverage(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compac
       GK_CALLED_LAUNCH(n_cols, GK_COV_LAUNCH)
 #undef GK_COV_LAUNCH
     }
-    if (e == hipSuccess) e = hipGetLastError();
+    GK_TRY("call coverage", e);
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(scan, diff, (size_t)slots * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
-  if (e != hipSuccess) return fail(e);
+  GK_TRY("call coverage", hipGetLastError());
+  GK_TRY("call coverage", hipMemcpyAsync(scan, diff, (size_t)slots * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
   const int rc = gk_scan_u32(ctx, scan, slots, nullptr);
   if (rc) return rc;
-  if (temps.take(&depth, (size_t)total * sizeof(uint32_t)) != hipSuccess) {
+  if (call.take(&depth, (size_t)total * sizeof(uint32_t)) != hipSuccess) {
     gk_set_error("out of device memory for the tracks of a call coverage");
     return GK_ERR_HIP;
   }
   GK_PROF(ctx, "callcov_finish", GK_KERNEL(callcov_finish, dim3((unsigned)((total + kCovThreads - 1) / kCovThreads)),
                                            dim3(kCovThreads), 0, st, scan, diff, gene_len, total, depth));
-  e = hipGetLastError();
-  if (e == hipSuccess) e = gk_fetch(ctx, depth_out, depth, (size_t)total * sizeof(uint32_t));
-  if (e != hipSuccess) return fail(e);
+  GK_TRY("call coverage", hipGetLastError());
+  GK_TRY("call coverage", call.fetch(depth_out, depth, (size_t)total * sizeof(uint32_t)));
+  GK_TRY("call coverage", call.wait());
   return GK_OK;
 }
 

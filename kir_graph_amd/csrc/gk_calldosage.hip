@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "gk_called.h"
+#include "gk_calls.h"
 #include "gk_env.h"
 
 namespace {
@@ -244,15 +245,16 @@ int gk_call_patterns(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, 
   const size_t n = (size_t)n_slots, n_key_tables = wide ? 3 : 1;
   const size_t key_bytes = n_key_tables * n * sizeof(unsigned long long), count_bytes = (n + 2) * sizeof(unsigned long long);
   hipStream_t st = ctx->stream;
-  GkBlocks temps(ctx);
+  std::vector<unsigned long long> keys, counts;      // before the record that delivers into them (GkCall::fetch)
+  GkCall call(ctx);
   unsigned long long *d_keys = nullptr, *d_counts = nullptr;      // [fin | lo | hi]; [counts | unplaced, out of range]
-  if (temps.take(&d_keys, key_bytes) != hipSuccess || temps.take(&d_counts, count_bytes) != hipSuccess) {
+  if (call.take(&d_keys, key_bytes) != hipSuccess || call.take(&d_counts, count_bytes) != hipSuccess) {
     gk_set_error("out of device memory for the pattern tables of a call dosage");
     return GK_ERR_HIP;
   }
-  hipError_t e = hipMemsetAsync(d_keys, 0xFF, key_bytes, st);
-  if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, count_bytes, st);
-  if (e == hipSuccess) {
+  GK_TRY("call patterns", hipMemsetAsync(d_keys, 0xFF, key_bytes, st));
+  GK_TRY("call patterns", hipMemsetAsync(d_counts, 0, count_bytes, st));
+  {
     PatGlobal g;
     g.fin = d_keys; g.lo = wide ? d_keys + n : d_keys; g.hi = wide ? d_keys + 2 * n : d_keys;
     g.counts = d_counts; g.counters = d_counts + n; g.mask = (uint32_t)(n - 1);
@@ -263,17 +265,13 @@ int gk_call_patterns(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, 
   GK_PROF(ctx, "calldosage_patterns", GK_KERNEL(calldosage_patterns<KT>, grid, block, 0, st, m, ldm, n_rows, pc, (int)n_cols, hash_mask, g))
     GK_CALLED_LAUNCH(n_cols, GK_PAT_LAUNCH)
 #undef GK_PAT_LAUNCH
-    e = hipGetLastError();
   }
-  std::vector<unsigned long long> keys(n_key_tables * n), counts(n + 2);
-  if (e == hipSuccess) e = gk_fetch_queue(ctx, keys.data(), d_keys, key_bytes);
-  if (e == hipSuccess) e = gk_fetch_queue(ctx, counts.data(), d_counts, count_bytes);
-  if (e == hipSuccess) e = gk_fetch_wait(ctx);
-  if (e != hipSuccess) {
-    gk_fetch_cancel(ctx);
-    gk_set_error("call patterns: %s", hipGetErrorString(e));
-    return GK_ERR_HIP;
-  }
+  GK_TRY("call patterns", hipGetLastError());
+  keys.resize(n_key_tables * n);      // sized while the kernel runs
+  counts.resize(n + 2);
+  GK_TRY("call patterns", call.fetch(keys.data(), d_keys, key_bytes));
+  GK_TRY("call patterns", call.fetch(counts.data(), d_counts, count_bytes));
+  GK_TRY("call patterns", call.wait());
   int64_t found = 0;
   for (size_t s = 0; s < n; ++s) {
     if (keys[s] == kPatEmpty || counts[s] == 0) continue;

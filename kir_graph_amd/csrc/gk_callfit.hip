@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "gk_called.h"
+#include "gk_calls.h"
 
 namespace {
 
@@ -247,14 +248,15 @@ int gk_call_fit(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32
   });
   if (bad) return bad;
   hipStream_t st = ctx->stream;
-  GkBlocks temps(ctx);
+  unsigned long long host[kFitCounters];      // before the record that delivers into it (GkCall::fetch)
+  GkCall call(ctx);
   unsigned long long* d_out = nullptr;
-  if (temps.take(&d_out, kFitCounters * sizeof(unsigned long long)) != hipSuccess) {
+  if (call.take(&d_out, kFitCounters * sizeof(unsigned long long)) != hipSuccess) {
     gk_set_error("out of device memory for the counters of a call fit");
     return GK_ERR_HIP;
   }
-  hipError_t e = hipMemsetAsync(d_out, 0, kFitCounters * sizeof(unsigned long long), st);
-  if (e == hipSuccess) {
+  GK_TRY("call fit", hipMemsetAsync(d_out, 0, kFitCounters * sizeof(unsigned long long), st));
+  {
     const int64_t chunks = (n_rows + kFitChunk - 1) / kFitChunk;
     const dim3 grid((unsigned)std::min(chunks, kFitMaxGroups)), block(kFitThreads);
     const uint8_t* m = gk_ptr<const uint8_t>(d_miss8);
@@ -263,15 +265,10 @@ int gk_call_fit(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int32
   GK_PROF(ctx, "callfit_profile", GK_KERNEL(callfit_profile<KT>, grid, block, 0, st, m, ldm, n_rows, fc, (int)n_cols, d_out, dm))
     GK_CALLED_LAUNCH(n_cols, GK_FIT_LAUNCH)
 #undef GK_FIT_LAUNCH
-    e = hipGetLastError();
   }
-  unsigned long long host[kFitCounters];
-  if (e == hipSuccess) e = gk_fetch(ctx, host, d_out, sizeof(host));
-  if (e != hipSuccess) {
-    gk_fetch_cancel(ctx);
-    gk_set_error("call fit: %s", hipGetErrorString(e));
-    return GK_ERR_HIP;
-  }
+  GK_TRY("call fit", hipGetLastError());
+  GK_TRY("call fit", call.fetch(host, d_out, sizeof(host)));
+  GK_TRY("call fit", call.wait());
   for (int i = 0; i < kFitBins; ++i) hist_out[i] = host[i];
   m_out[0] = host[kFitBins];
   for (int i = 0; i < 3 * n_cols; ++i) col_out[i] = host[kFitBins + 1 + i];
@@ -293,24 +290,18 @@ int gk_call_fit_extra(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows,
   hipStream_t st = ctx->stream;
   unsigned long long* d_with = nullptr;
   const size_t bytes = (size_t)n_table_cols * sizeof(unsigned long long);
-  GkBlocks temps(ctx);
-  if (temps.take(&d_with, bytes) != hipSuccess) {
+  GkCall call(ctx);
+  if (call.take(&d_with, bytes) != hipSuccess) {
     gk_set_error("out of device memory for the sums of a call fit");
     return GK_ERR_HIP;
   }
-  hipError_t e = hipMemsetAsync(d_with, 0, bytes, st);
-  if (e == hipSuccess) {
-    GK_PROF(ctx, "callfit_extra", GK_KERNEL(callfit_extra, dim3((unsigned)(n_tiles * n_slices)), dim3(kFitThreads), 0, st,
-                                            gk_ptr<const uint8_t>(d_miss8), ldm, n_rows, (int)n_table_cols,
-                                            gk_ptr<const uint8_t>(d_min), (int)n_tiles, (int)n_slices, d_with));
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = gk_fetch(ctx, with_out, d_with, bytes);
-  if (e != hipSuccess) {
-    gk_fetch_cancel(ctx);
-    gk_set_error("call fit: extra copies: %s", hipGetErrorString(e));
-    return GK_ERR_HIP;
-  }
+  GK_TRY("call fit: extra copies", hipMemsetAsync(d_with, 0, bytes, st));
+  GK_PROF(ctx, "callfit_extra", GK_KERNEL(callfit_extra, dim3((unsigned)(n_tiles * n_slices)), dim3(kFitThreads), 0, st,
+                                          gk_ptr<const uint8_t>(d_miss8), ldm, n_rows, (int)n_table_cols,
+                                          gk_ptr<const uint8_t>(d_min), (int)n_tiles, (int)n_slices, d_with));
+  GK_TRY("call fit: extra copies", hipGetLastError());
+  GK_TRY("call fit: extra copies", call.fetch(with_out, d_with, bytes));
+  GK_TRY("call fit: extra copies", call.wait());
   return GK_OK;
 }
 

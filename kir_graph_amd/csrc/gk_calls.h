@@ -2,6 +2,9 @@
 // result on the context's stream and returns at once; `collect`, after ONE stream synchronisation that may cover the
 // calls of many genes (gk_fetch_wait), unpacks the result and releases the temporaries.  The blocking entry points of
 // the C ABI (gk_bound_step, gk_setsum, gk_fraction, gk_setsum_few) are enqueue + gk_call_wait + collect.
+// A blocking entry point that delivers into its caller's arrays (the call reports, the bootstraps, the novel-variant
+// step) holds a GkCall on its stack instead: take / send / fetch ... wait(), and every return before the wait is a plain
+// return -- the record's drop gives the blocks back and cancels what was queued.  It frees and cancels nothing by hand.
 #pragma once
 #include <utility>
 #include <vector>
@@ -19,6 +22,7 @@
 // done() once it has been waited for (GeneSearch::discard), as `collect` does.
 struct GkCall {
   GkCall() = default;
+  explicit GkCall(gk_ctx* ctx) { begin(ctx); }
   GkCall(const GkCall&) = delete;
   GkCall& operator=(const GkCall&) = delete;
   GkCall(GkCall&& o) noexcept { *this = std::move(o); }
@@ -48,6 +52,8 @@ struct GkCall {
   hipError_t take(T** p, size_t bytes) { return blocks_.take(p, bytes); }
   // the block stays out when the call is over (it has another owner now)
   void keep(const void* p) { blocks_.keep(p); }
+  // the owner itself, for a helper that takes its scratch through one (gk_compact_enqueue)
+  GkBlocks& blocks() { return blocks_; }
   // host -> device; `src` may be reused at once (a transfer too large for the pinned ring goes straight from `src`, so
   // the stream is waited for)
   hipError_t send(void* dst_dev, const void* src, size_t bytes) {
@@ -62,6 +68,22 @@ struct GkCall {
     due_ = nullptr;
     pending_ = true;               // also when the copy fails: the delivery may be registered by then
     return gk_fetch_queue(ctx_, dst_, src, dst_bytes_);
+  }
+  // device -> host into memory the record does NOT own, delivered by wait().  THE lifetime rule of a destination: it is the
+  // caller's memory, or an object declared BEFORE the record -- that one is destroyed after the record, whose drop has
+  // cancelled the delivery by then.  Pending from here on, also when the queue fails (as in finish)
+  hipError_t fetch(void* dst, const void* src_dev, size_t bytes) {
+    pending_ = true;
+    return gk_fetch_queue(ctx_, dst, src_dev, bytes);
+  }
+  // the entry point queued a copy itself that reads or writes memory under the rule above (a gk_send too large for the
+  // ring, a strided copy into the caller's array): a drop drains the stream before that memory may go away
+  void expect() { pending_ = true; }
+  // the stream is drained and everything queued is delivered; not pending afterwards whatever the result (the context's
+  // list is cleared either way).  The blocks stay until the record goes
+  hipError_t wait() {
+    pending_ = false;
+    return gk_fetch_wait(ctx_);
   }
   // the stream has passed the call and its result is delivered (collect), or was never asked for: blocks back to the pool
   void done() {
@@ -123,6 +145,16 @@ static inline int gk_call_wait(gk_ctx* ctx, GkCall& call, int rc, const char* wh
   if (rc != GK_OK) call.drop();
   return rc;
 }
+
+// GK_HIP with the message of an entry point: `what` ("call fit", "EM bootstrap: queueing the draws") comes first
+#define GK_TRY(what, call)                                         \
+  do {                                                             \
+    const hipError_t e_ = (call);                                  \
+    if (e_ != hipSuccess) {                                        \
+      gk_set_error("%s: %s", what, hipGetErrorString(e_));         \
+      return GK_ERR_HIP;                                           \
+    }                                                              \
+  } while (0)
 
 // ---- gk_bound.hip: integer bound of a step (gk_bound_step)
 struct GkBoundCall : GkCallOf<char> {      // back: [SelState | idx[cap] | m[cap]]

@@ -37,6 +37,7 @@
 #include <algorithm>
 
 #include "gk_called.h"
+#include "gk_calls.h"
 
 namespace {
 
@@ -290,21 +291,22 @@ int gk_call_swap(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int3
   GK_REQUIRE(n_tiles * n_slices <= 0x7FFFFFFFll, "call swap: too many columns for one call");
 
   hipStream_t st = ctx->stream;
-  GkBlocks temps(ctx);
+  unsigned long long head[2] = {0, 0};      // before the record that delivers into it (GkCall::fetch)
+  GkCall call(ctx);
   const int64_t A = n_table_cols;
   const size_t n_counters = (size_t)(2 + 2 * A + 2 * (int64_t)n_cols * A);      // M, out of range, then callswap_sums' planes
   unsigned long long* d_out = nullptr;
-  if (temps.take(&d_out, n_counters * sizeof(unsigned long long)) != hipSuccess) {
+  if (call.take(&d_out, n_counters * sizeof(unsigned long long)) != hipSuccess) {
     gk_set_error("out of device memory for the counters of a call swap");
     return GK_ERR_HIP;
   }
   uint8_t* state = gk_ptr<uint8_t>(d_state);
-  if (state == nullptr && temps.take(&state, 3 * (size_t)ldm) != hipSuccess) {
+  if (state == nullptr && call.take(&state, 3 * (size_t)ldm) != hipSuccess) {
     gk_set_error("out of device memory for the row state of a call swap");
     return GK_ERR_HIP;
   }
-  hipError_t e = hipMemsetAsync(d_out, 0, n_counters * sizeof(unsigned long long), st);
-  if (e == hipSuccess) {
+  GK_TRY("call swap", hipMemsetAsync(d_out, 0, n_counters * sizeof(unsigned long long), st));
+  {
     const dim3 grid_rows((unsigned)std::min(chunks, kSwapMaxGroups)), grid_sums((unsigned)(n_tiles * n_slices)), block(kSwapThreads);
     const uint8_t* m = gk_ptr<const uint8_t>(d_miss8);
 #define GK_SWAP_LAUNCH(KT)                                                                                                   \
@@ -317,21 +319,15 @@ int gk_call_swap(gk_ctx* ctx, gk_dptr d_miss8, int64_t ldm, int64_t n_rows, int3
   } while (0)
     GK_CALLED_LAUNCH(n_cols, GK_SWAP_LAUNCH)
 #undef GK_SWAP_LAUNCH
-    e = hipGetLastError();
   }
-  unsigned long long head[2] = {0, 0};
+  GK_TRY("call swap", hipGetLastError());
   const size_t plane = (size_t)A * sizeof(unsigned long long);
-  if (e == hipSuccess) e = gk_fetch_queue(ctx, head, d_out, sizeof(head));
-  if (e == hipSuccess) e = gk_fetch_queue(ctx, gain_out, d_out + 2, plane);
-  if (e == hipSuccess) e = gk_fetch_queue(ctx, against_out, d_out + 2 + A, plane);
-  if (e == hipSuccess) e = gk_fetch_queue(ctx, loss_out, d_out + 2 + 2 * A, plane * n_cols);
-  if (e == hipSuccess) e = gk_fetch_queue(ctx, for_out, d_out + 2 + (2 + (int64_t)n_cols) * A, plane * n_cols);
-  if (e == hipSuccess) e = gk_fetch_wait(ctx);
-  if (e != hipSuccess) {
-    gk_fetch_cancel(ctx);
-    gk_set_error("call swap: %s", hipGetErrorString(e));
-    return GK_ERR_HIP;
-  }
+  GK_TRY("call swap", call.fetch(head, d_out, sizeof(head)));
+  GK_TRY("call swap", call.fetch(gain_out, d_out + 2, plane));
+  GK_TRY("call swap", call.fetch(against_out, d_out + 2 + A, plane));
+  GK_TRY("call swap", call.fetch(loss_out, d_out + 2 + 2 * A, plane * n_cols));
+  GK_TRY("call swap", call.fetch(for_out, d_out + 2 + (2 + (int64_t)n_cols) * A, plane * n_cols));
+  GK_TRY("call swap", call.wait());
   m_out[0] = head[0];
   out_of_range_out[0] = head[1];
   return GK_OK;

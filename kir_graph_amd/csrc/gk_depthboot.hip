@@ -28,7 +28,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "gk_blocks.h"
+#include "gk_calls.h"
 #include "gk_materuns.h"
 
 namespace {
@@ -237,40 +237,34 @@ int gk_depth_weighted(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compa
   // replicates of one slice: their difference arrays and the scan copy stay within the budget
   const int64_t slice = std::max<int64_t>(1, std::min<int64_t>(n_boot, (int64_t)(depthw_budget() / (2 * sizeof(uint32_t) * (size_t)slots))));
   hipStream_t st = ctx->stream;
-  GkBlocks temps(ctx);
+  GkCall call(ctx);
   uint32_t *diff = nullptr, *scan = nullptr, *d_stat = nullptr;
   int64_t *d_off = nullptr, *d_rank = nullptr;
   unsigned long long* d_sum = nullptr;
   uint8_t* d_sel = nullptr;
-  // every way out but the last drains the stream: sel / rank / gene_off and depth_out are the caller's again
-  auto fail = [&](hipError_t err) {
-    gk_fetch_cancel(ctx);
-    gk_set_error("weighted depth: %s", hipGetErrorString(err));
-    return GK_ERR_HIP;
-  };
-  if (temps.take(&diff, (size_t)slice * slots * sizeof(uint32_t)) != hipSuccess ||
-      temps.take(&scan, (size_t)slice * slots * sizeof(uint32_t)) != hipSuccess ||
-      temps.take(&d_off, (size_t)(n_gene + 1) * sizeof(int64_t)) != hipSuccess ||
-      temps.take(&d_rank, (size_t)2 * n_gene * sizeof(int64_t)) != hipSuccess ||
-      temps.take(&d_stat, 2 * n_cells * sizeof(uint32_t)) != hipSuccess ||
-      temps.take(&d_sum, n_cells * sizeof(unsigned long long)) != hipSuccess ||
-      (sel && temps.take(&d_sel, (size_t)total) != hipSuccess)) {
-    gk_fetch_cancel(ctx);
+  if (call.take(&diff, (size_t)slice * slots * sizeof(uint32_t)) != hipSuccess ||
+      call.take(&scan, (size_t)slice * slots * sizeof(uint32_t)) != hipSuccess ||
+      call.take(&d_off, (size_t)(n_gene + 1) * sizeof(int64_t)) != hipSuccess ||
+      call.take(&d_rank, (size_t)2 * n_gene * sizeof(int64_t)) != hipSuccess ||
+      call.take(&d_stat, 2 * n_cells * sizeof(uint32_t)) != hipSuccess ||
+      call.take(&d_sum, n_cells * sizeof(unsigned long long)) != hipSuccess ||
+      (sel && call.take(&d_sel, (size_t)total) != hipSuccess)) {
     gk_set_error("out of device memory for the replicates of a weighted depth");
     return GK_ERR_HIP;
   }
-  hipError_t e = gk_send(ctx, d_off, gene_off, (size_t)(n_gene + 1) * sizeof(int64_t));
-  if (e == hipSuccess) e = gk_send(ctx, d_rank, rank, (size_t)2 * n_gene * sizeof(int64_t));
-  if (e == hipSuccess && sel) e = gk_send(ctx, d_sel, sel, (size_t)total);      // once, for every slice
-  if (e != hipSuccess) return fail(e);
+  GK_TRY("weighted depth", call.send(d_off, gene_off, (size_t)(n_gene + 1) * sizeof(int64_t)));      // at most 257 words
+  GK_TRY("weighted depth", call.send(d_rank, rank, (size_t)2 * n_gene * sizeof(int64_t)));
+  // From here on the stream may read `sel` (a selection too large for the ring is copied straight from it, and the wait
+  // at the end covers that copy) and write `depth_out`: a way out before that wait drains the stream
+  call.expect();
+  if (sel) GK_TRY("weighted depth", gk_send(ctx, d_sel, sel, (size_t)total));      // once, for every slice
   const GkMateSample s = gk_mate_sample(tab, d_mates, d_compact);
   const uint32_t* W = gk_ptr<const uint32_t>(d_W);
   const unsigned mate_groups = (unsigned)((2 * tab->n_valid + kDwThreads - 1) / kDwThreads);
   for (int64_t b0 = 0; b0 < n_boot; b0 += slice) {
     const int nb = (int)std::min<int64_t>(slice, n_boot - b0);
     const int64_t n = (int64_t)nb * slots;
-    e = hipMemsetAsync(diff, 0, (size_t)n * sizeof(uint32_t), st);
-    if (e != hipSuccess) return fail(e);
+    GK_TRY("weighted depth", hipMemsetAsync(diff, 0, (size_t)n * sizeof(uint32_t), st));
     const dim3 grid(mate_groups, (unsigned)((nb + kBootPerThread - 1) / kBootPerThread));
     if (s.c_off)
       GK_PROF(ctx, "depthw_mark", GK_KERNEL(depthw_mark<true>, grid, dim3(kDwThreads), 0, st, s, (int)multiple, d_off, (int)n_gene,
@@ -278,25 +272,23 @@ int gk_depth_weighted(gk_ctx* ctx, gk_tab* tab, gk_dptr d_mates, gk_dptr d_compa
     else
       GK_PROF(ctx, "depthw_mark", GK_KERNEL(depthw_mark<false>, grid, dim3(kDwThreads), 0, st, s, (int)multiple, d_off, (int)n_gene,
                                             W + b0 * ldw, ldw, nb, slots, diff));
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(scan, diff, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return fail(e);
+    GK_TRY("weighted depth", hipGetLastError());
+    GK_TRY("weighted depth", hipMemcpyAsync(scan, diff, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     const int rc = gk_scan_u32(ctx, scan, n, nullptr);
-    if (rc) { gk_fetch_cancel(ctx); return rc; }
+    if (rc) return rc;
     GK_PROF(ctx, "depthw_finish", GK_KERNEL(depthw_finish, dim3((unsigned)((n + kDwThreads - 1) / kDwThreads)), dim3(kDwThreads), 0,
                                             st, scan, diff, n));
     GK_PROF(ctx, "depthw_select", GK_KERNEL(depthw_select, dim3((unsigned)n_gene, (unsigned)nb), dim3(kDwThreads), 0, st, diff, slots,
                                             d_off, d_sel, d_rank, d_stat + 2 * b0 * n_gene, d_sum + b0 * n_gene));
-    e = hipGetLastError();
-    if (e == hipSuccess && depth_out)      // the tracks without their extra slots (the tests ask for them)
-      e = hipMemcpy2DAsync(depth_out + b0 * total, (size_t)total * sizeof(uint32_t), diff, (size_t)slots * sizeof(uint32_t),
-                           (size_t)total * sizeof(uint32_t), (size_t)nb, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) return fail(e);
+    GK_TRY("weighted depth", hipGetLastError());
+    if (depth_out)      // the tracks without their extra slots (the tests ask for them)
+      GK_TRY("weighted depth",
+             hipMemcpy2DAsync(depth_out + b0 * total, (size_t)total * sizeof(uint32_t), diff, (size_t)slots * sizeof(uint32_t),
+                              (size_t)total * sizeof(uint32_t), (size_t)nb, hipMemcpyDeviceToHost, st));
   }
-  e = gk_fetch_queue(ctx, stat_out, d_stat, 2 * n_cells * sizeof(uint32_t));
-  if (e == hipSuccess) e = gk_fetch_queue(ctx, sum_out, d_sum, n_cells * sizeof(uint64_t));
-  if (e == hipSuccess) e = gk_fetch_wait(ctx);
-  if (e != hipSuccess) return fail(e);
+  GK_TRY("weighted depth", call.fetch(stat_out, d_stat, 2 * n_cells * sizeof(uint32_t)));
+  GK_TRY("weighted depth", call.fetch(sum_out, d_sum, n_cells * sizeof(uint64_t)));
+  GK_TRY("weighted depth", call.wait());
   return GK_OK;
 }
 

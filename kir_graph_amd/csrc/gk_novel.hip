@@ -24,7 +24,7 @@
 // (novel_discover.py:139-143).  All counts are integers: the result does not depend on the order of arrival.
 #include <climits>
 
-#include "gk_blocks.h"
+#include "gk_calls.h"
 
 namespace {
 
@@ -177,23 +177,17 @@ int gk_novel_assign(gk_ctx* ctx, gk_dptr d_probs, int64_t n_rows, int32_t n_cols
     return GK_OK;
   }
   GK_REQUIRE(d_probs && d_code, "null device pointer");
-  GkBlocks temps(ctx);
+  GkCall call(ctx);
   uint32_t *d_count = nullptr, *d_cols = nullptr;
-  GK_HIP(temps.take(&d_count, sizeof(uint32_t) * 2 * bins));
+  GK_HIP(call.take(&d_count, sizeof(uint32_t) * 2 * bins));
   int32_t* d_first = (int32_t*)(d_count + bins);
-  if (temps.take(&d_cols, sizeof(uint32_t) * kMaxEntries) != hipSuccess) {
+  if (call.take(&d_cols, sizeof(uint32_t) * kMaxEntries) != hipSuccess) {
     gk_set_error("device allocation failed");
     return GK_ERR_HIP;
   }
-  auto fail = [&](const char* what) {
-    gk_fetch_cancel(ctx);            // nothing queued may be delivered into the caller's buffers after we return
-    gk_set_error("%s", what);
-    return GK_ERR_HIP;
-  };
-  if (hipMemsetAsync(d_count, 0, sizeof(uint32_t) * bins, ctx->stream) != hipSuccess ||
-      hipMemsetAsync(d_first, 0x7F, sizeof(int32_t) * bins, ctx->stream) != hipSuccess ||
-      gk_send(ctx, d_cols, col_entries, sizeof(uint32_t) * n_cols) != hipSuccess)
-    return fail("novel_assign: set-up failed");
+  GK_TRY("novel_assign: set-up failed", hipMemsetAsync(d_count, 0, sizeof(uint32_t) * bins, ctx->stream));
+  GK_TRY("novel_assign: set-up failed", hipMemsetAsync(d_first, 0x7F, sizeof(int32_t) * bins, ctx->stream));
+  GK_TRY("novel_assign: set-up failed", call.send(d_cols, col_entries, sizeof(uint32_t) * n_cols));      // at most 16 words
   const bool lds = n_cols <= kLdsCols;
   GK_PROF(ctx, "novel_assign", {
     if (lds)
@@ -203,12 +197,11 @@ int gk_novel_assign(gk_ctx* ctx, gk_dptr d_probs, int64_t n_rows, int32_t n_cols
       GK_KERNEL(novel_assign<false>, dim3(nblk(n_rows)), dim3(kThreads), 0, ctx->stream, gk_ptr<double>(d_probs), n_rows,
                 (int)n_cols, d_cols, gk_ptr<uint16_t>(d_code), d_count, d_first);
   });
-  if (hipGetLastError() != hipSuccess) return fail("novel_assign: launch failed");
-  if (gk_fetch_queue(ctx, count_out, d_count, sizeof(uint32_t) * bins) != hipSuccess ||
-      gk_fetch_queue(ctx, first_out, d_first, sizeof(int32_t) * bins) != hipSuccess ||
-      (code_out && gk_fetch_queue(ctx, code_out, gk_ptr<void>(d_code), sizeof(uint16_t) * n_rows) != hipSuccess) ||
-      gk_fetch_wait(ctx) != hipSuccess)
-    return fail("novel_assign: fetch failed");
+  GK_TRY("novel_assign: launch failed", hipGetLastError());
+  GK_TRY("novel_assign: fetch failed", call.fetch(count_out, d_count, sizeof(uint32_t) * bins));
+  GK_TRY("novel_assign: fetch failed", call.fetch(first_out, d_first, sizeof(int32_t) * bins));
+  if (code_out) GK_TRY("novel_assign: fetch failed", call.fetch(code_out, gk_ptr<void>(d_code), sizeof(uint16_t) * n_rows));
+  GK_TRY("novel_assign: fetch failed", call.wait());
   return GK_OK;
 }
 
@@ -233,65 +226,61 @@ int gk_novel_confusion(gk_ctx* ctx, gk_tab* tab, gk_dptr d_rows, int64_t n_rows,
   if (n_rows == 0 || n_slots == 0 || nvt == 0) return GK_OK;
   GK_REQUIRE(d_rows && d_code && d_vflag && (d_carry || vend == vbeg), "null device pointer");
   const int64_t n_cells = nvt * n_slots;
-  GkBlocks temps(ctx);
-  auto take = [&](auto** p, size_t bytes) { return temps.take(p, bytes) == hipSuccess; };
-  auto fail = [&](const char* what) {
-    gk_fetch_cancel(ctx);            // drop what is queued: the caller's buffers may go away
-    gk_set_error("%s", what);
-    return GK_ERR_HIP;
-  };
+  uint32_t found = 0;              // before the record that delivers into it (GkCall::fetch)
+  GkCall call(ctx);
+  const char* const no_memory = "novel_confusion: device allocation failed";
   uint32_t* d_cnt = nullptr;
   unsigned long long *d_key = nullptr, *d_tot = nullptr;
   int32_t* d_meta = nullptr;       // entry_col[16], entry_slot[16]
   uint32_t* d_n = nullptr;
-  if (!take(&d_cnt, sizeof(uint32_t) * n_cells) || !take(&d_key, sizeof(uint64_t) * n_cells) ||
-      !take(&d_tot, sizeof(uint64_t) * kStats * n_slots) || !take(&d_meta, sizeof(int32_t) * 2 * kMaxEntries) ||
-      !take(&d_n, sizeof(uint32_t)))
-    return fail("novel_confusion: device allocation failed");
+  GK_TRY(no_memory, call.take(&d_cnt, sizeof(uint32_t) * n_cells));
+  GK_TRY(no_memory, call.take(&d_key, sizeof(uint64_t) * n_cells));
+  GK_TRY(no_memory, call.take(&d_tot, sizeof(uint64_t) * kStats * n_slots));
+  GK_TRY(no_memory, call.take(&d_meta, sizeof(int32_t) * 2 * kMaxEntries));
+  GK_TRY(no_memory, call.take(&d_n, sizeof(uint32_t)));
   int32_t meta[2 * kMaxEntries];
   for (int e = 0; e < kMaxEntries; ++e) {
     meta[e] = e < n_entries ? entry_col[e] : 0;
     meta[kMaxEntries + e] = e < n_entries ? entry_slot[e] : -1;
   }
-  if (hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * n_cells, ctx->stream) != hipSuccess ||
-      hipMemsetAsync(d_key, 0xFF, sizeof(uint64_t) * n_cells, ctx->stream) != hipSuccess ||
-      hipMemsetAsync(d_tot, 0, sizeof(uint64_t) * kStats * n_slots, ctx->stream) != hipSuccess ||
-      hipMemsetAsync(d_n, 0, sizeof(uint32_t), ctx->stream) != hipSuccess ||
-      gk_send(ctx, d_meta, meta, sizeof(meta)) != hipSuccess)
-    return fail("novel_confusion: set-up failed");
+  GK_TRY("novel_confusion: set-up failed", hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * n_cells, ctx->stream));
+  GK_TRY("novel_confusion: set-up failed", hipMemsetAsync(d_key, 0xFF, sizeof(uint64_t) * n_cells, ctx->stream));
+  GK_TRY("novel_confusion: set-up failed", hipMemsetAsync(d_tot, 0, sizeof(uint64_t) * kStats * n_slots, ctx->stream));
+  GK_TRY("novel_confusion: set-up failed", hipMemsetAsync(d_n, 0, sizeof(uint32_t), ctx->stream));
+  GK_TRY("novel_confusion: set-up failed", call.send(d_meta, meta, sizeof(meta)));      // 128 bytes
   GK_PROF(ctx, "novel_confusion",
           GK_KERNEL(novel_confusion, dim3(nblk(n_rows)), dim3(kThreads), 0, ctx->stream, gk_ptr<int32_t>(d_rows), n_rows,
                     gk_ptr<uint16_t>(d_code), tab->d_off, tab->d_ids, gk_ptr<uint8_t>(d_vflag), vbeg, vend - vbeg,
                     gk_ptr<uint32_t>(d_carry), d_meta, d_meta + kMaxEntries, n_slots, nvt, d_tot, d_cnt, d_key));
-  if (hipGetLastError() != hipSuccess) return fail("novel_confusion: launch failed");
+  GK_TRY("novel_confusion: launch failed", hipGetLastError());
   // first wait: the totals and the number of counted pairs
   int32_t* d_slot = nullptr;
   int32_t* d_ord = nullptr;
   uint32_t* d_count = nullptr;
   unsigned long long* d_okey = nullptr;
   const int64_t cap = std::min<int64_t>(n_cells, std::max<int64_t>(max_out, 1));
-  if (!take(&d_slot, sizeof(int32_t) * cap) || !take(&d_ord, sizeof(int32_t) * cap) ||
-      !take(&d_count, sizeof(uint32_t) * cap) || !take(&d_okey, sizeof(uint64_t) * cap))
-    return fail("novel_confusion: device allocation failed");
+  GK_TRY(no_memory, call.take(&d_slot, sizeof(int32_t) * cap));
+  GK_TRY(no_memory, call.take(&d_ord, sizeof(int32_t) * cap));
+  GK_TRY(no_memory, call.take(&d_count, sizeof(uint32_t) * cap));
+  GK_TRY(no_memory, call.take(&d_okey, sizeof(uint64_t) * cap));
   GK_PROF(ctx, "novel_compact",
           GK_KERNEL(novel_compact, dim3(nblk(n_cells)), dim3(kThreads), 0, ctx->stream, d_cnt, d_key, n_cells, nvt, cap,
                     d_n, d_slot, d_ord, d_count, d_okey));
-  if (hipGetLastError() != hipSuccess) return fail("novel_confusion: launch failed");
-  uint32_t found = 0;
-  if (gk_fetch_queue(ctx, totals_out, d_tot, sizeof(uint64_t) * kStats * n_slots) != hipSuccess ||
-      gk_fetch_queue(ctx, &found, d_n, sizeof(uint32_t)) != hipSuccess || gk_fetch_wait(ctx) != hipSuccess)
-    return fail("novel_confusion: fetch failed");
+  GK_TRY("novel_confusion: launch failed", hipGetLastError());
+  GK_TRY("novel_confusion: fetch failed", call.fetch(totals_out, d_tot, sizeof(uint64_t) * kStats * n_slots));
+  GK_TRY("novel_confusion: fetch failed", call.fetch(&found, d_n, sizeof(uint32_t)));
+  GK_TRY("novel_confusion: fetch failed", call.wait());
   *n_out = found;
   if ((int64_t)found > max_out) {
     gk_set_error("novel_confusion: %u counted variants, room for %lld", found, (long long)max_out);
     return GK_ERR_CAPACITY;
   }
-  if (found &&
-      (gk_fetch_queue(ctx, slot_out, d_slot, sizeof(int32_t) * found) != hipSuccess ||
-       gk_fetch_queue(ctx, ord_out, d_ord, sizeof(int32_t) * found) != hipSuccess ||
-       gk_fetch_queue(ctx, count_out, d_count, sizeof(uint32_t) * found) != hipSuccess ||
-       gk_fetch_queue(ctx, key_out, d_okey, sizeof(uint64_t) * found) != hipSuccess || gk_fetch_wait(ctx) != hipSuccess))
-    return fail("novel_confusion: fetch failed");
+  if (!found) return GK_OK;
+  GK_TRY("novel_confusion: fetch failed", call.fetch(slot_out, d_slot, sizeof(int32_t) * found));
+  GK_TRY("novel_confusion: fetch failed", call.fetch(ord_out, d_ord, sizeof(int32_t) * found));
+  GK_TRY("novel_confusion: fetch failed", call.fetch(count_out, d_count, sizeof(uint32_t) * found));
+  GK_TRY("novel_confusion: fetch failed", call.fetch(key_out, d_okey, sizeof(uint64_t) * found));
+  GK_TRY("novel_confusion: fetch failed", call.wait());
   return GK_OK;
 }
 

@@ -306,6 +306,9 @@ hipError_t gk_send(gk_ctx* ctx, void* dst_dev, const void* src, size_t bytes) {
   return hipMemcpyAsync(dst_dev, slot, bytes, hipMemcpyHostToDevice, ctx->stream);
 }
 
+// A copy that could not be queued registers nothing: its entry leaves ctx->fetches again, so no later drain writes to
+// `dst` (which may be a local of a caller that has returned by then).  The ring bytes it took stay taken until the next
+// drain or mark gives them back with the rest.
 hipError_t gk_fetch_queue(gk_ctx* ctx, void* dst, const void* src_dev, size_t bytes) {
   if (!bytes) return hipSuccess;
   if (bytes > kStageDirect) return hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
@@ -313,7 +316,9 @@ hipError_t gk_fetch_queue(gk_ctx* ctx, void* dst, const void* src_dev, size_t by
   hipError_t e = ring_take(ctx, ctx->fetch_ring, (bytes + 63) / 64 * 64, (size_t)8 << 20, &off);
   if (e != hipSuccess) return e;
   ctx->fetches.push_back({dst, off, bytes, ctx->fetch_ring.head});
-  return hipMemcpyAsync((char*)ctx->fetch_ring.base + off, src_dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
+  e = hipMemcpyAsync((char*)ctx->fetch_ring.base + off, src_dev, bytes, hipMemcpyDeviceToHost, ctx->stream);
+  if (e != hipSuccess) ctx->fetches.pop_back();
+  return e;
 }
 
 // A result that a kernel writes ITSELF into the pinned ring (device-visible host memory): no copy is queued -- a copy per

@@ -2,8 +2,8 @@
 // holds (csrc/gk_blocks.h: GkBlocks) on the CPU, under AddressSanitizer.
 // A stand-alone program: it supplies the pool, the two transfer directions and the result ring that the record uses --
 // they count live blocks, cancels and waits, keep the list of pending deliveries, and make the k-th fallible call fail.
-// gk_fetch_wait copies into EVERY pending destination, so a delivery left pointing into a dead record is a sanitizer
-// report.  Built by tests/test_call_record.py with `hipcc --cuda-host-only -Xarch_host -fsanitize=address,undefined`.
+// gk_fetch_wait copies into EVERY pending destination, so a delivery left pointing into a dead record, or into a dead
+// local of a blocking entry point that holds the record on its stack, is a sanitizer report.  Built by tests/test_call_record.py with `hipcc --cuda-host-only -Xarch_host -fsanitize=address,undefined`.
 #include <cstdarg>
 #include <cstdio>
 #include <set>
@@ -58,8 +58,10 @@ hipError_t gk_fetch_direct(gk_ctx*, void* dst, size_t bytes, void** dev) {
 }
 hipError_t gk_fetch_queue(gk_ctx*, void* dst, const void*, size_t bytes) {
   ++g_queued;
-  g_pending.push_back({(char*)dst, bytes});      // registered before the copy is queued, as the ring does
-  return fails() ? hipErrorUnknown : hipSuccess;
+  g_pending.push_back({(char*)dst, bytes});      // follows the runtime (gk_runtime.hip): registered before the copy is
+  if (!fails()) return hipSuccess;               // queued, and taken out again when that fails -- a failed queue leaves
+  g_pending.pop_back();                          // nothing behind
+  return hipErrorUnknown;
 }
 hipError_t gk_fetch_wait(gk_ctx*) {
   ++g_waits;
@@ -205,6 +207,75 @@ void kept_block() {
   gk_pool_free(ctx(), p);
 }
 
+// ---- the shape of a blocking entry point: the record on its stack, deliveries into two arrays of the caller and into a
+// local declared BEFORE the record (the lifetime rule at GkCall::fetch).  take, send, take, "launch", fetch, fetch, an
+// early return between two fetches (a result that has no room), fetch: kBlockingSteps fallible steps, then the wait
+constexpr int kBlockingSteps = 8;
+struct Caller { char a[40], b[24]; bool local_filled; };
+
+bool filled(const char* p, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (p[i] != 0x5A) return false;
+  return true;
+}
+
+int blocking(Caller& out) {
+  const char par[64] = {1};
+  std::vector<char> local(16, 0);
+  GkCall call(ctx());
+  void *x = nullptr, *y = nullptr;
+  GK_HIP(call.take(&x, 100));
+  GK_HIP(call.send(x, par, sizeof(par)));
+  GK_HIP(call.take(&y, 200));
+  GK_HIP(fails() ? hipErrorLaunchFailure : hipSuccess);
+  GK_HIP(call.fetch(out.a, g_device, sizeof(out.a)));
+  GK_HIP(call.fetch(local.data(), g_device, local.size()));
+  if (fails()) return GK_ERR_CAPACITY;
+  GK_HIP(call.fetch(out.b, g_device, sizeof(out.b)));
+  GK_HIP(call.wait());
+  out.local_filled = filled(local.data(), local.size());
+  return GK_OK;
+}
+
+void blocking_entry_point() {
+  for (int k = 1; k <= kBlockingSteps; ++k) {
+    reset(k);
+    Caller out = {};
+    CHECK(blocking(out) != GK_OK);
+    CHECK(g_calls == k);
+    CHECK(g_live.empty());
+    CHECK(g_pending.empty());
+    CHECK(g_cancels == (g_queued ? 1 : 0));        // one cancel once a fetch was reached, none before
+    CHECK(g_waits == 0);
+    CHECK(gk_fetch_wait(ctx()) == hipSuccess);     // a delivery into the dead local would be written here
+  }
+  reset(0);
+  Caller out = {};
+  CHECK(blocking(out) == GK_OK);
+  CHECK(g_calls == kBlockingSteps && g_queued == 3);
+  CHECK(g_waits == 1 && g_cancels == 0 && g_stream_waits == 0);
+  CHECK(filled(out.a, sizeof(out.a)) && filled(out.b, sizeof(out.b)) && out.local_filled);
+  CHECK(g_live.empty() && g_pending.empty());
+  // a queue that failed left nothing registered, before any cancel
+  reset(1);
+  CHECK(gk_fetch_queue(ctx(), out.a, g_device, sizeof(out.a)) != hipSuccess);
+  CHECK(g_pending.empty() && g_cancels == 0);
+  // a copy that the entry point queues itself: the record is told, and a drop drains the stream
+  reset(0);
+  {
+    GkCall call(ctx());
+    call.expect();
+  }
+  CHECK(g_cancels == 1);
+  // ... while a record that has waited drops nothing
+  {
+    GkCall call(ctx());
+    call.expect();
+    CHECK(call.wait() == hipSuccess);
+  }
+  CHECK(g_cancels == 1 && g_waits == 1);
+}
+
 // ---- the bare owner (csrc/gk_blocks.h: GkBlocks), as a host function that takes scratch uses it
 int five_takes(void** kept) {
   GkBlocks temps(ctx());
@@ -295,6 +366,7 @@ int main() {
   large_result();
   large_send();
   kept_block();
+  blocking_entry_point();
   CHECK(g_live.empty());
   owner_failures();
   owner_keep();

@@ -2,7 +2,9 @@
 a stand-alone program with its own pool, transfers and result ring, is built for the host with AddressSanitizer and
 UBSan and run.  It fails an enqueue at every step and lets the record go out of scope (no block out, no delivery left
 pointing into it, the next wait clean), runs the good path on a reused and on a moved record (no cancel, no wait of the
-record's own), and both sides of the limit above which a result, or a parameter block, does not go through a ring."""
+record's own), and both sides of the limit above which a result, or a parameter block, does not go through a ring.  The
+shape of a blocking entry point -- the record on its stack, deliveries into the caller's arrays and into a local declared
+before it -- is failed at every step in the same way."""
 import os
 import shutil
 import subprocess

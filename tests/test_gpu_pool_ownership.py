@@ -464,6 +464,35 @@ def s_call_fit_extra(w):
     return call
 
 
+def s_call_swap(w):
+    """No row state passed in: the call takes its own."""
+    loss, rows_for = np.zeros((2, 3), np.uint64), np.zeros((2, 3), np.uint64)
+    gain, against, m, beyond = (np.zeros(k, np.uint64) for k in (3, 3, 1, 1))
+
+    def call():
+        rc = lib().gk_call_swap(w.dev.ctx, w.miss8.ptr, w.ldm, w.n, 3, w.fit_cols.ctypes.data, 2, loss.ctypes.data,
+                                rows_for.ctypes.data, gain.ctypes.data, against.ctypes.data, m.ctypes.data, beyond.ctypes.data, 0)
+        return rc, lambda: [a.copy() for a in (loss, rows_for, gain, against, m, beyond)]
+    return call
+
+
+def s_call_patterns(w):
+    slots = 64
+    patterns, counts = np.zeros((slots, 16), np.uint8), np.zeros(slots, np.uint64)
+    n, beyond, unplaced = np.zeros(1, np.int64), np.zeros(1, np.uint64), np.zeros(1, np.uint64)
+
+    def call():
+        rc = lib().gk_call_patterns(w.dev.ctx, w.miss8.ptr, w.ldm, w.n, 3, w.fit_cols.ctypes.data, 2, slots, patterns.ctypes.data,
+                                    counts.ctypes.data, n.ctypes.data, beyond.ctypes.data, unplaced.ctypes.data)
+
+        def finish():      # in the order of the hash table's slots, which the schedule may change: sorted by pattern
+            k = int(n[0])
+            order = np.lexsort(patterns[:k, ::-1].T)
+            return [np.array([k]), patterns[:k][order], counts[:k][order], beyond.copy(), unplaced.copy()]
+        return rc, finish
+    return call
+
+
 def s_novel_assign(w):
     code, count, first = np.zeros(w.n, np.uint16), np.zeros(4, np.uint32), np.zeros(4, np.int32)
 
@@ -522,6 +551,8 @@ SCENARIOS = {
     "weighted_sums": s_weighted_sums,
     "call_fit": s_call_fit,
     "call_fit_extra": s_call_fit_extra,
+    "call_swap": s_call_swap,
+    "call_patterns": s_call_patterns,
     "novel_assign": s_novel_assign,
     "novel_confusion": s_novel_confusion,
 }
@@ -556,6 +587,8 @@ TAKES = {
     "weighted_sums": 2,
     "call_fit": 1,
     "call_fit_extra": 1,
+    "call_swap": 2,
+    "call_patterns": 2,
     "novel_assign": 2,
     "novel_confusion": 9,
 }
