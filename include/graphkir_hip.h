@@ -690,6 +690,16 @@ int gk_bam_next(gk_bam* bam, char* text_out, int64_t capacity, int64_t* n_writte
 /* every record, in output order, straight into a packer (created with gk_packer_create): the same pairs
  * and gk_mate records as feeding the rendered text to gk_packer_feed, without producing the text. */
 int gk_bam_pack(gk_bam* bam, struct gk_packer* packer);
+/* gk_bam_pack with the decode of the plain pairs (M and D ops only, nothing beyond gk_mate) in a kernel and the rest
+ * decoded by the packer: the same packer state.  *n_device_pairs / *n_host_pairs: who decoded how many pairs; a file
+ * the route cannot take (2^27 mates or more; stream, tables and records, together with what calls in flight on other
+ * contexts have claimed, beyond half the free device memory) is decoded wholly by the packer (*n_device_pairs == 0).  d_mates_out may be NULL; otherwise, when the packer holds no error,
+ * *d_mates_out is a block of the context's pool (gk_free) with the final 2 x n_pairs records.  Ends synchronised. */
+int gk_bam_pack_device(gk_ctx* ctx, gk_bam* bam, struct gk_packer* packer, gk_dptr* d_mates_out, int64_t* n_device_pairs,
+                       int64_t* n_host_pairs);
+/* the same split with the kernel's decoder run on the ingest threads: the rehearsal of the device route where there
+ * is no GPU and the source of the pair counts a device run is held against; nothing falls back to it */
+int gk_bam_pack_plain_host(gk_bam* bam, struct gk_packer* packer, int64_t* n_plain, int64_t* n_host);
 /* SAM text (header lines + alignment lines) -> BGZF-compressed BAM at `path`: the native form of
  * saveReadsToBam / samtobam (hisat2.py:869-901, `samtools sort`).  coordinate_sort != 0 orders the
  * records by (reference, position), stable, unmapped last, and writes the index `{path}.bai` next to the

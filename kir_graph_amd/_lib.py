@@ -173,6 +173,9 @@ _SIGS = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
                                       C.c_void_p, C.c_void_p]),
     "gk_bam_pack": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gk_bam_pack_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int64)]),
+    "gk_bam_pack_plain_host": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "gk_bam_next": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "gk_compat_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_uint64, C.c_int32, C.c_int32,
                                 C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64]),
@@ -377,6 +380,18 @@ class DeviceBuffer:
         p = C.c_uint64()
         check(lib().gk_malloc(dev.ctx, max(self.nbytes, 16), C.byref(p)))
         self.ptr = p.value
+
+    @classmethod
+    def adopt(cls, dev: "Device", ptr: int, shape, dtype) -> "DeviceBuffer":
+        """A block of ``dev``'s pool that an entry point of the library handed out (``gk_free`` gives it back), as a
+        buffer that owns it from now on."""
+        self = cls.__new__(cls)
+        self.dev = dev
+        self.shape = tuple(int(s) for s in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+        self.dtype = np.dtype(dtype)
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
+        self.ptr = int(ptr)
+        return self
 
     @property
     def size(self) -> int:

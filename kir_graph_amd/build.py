@@ -12,7 +12,7 @@ SOURCES = ["gk_runtime.hip", "gk_scan.hip", "gk_tabulate.hip", "gk_typing.hip", 
            "gk_search.hip", "gk_bound.hip", "gk_em.hip", "gk_cn.hip", "gk_depth.hip", "gk_sampack.cpp", "gk_bamread.cpp", "gk_textout.cpp",
            "gk_comm.cpp", "gk_hostsearch.cpp", "gk_novel.hip", "gk_boot.hip", "gk_callboot.hip", "gk_compat_narrow.hip",
            "gk_callfit.hip", "gk_callcov.hip", "gk_depthboot.hip", "gk_setsum_few.hip", "gk_rowclass.hip",
-           "gk_callswap.hip", "gk_classrows.hip", "gk_calldosage.hip"]
+           "gk_callswap.hip", "gk_classrows.hip", "gk_calldosage.hip", "gk_ingest_decode.hip"]
 
 
 def hipcc() -> str:
@@ -90,6 +90,8 @@ KERNEL_SOURCES = {
     "class_planes": ["gk_classrows.hip", "gk_classrows.h", "gk_common.h"],
     "class_scatter": ["gk_classrows.hip", "gk_classrows.h", "gk_common.h"],
     "class_gather": ["gk_classrows.hip", "gk_classrows.h", "gk_common.h"],
+    "ingest_decode_pairs": ["gk_ingest_decode.hip", "gk_mate_decode.h", "gk_common.h"],
+    "ingest_patch_pairs": ["gk_ingest_decode.hip", "gk_mate_decode.h", "gk_common.h"],
 }
 
 

@@ -34,6 +34,7 @@
 
 #include "gk_env.h"
 #include "gk_ingest.h"
+#include "gk_mate_decode.h"
 #include "graphkir_hip.h"
 
 void gk_set_error(const char* fmt, ...);
@@ -97,6 +98,7 @@ class Pooled {
   T* begin() { return p_; }
   T* end() { return p_ + size_; }
   size_t size() const { return size_; }
+  size_t capacity() const { return cap_; }
   bool empty() const { return size_ == 0; }
   T& operator[](size_t i) { return p_[i]; }
   const T& operator[](size_t i) const { return p_[i]; }
@@ -876,10 +878,15 @@ static int bam_open_impl(const char* path, int32_t name_sorted, gk_bam** out) {
 // The records of an open file as the packer reads them (gk_ingest.h: GkBamRecords).  Only what the packer reads
 // is converted (CIGAR and SEQ to text where they do not go over as they are; NM / MD / Zs / NH from the optional fields).
 void gk_bam_records(gk_bam* b, gk_packer* pk, GkBamRecords& out) {
-  static_assert(sizeof(gk_bam::Rec) == 16, "the layout GkBamRecords promises");
+  // GkBamRecords::recs is read as GkBamRec [n_recs], on the host and, uploaded as it is, by ingest_decode_pairs
+  static_assert(sizeof(gk_bam::Rec) == sizeof(GkBamRec) && alignof(gk_bam::Rec) == alignof(GkBamRec) &&
+                    offsetof(gk_bam::Rec, off) == offsetof(GkBamRec, off) && offsetof(gk_bam::Rec, size) == offsetof(GkBamRec, size) &&
+                    sizeof(GkBamRec) == 16,
+                "the layout GkBamRecords promises");
   const uint8_t* base = b->data.data();
   out.data = base;
   out.data_bytes = b->data.size();
+  out.data_capacity = b->data.capacity();
   out.recs = b->recs.data();
   out.n_recs = (int64_t)b->recs.size();
   out.names_contiguous = b->name_sorted;
@@ -1085,26 +1092,71 @@ static int bam_next_impl(gk_bam* b, char* text_out, int64_t capacity, int64_t* n
 
 }  // extern "C"
 
-// The entry points that allocate with the size of the input: running out of memory is an error code, not an abort
-// (an exception must not cross the C boundary).
+// The entry points that allocate with the size of the input go through gk_guarded (gk_ingest.h).
 template <typename Call>
-static int guarded(const char* what, const Call& call) {
-  try {
-    return call();
-  } catch (const std::bad_alloc&) {
-    gk_set_error("%s: out of host memory", what);
-    return GK_ERR_CAPACITY;
-  } catch (const std::exception& e) {
-    gk_set_error("%s: %s", what, e.what());
-    return GK_ERR_ARG;
-  }
-}
+static int guarded(const char* what, const Call& call) { return gk_guarded(what, call); }
 
 extern "C" int gk_bam_open(const char* path, int32_t name_sorted, gk_bam** out) {
   return guarded("gk_bam_open", [&] { return bam_open_impl(path, name_sorted, out); });
 }
 extern "C" int gk_bam_pack(gk_bam* b, gk_packer* pk) {
   return guarded("gk_bam_pack", [&] { return bam_pack_impl(b, pk); });
+}
+// every record of the table lies inside the stream (a decoder that reads records by their table entries checks it first)
+bool gk_bam_records_inside(const GkBamRecords& r) {
+  const GkBamRec* recs = (const GkBamRec*)r.recs;
+  for (int64_t i = 0; i < r.n_recs; ++i)
+    if (recs[i].off > r.data_bytes || recs[i].size > r.data_bytes - recs[i].off) return false;
+  return true;
+}
+
+// The decoder of the split route that a device ingest runs in a kernel, run on the ingest threads: gk_pair_decode over
+// aligned words (GkWordBytes), as the kernel reads them.  The words are the stream itself when its block starts on a
+// word and holds the last word whole, else a padded copy.
+static int plain_decode_host(const GkBamRecords& r, const GkPairList& pairs, gk_mate* mates_out, uint8_t* verdict_out) {
+  if (!gk_bam_records_inside(r)) return kGkDecoderDeclines;
+  const size_t n_words = (r.data_bytes + 3) / 4;
+  std::vector<uint32_t, GkRawInit<uint32_t>> copy;
+  const uint32_t* words = (const uint32_t*)r.data;
+  if ((uintptr_t)r.data % 4 != 0 || r.data_capacity < 4 * n_words) {
+    copy.resize(n_words);
+    if (n_words) copy[n_words - 1] = 0;
+    if (r.data_bytes) memcpy(copy.data(), r.data, r.data_bytes);
+    words = copy.data();
+  }
+  const GkBamRec* recs = (const GkBamRec*)r.recs;
+  const int64_t n = (int64_t)pairs.size() / 2;
+  const int n_thr = (int)std::max<int64_t>(1, std::min<int64_t>(ingest_threads(), (n + 255) / 256));
+  auto work = [&](int64_t a, int64_t e) {
+    for (int64_t p = a; p < e; ++p) {
+      const GkBamRec& left = recs[pairs[(size_t)(2 * p)]];
+      const GkBamRec& right = recs[pairs[(size_t)(2 * p + 1)]];
+      verdict_out[p] = (uint8_t)gk_pair_decode(GkWordBytes{words}, left.off, left.size, right.off, right.size,
+                                               r.gene_of_ref.data(), (int32_t)r.gene_of_ref.size(), mates_out + 2 * p);
+    }
+  };
+  if (n_thr == 1) {
+    work(0, n);
+  } else {
+    std::vector<std::thread> pool;
+    for (int t = 0; t < n_thr; ++t) pool.emplace_back(work, n * t / n_thr, n * (t + 1) / n_thr);
+    for (auto& th : pool) th.join();
+  }
+  return GK_OK;
+}
+
+// gk_bam_pack through the split route with the shared decoder on the host: the rehearsal of the device route on a
+// machine without a GPU, and the source of the verdict counts a device run is held against (*n_plain pairs taken by
+// the shared decoder, *n_host by the packer).  Not a fallback of anything: nothing calls it but the tests.
+extern "C" int gk_bam_pack_plain_host(gk_bam* b, gk_packer* pk, int64_t* n_plain, int64_t* n_host) {
+  return guarded("gk_bam_pack_plain_host", [&] {
+    if (!b || !pk) { gk_set_error("null handle"); return GK_ERR_ARG; }
+    GkSplit split;
+    const int rc = gk_bam_pack_with(b, pk, plain_decode_host, split);
+    if (n_plain) *n_plain = split.n_plain;
+    if (n_host) *n_host = split.n_pairs - split.n_plain;
+    return rc;
+  });
 }
 extern "C" int gk_bam_next(gk_bam* b, char* text_out, int64_t capacity, int64_t* n_written) {
   return guarded("gk_bam_next", [&] { return bam_next_impl(b, text_out, capacity, n_written); });

@@ -14,7 +14,9 @@
 //                  N bits: rows of different sequences meet in one slot), calldosage_hashbits=N (gk_call_patterns: the hash
 //                  cut to N bits, so that different keys start their probes in one slot), class_bound=on|off|nomem (read per call: the integer bound
 //                  over the pseudo-rows of the row classes wherever a class record exists, or never; nomem: taken, and the
-//                  pool refuses the pseudo-row table, gk_classrows.h); read by the Python side only:
+//                  pool refuses the pseudo-row table, gk_classrows.h), ingest_device_max_bytes=N (gk_bam_pack_device: a file whose
+//                  stream, tables and records take more than N device bytes goes wholly through the host decode; without
+//                  the hook N is half the free device memory); read by the Python side only:
 //                  bam_reader=samtools, ingest_ahead=N
 #pragma once
 #include <cstdlib>

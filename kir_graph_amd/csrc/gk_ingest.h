@@ -8,6 +8,8 @@
 #include <string_view>
 #include <algorithm>
 #include <cstring>
+#include <exception>
+#include <new>
 #include <vector>
 
 #include <chrono>
@@ -17,6 +19,7 @@
 #include <thread>
 
 #include "gk_env.h"
+#include "graphkir_hip.h"
 
 struct gk_packer;
 
@@ -103,15 +106,32 @@ int gk_packer_pair_records(gk_packer* pk, int64_t n, bool names_contiguous,
 int gk_packer_decode_pairs(gk_packer* pk, int64_t first_line, const GkPairList& pairs,
                            const std::function<void(int64_t, GkAlnRecord&)>& full,
                            const std::function<void(int64_t, bool)>& soon);
+// The split route: somebody else (a device ingest) writes the records of most pairs of the list and the packer decodes
+// the rest.  gk_packer_reserve_pairs makes room for the n_pairs pairs of the NEXT list and returns their first slot
+// (nullptr, and nothing changed: no pairs, a buffer of gk_packer_set_output that is too small, an error held);
+// gk_packer_unreserve takes that back when the list is not going to come.
+// gk_packer_decode_subset decodes the pairs which[0] < which[1] < ... (n_which of them, checked: GK_ERR_ARG and the
+// room taken back) of the list into their slots of the whole list, and fills `pair_lines` for every pair of the
+// list; strings, spills, the error and the truncation at the first failing pair are what gk_packer_decode_pairs
+// makes of the same list as long as the other pairs need none of them.  The subset is a (pointer, count) pair:
+// n_which == 0 decodes NOTHING (and still makes the room and fills the lines) whatever the pointer is, null included;
+// "every pair" is n_which == n_pairs, never a null pointer.
+gk_mate* gk_packer_reserve_pairs(gk_packer* pk, int64_t n_pairs);
+void gk_packer_unreserve(gk_packer* pk);
+int gk_packer_decode_subset(gk_packer* pk, int64_t first_line, const GkPairList& pairs, const int64_t* which,
+                            int64_t n_which, const std::function<void(int64_t, GkAlnRecord&)>& full,
+                            const std::function<void(int64_t, bool)>& soon);
 
-// An open BAM file as the packer's callers see it: the inflated stream, the record table in output order ({uint64
-// offset, uint32 size, 4 bytes unused} per record), the file's reference id -> backbone ordinal table for the packer's
+// An open BAM file as the packer's callers see it: the inflated stream, the record table in output order (GkBamRec),
+// the file's reference id -> backbone ordinal table for the packer's
 // index (-1: no backbone) and the three callbacks of gk_packer_feed_records.  The callbacks point into this object and
 // into the file handle: neither may move or go away while they are in use.
 struct gk_bam;
+struct GkBamRec { uint64_t off; uint32_t size; uint32_t unused; };   // a record's bytes are data[off, off + size)
 struct GkBamRecords {
   const uint8_t* data = nullptr;
   size_t data_bytes = 0;
+  size_t data_capacity = 0;        // bytes of the allocation behind `data` (>= data_bytes; what lies behind data_bytes is anything)
   const void* recs = nullptr;
   int64_t n_recs = 0;
   bool names_contiguous = false;
@@ -121,6 +141,67 @@ struct GkBamRecords {
   std::function<void(int64_t, bool)> soon;      // empty when the records lie in reading order
 };
 void gk_bam_records(gk_bam* b, gk_packer* pk, GkBamRecords& out);
+bool gk_bam_records_inside(const GkBamRecords& r);   // every record of the table lies inside the stream
+
+// The split route over an open file: gk_bam_records, gk_packer_pair_records, then `decoder` writes the
+// final records of the pairs it can take into mates_out (2 per pair, the packer's own slots) and one verdict per pair
+// (GK_DECODE_DONE / GK_DECODE_HOST, gk_mate_decode.h; a HOST pair may leave anything in its slots), then
+// gk_packer_decode_subset over the HOST pairs.  The decoder returns GK_OK, an error code (returned as it is, the
+// packer as before the call but for the counts of the pairing) or kGkDecoderDeclines: the file is not for it, and
+// gk_packer_decode_pairs takes the whole list.  The packer afterwards is what gk_bam_pack leaves of the same file.
+using GkPlainDecoder = std::function<int(const GkBamRecords&, const GkPairList&, gk_mate* mates_out, uint8_t* verdict_out)>;
+constexpr int kGkDecoderDeclines = 1;
+struct GkSplit {
+  int64_t n_pairs = 0, n_plain = 0;   // pairs of the list / of them decoded by the decoder
+  std::vector<int64_t> host;          // the pairs the packer decoded itself, ascending (all of them: n_plain == 0)
+  gk_mate* mates = nullptr;           // first slot of the list's pairs in the packer's array (nullptr: no pairs)
+};
+inline int gk_bam_pack_with(gk_bam* b, gk_packer* pk, const GkPlainDecoder& decoder, GkSplit& split) {
+  split = GkSplit();
+  GkBamRecords r;
+  gk_bam_records(b, pk, r);
+  GkPairList pairs;
+  int64_t first_line = 0;
+  int rc = gk_packer_pair_records(pk, r.n_recs, r.names_contiguous, r.key, r.soon, pairs, &first_line);
+  if (rc != GK_OK) return rc;
+  const int64_t n = (int64_t)pairs.size() / 2;
+  split.n_pairs = n;
+  if (!n) return GK_OK;
+  auto all_host = [&] {
+    split.host.resize((size_t)n);
+    for (int64_t p = 0; p < n; ++p) split.host[(size_t)p] = p;
+    return gk_packer_decode_pairs(pk, first_line, pairs, r.full, r.soon);
+  };
+  gk_mate* const mates = gk_packer_reserve_pairs(pk, n);
+  if (!mates) return all_host();      // no room: the host route reports it in its own words
+  split.mates = mates;
+  std::vector<uint8_t, GkRawInit<uint8_t>> verdict((size_t)n);
+  rc = decoder(r, pairs, mates, verdict.data());
+  if (rc != GK_OK) {
+    gk_packer_unreserve(pk);
+    return rc == kGkDecoderDeclines ? all_host() : rc;
+  }
+  for (int64_t p = 0; p < n; ++p)
+    if (verdict[(size_t)p] != 0) split.host.push_back(p);   // GK_DECODE_DONE is 0
+  split.n_plain = n - (int64_t)split.host.size();
+  return gk_packer_decode_subset(pk, first_line, pairs, split.host.data(), (int64_t)split.host.size(), r.full, r.soon);
+}
+
+// the entry points that allocate with the size of the input: running out of memory is an error code, not an abort
+// (an exception must not cross the C boundary)
+void gk_set_error(const char* fmt, ...);
+template <typename Call>
+static inline int gk_guarded(const char* what, const Call& call) {
+  try {
+    return call();
+  } catch (const std::bad_alloc&) {
+    gk_set_error("%s: out of host memory", what);
+    return GK_ERR_CAPACITY;
+  } catch (const std::exception& e) {
+    gk_set_error("%s: %s", what, e.what());
+    return GK_ERR_ARG;
+  }
+}
 
 // start offset of every line of a text (a final line without '\n' counts), plus the end as sentinel
 inline std::vector<int64_t> gk_line_starts(std::string_view text) {

@@ -1,6 +1,6 @@
 // One decoder of a PLAIN mate pair in BAM form, written for the host and for the device alike (`__host__ __device__`):
-// the decode step of a device ingest, which sits between the two halves of gk_packer_feed_records (gk_ingest.h).  No
-// kernel runs it yet; on the host it is held against the decoder it restates.
+// the decode step of the device ingest, which sits between the two halves of gk_packer_feed_records (gk_ingest.h).
+// ingest_decode_pairs (gk_ingest_decode.hip) runs it, one lane per mate; on the host it is held against the decoder it restates.
 //
 // It restates, for records as they lie in a BAM stream, what bam_pack_impl's `full` (gk_bamread.cpp), walk_alignment<BamSource>
 // and decode_records (gk_sampack.cpp) do for a pair that needs nothing but two gk_mate records: the fixed fields, the tag

@@ -68,6 +68,7 @@ struct gk_packer {
   gk_mate* ext = nullptr;            // caller's buffer (gk_packer_set_output) of ext_cap records
   int64_t ext_cap = 0;
   size_t n_mates = 0;                // records made so far (2 per pair)
+  size_t reserved = 0;               // pairs at the end of them that gk_packer_reserve_pairs made room for: the next list's
   std::vector<gk_mate_wide> wide;    // pairs that do not fit gk_mate (2 records per pair) ...
   std::vector<int64_t> spill_pair;   // ... and which pairs they are, ascending
   gk_mate* mates() { return ext ? ext : own.data(); }
@@ -536,31 +537,46 @@ void on_threads(size_t n, const Work& work) {
   for (auto& th : pool) th.join();
 }
 
-// Steps (2) and (3) for n emitted pairs: decode(i, out) fills the records of pair i; lines(i, s) is the
+// Steps (2) and (3) for n emitted pairs: decode(j, i, out) fills the records of pair i, the j-th to be decoded; lines(i, s) is the
 // stream index of its left (s = 0) / right (s = 1) record.  The records are written straight into their
 // final place by the decoding threads.  What depends on the order of the pairs -- ids of inserted
 // strings (first seen, first numbered) and "stop at the first failing pair" -- is settled afterwards
 // in one pass over the few pairs that met an inserted string or failed.
+//
+// With an indirection: the n_sub items that are decoded are the pairs which(0) < which(1) < ... of the n (a device
+// ingest has written the records of the others, which carry no string, no spill and no failure).  The slots and the
+// line numbers are those of all n pairs, and everything keyed on a pair -- Special::pair, Spill::pair, file_spills,
+// the truncation at the first failing pair -- keeps the pair's index, so the ordered parts are what they are when
+// every pair is decoded here.  `which` is a function, never a pointer: "every pair" is the identity over n_sub == n.
 struct Special {
   size_t pair;
   Outcome d;
 };
 
-template <typename DecodeOne, typename LineOf>
-bool decode_all(gk_packer* pk, size_t n, const DecodeOne& decode, const LineOf& line_of) {
+template <typename Which, typename DecodeOne, typename LineOf>
+bool decode_all(gk_packer* pk, size_t n, size_t n_sub, const Which& which, const DecodeOne& decode, const LineOf& line_of) {
   if (!n) return true;
-  const size_t first = pk->n_mates / 2;
+  const size_t first = pk->n_mates / 2 - pk->reserved;   // slots made ahead (gk_packer_reserve_pairs) are these pairs'
+  pk->reserved = 0;
   if (!pk->resize_mates(2 * (first + n)))
     return fail(pk, Fail{3, "more records than the output buffer of gk_packer_set_output holds"}, -1);
   gk_mate* const mates = pk->mates();
   pk->pair_lines.resize(2 * (first + n));
+  if (n_sub != n)                    // the pairs that are not decoded here have line numbers too
+    on_threads(n, [&](int, size_t a, size_t b) {
+      for (size_t i = a; i < b; ++i) {
+        pk->pair_lines[2 * (first + i)] = line_of(i, 0);
+        pk->pair_lines[2 * (first + i) + 1] = line_of(i, 1);
+      }
+    });
   std::vector<std::vector<Special>> special((size_t)pack_threads() + 1);
   struct Spill { size_t pair; gk_mate_wide w[2]; };
   std::vector<std::vector<Spill>> spills((size_t)pack_threads() + 1);   // per thread, ascending pairs
-  on_threads(n, [&](int t, size_t a, size_t b) {
+  on_threads(n_sub, [&](int t, size_t a, size_t b) {
     std::unique_ptr<Decoded> holder(new Decoded());   // two wide records inside: not for the stack
     Decoded& d = *holder;
-    for (size_t i = a; i < b; ++i) {
+    for (size_t j = a; j < b; ++j) {
+      const size_t i = which(j);
       d.ins[0].clear(); d.ins[1].clear();
       d.store_ins[0] = d.store_ins[1] = false;
       d.spilled = false;
@@ -568,7 +584,7 @@ bool decode_all(gk_packer* pk, size_t n, const DecodeOne& decode, const LineOf& 
       d.fail.msg.clear();
       d.fail_line = -1;
       d.rec = mates + 2 * (first + i);
-      decode(i, d);
+      decode(j, i, d);
       pk->pair_lines[2 * (first + i)] = line_of(i, 0);
       pk->pair_lines[2 * (first + i) + 1] = line_of(i, 1);
       if (d.fail.kind) d.spilled = false;
@@ -645,8 +661,8 @@ bool decode_all(gk_packer* pk, size_t n, const DecodeOne& decode, const LineOf& 
 // the pairs queued by the pairing pass of the text reader
 bool run_jobs(gk_packer* pk) {
   const bool ok = decode_all(
-      pk, pk->jobs.size(),
-      [&](size_t i, Decoded& out) {
+      pk, pk->jobs.size(), pk->jobs.size(), [](size_t j) { return j; },
+      [&](size_t, size_t i, Decoded& out) {
         const gk_packer::Job& j = pk->jobs[i];
         decode_pair(pk, j.left, j.left_idx, j.right_owned.empty() ? j.right : sv(j.right_owned), j.right_idx, out);
       },
@@ -845,19 +861,22 @@ int gk_packer_pair_records(gk_packer* pk, int64_t n, bool names_contiguous,
   return GK_OK;
 }
 
-int gk_packer_decode_pairs(gk_packer* pk, int64_t base, const GkPairList& pairs,
-                           const std::function<void(int64_t, GkAlnRecord&)>& full,
-                           const std::function<void(int64_t, bool)>& soon) {
+namespace {
+// n_sub pairs of the list, which(0) < which(1) < ..., decoded into the slots of the whole list
+template <typename Which>
+int decode_listed(gk_packer* pk, int64_t base, const GkPairList& pairs, size_t n_sub, const Which& which,
+                  const std::function<void(int64_t, GkAlnRecord&)>& full, const std::function<void(int64_t, bool)>& soon) {
   GkPhaseClock clock("feed_records");
   constexpr size_t kAhead = 6;
   // (2) decode on threads, (3) ordered pass over the pairs with inserted strings
   const bool merged = decode_all(
-      pk, pairs.size() / 2,
-      [&](size_t i, Decoded& out) {
+      pk, pairs.size() / 2, n_sub, which,
+      [&](size_t j, size_t i, Decoded& out) {
         GkAlnRecord* pr = out.sc.pr;
-        if (soon && 2 * (i + kAhead) + 1 < pairs.size()) {   // the records are far apart in memory: ask for them early
-          soon(pairs[2 * (i + kAhead)], false);
-          soon(pairs[2 * (i + kAhead) + 1], false);
+        if (soon && j + kAhead < n_sub) {   // the records are far apart in memory: ask for them early
+          const size_t next = which(j + kAhead);
+          soon(pairs[2 * next], false);
+          soon(pairs[2 * next + 1], false);
         }
         const int64_t idx[2] = {base + pairs[2 * i], base + pairs[2 * i + 1]};
         full(pairs[2 * i], pr[0]);
@@ -871,6 +890,42 @@ int gk_packer_decode_pairs(gk_packer* pk, int64_t base, const GkPairList& pairs,
     return GK_ERR_ASSERT;
   }
   return GK_OK;
+}
+}  // namespace
+
+int gk_packer_decode_pairs(gk_packer* pk, int64_t base, const GkPairList& pairs,
+                           const std::function<void(int64_t, GkAlnRecord&)>& full,
+                           const std::function<void(int64_t, bool)>& soon) {
+  return decode_listed(pk, base, pairs, pairs.size() / 2, [](size_t j) { return j; }, full, soon);
+}
+
+gk_mate* gk_packer_reserve_pairs(gk_packer* pk, int64_t n_pairs) {
+  if (!pk || n_pairs < 1 || pk->reserved || pk->err_kind) return nullptr;
+  const size_t first = pk->n_mates / 2;
+  if (!pk->resize_mates(2 * (first + (size_t)n_pairs))) return nullptr;
+  pk->reserved = (size_t)n_pairs;
+  return pk->mates() + 2 * first;
+}
+
+void gk_packer_unreserve(gk_packer* pk) {
+  if (!pk || !pk->reserved) return;
+  pk->resize_mates(pk->n_mates - 2 * pk->reserved);
+  pk->reserved = 0;
+}
+
+int gk_packer_decode_subset(gk_packer* pk, int64_t base, const GkPairList& pairs, const int64_t* which, int64_t n_which,
+                            const std::function<void(int64_t, GkAlnRecord&)>& full,
+                            const std::function<void(int64_t, bool)>& soon) {
+  const int64_t n = (int64_t)pairs.size() / 2;
+  bool ok = pk && n_which >= 0 && n_which <= n && (which || !n_which) && (!pk->reserved || (int64_t)pk->reserved == n);
+  for (int64_t j = 0; ok && j < n_which; ++j) ok = which[j] >= (j ? which[j - 1] + 1 : 0) && which[j] < n;
+  if (!ok) {
+    gk_packer_unreserve(pk);
+    gk_set_error("gk_packer_decode_subset: the subset is not a strictly ascending list of pairs of the list");
+    return GK_ERR_ARG;
+  }
+  // n_which == 0 never reads `which`: the index function is all that goes on
+  return decode_listed(pk, base, pairs, (size_t)n_which, [which](size_t j) { return (size_t)which[j]; }, full, soon);
 }
 
 int gk_packer_feed_records(gk_packer* pk, int64_t n, bool names_contiguous,

@@ -468,13 +468,36 @@ def extractVariant(pair_reads: Iterable[tuple[str, str]], index: GkIndex | list[
     return SampleData(tab, index, None, pairs_text=pairs, ins_strings=table.strings)
 
 
-def packAlignments(source, index: GkIndex, keep_text: bool = True) -> dict:
+_decode_warned = False
+
+
+def packAlignments(source, index: GkIndex, keep_text: bool = True, decode: str = "host", dev: Device | None = None) -> dict:
     """Host half of ``extractVariantFromText``: alignment file (or byte chunks) -> packed records.
 
     Native code with the GIL released (``gk_bam_*`` / ``gk_packer_*``), so a cohort run can pack the
-    next sample on a helper thread (``cohort.prefetched``) while the current one is on the GPU."""
-    from .packed import packBam, packText, readChunks
-    if isinstance(source, str) and source.endswith(".bam") and not keep_text:
+    next sample on a helper thread (``cohort.prefetched``) while the current one is on the GPU.
+    ``decode="device"`` (``--ingest-decode device``): the plain pairs of a ``.bam`` whose text nobody needs are decoded
+    by a kernel of ``dev`` (``packed.packBamDevice``; one thread at a time per context) and the result also holds
+    ``"mates"``, the records in HBM.  Any other input takes the host route, with one warning per process."""
+    global _decode_warned
+    from .packed import packBam, packBamDevice, packText, readChunks
+    if decode not in ("host", "device"):
+        raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
+    binary = isinstance(source, str) and source.endswith(".bam") and not keep_text
+    if decode == "device" and not binary and not _decode_warned:
+        _decode_warned = True
+        logger.warning("[Graph] ingest decode: the device route takes .bam input whose SAM text is not kept; "
+                       "this input is decoded on the host")
+    mates = None
+    if binary and decode == "device":
+        if dev is None:
+            raise ValueError("decode='device' needs a device context (dev=)")
+        chunks = None
+        rec, table, pair_lines, counts = packBamDevice(source, index, dev, keep_device=True)
+        mates = counts.pop("mates")
+        logger.info(f"[Graph] Ingest decode on the {counts['decode']['route']} route: {counts['decode']['device_pairs']} pairs "
+                    f"decoded on the device, {counts['decode']['host_pairs']} on the host")
+    elif binary:
         # nobody needs the SAM text: the BAM records go to the packer in binary form
         chunks = None
         rec, table, pair_lines, counts = packBam(source, index)
@@ -484,7 +507,10 @@ def packAlignments(source, index: GkIndex, keep_text: bool = True) -> dict:
             chunks = list(chunks)
         rec, table, pair_lines, counts = packText(chunks, index)
     pairs_text = PairsText(b"".join(chunks), pair_lines) if keep_text else None
-    return {"records": rec, "strings": table.strings, "pairs_text": pairs_text, "counts": counts}
+    pack = {"records": rec, "strings": table.strings, "pairs_text": pairs_text, "counts": counts}
+    if mates is not None:
+        pack["mates"] = mates
+    return pack
 
 
 def extractVariantFromPacked(pack: dict, index: GkIndex, dev: Device | None = None,

@@ -8,7 +8,8 @@ readMapping 124-168, alleleTyping 171-220, getCommonName 223-250).  What differs
   is handed to typing in memory (the ``.variant.json`` is still written unless
   ``--no-variant-json``);
 * additive flags: ``--alignment`` (use existing name-collated SAM/BAM instead of running hisat2),
-  ``--no-variant-json``, ``--novel-discovery`` (novel_discover.py after typing: ``{result}.novel.*``); ``--allele-strategy`` also accepts ``pv`` (= full) and maps ``report`` to
+  ``--no-variant-json``, ``--ingest-decode device`` (the plain pairs of a ``.bam`` sample decoded by a kernel,
+  csrc/gk_ingest_decode.hip), ``--novel-discovery`` (novel_discover.py after typing: ``{result}.novel.*``); ``--allele-strategy`` also accepts ``pv`` (= full) and maps ``report`` to
   the EM strategy (the reference forwards ``report`` to a factory that rejects it, main.py:192);
 * launched with RANK / WORLD_SIZE / LOCAL_RANK set (``torchrun`` or any launcher) the samples are sharded over
   the ranks (one GPU each, largest inputs first); ``--cn-cohort`` then pools the gene depths with one
@@ -67,7 +68,7 @@ def hisatMap(index: str, f1: str, f2: str, output_file: str, threads: int = 1) -
 
 
 def mapSamples(names, reads, index, index_ref, exon_region_only=False, alignments=None, write_json=True,
-               keep_records=False, keep_text=False, cn_bootstrap=None):
+               keep_records=False, keep_text=False, cn_bootstrap=None, ingest_decode="host"):
     """Graph mapping (external) -> tabulation (GPU) -> depth (GPU), one sample at a time (main.py:124-168).
 
     Yields ``(alignment file, "{name}.variant", SampleData, depth file)`` per sample, in order.  When a sample
@@ -78,7 +79,9 @@ def mapSamples(names, reads, index, index_ref, exon_region_only=False, alignment
     ``keep_text``: the SAM lines of the pairs stay with the sample (``--novel-discovery`` writes them grouped).
     ``cn_bootstrap`` (``--cn-bootstrap``): ``{"n_boot", "seed", "select_mode"}`` and optionally ``"samples"``, one flag per
     sample -- right after a flagged sample's depth, while its records are still in HBM, the read bootstrap of its gene
-    depths is written next to the depth file (``{depth_name}.boot.tsv``, ``cn_bootstrap.bootstrapGeneDepths``)."""
+    depths is written next to the depth file (``{depth_name}.boot.tsv``, ``cn_bootstrap.bootstrapGeneDepths``).
+    ``ingest_decode`` (``--ingest-decode``): ``"device"`` decodes the plain pairs of a ``.bam`` sample in a kernel
+    (``hisat2.packAlignments(decode="device")``) and tabulates from the records that kernel left in HBM."""
     gk = GkIndex.load(index_ref)
     gene_len = readLocusLengths(index_ref)
     dev = defaultDevice()
@@ -88,6 +91,17 @@ def mapSamples(names, reads, index, index_ref, exon_region_only=False, alignment
     # to HBM on the copier's stream, the tabulation and the depth run on a high-priority stream of their own -- beside the
     # typing lanes (cohort.SampleTyper), which are typing the samples before this one
     copier, ingest = cohort.stagingContexts(dev)
+    ahead = max(1, int(testHook("ingest_ahead") or 3))       # samples packed ahead of the typing (the hook: tools/ingest_cli_sweep.sh)
+    # --ingest-decode device: prepare() runs on `ahead` helper threads, and a context serves one thread at a time -- each
+    # call checks one of `ahead` worker contexts (beyond the staging ones) out of this queue and returns it afterwards.
+    # Only the FREE of a sample's device records crosses threads: they come from the decoder context's pool and go back
+    # to it from this thread (releaseInputs) while a helper may be packing on that context -- the pool takes frees from
+    # any thread (gk_pool_free); nothing else of a decoder context is touched from here
+    import queue
+    decoders: queue.Queue = queue.Queue()
+    if ingest_decode == "device":
+        for i in range(ahead):
+            decoders.put(dev.worker(cohort.sampleLanes() + 2 + i))
 
     def prepare(k: int):
         """External mapping (when needed) + native packing of sample k: host work, off the GPU's path."""
@@ -101,15 +115,22 @@ def mapSamples(names, reads, index, index_ref, exon_region_only=False, alignment
         pack = None
         if source.endswith((".sam", ".sam.gz")) or testHook("bam_reader") != "samtools":
             # SAM text, or BAM decoded + name-collated natively (packed.bamChunks / packBam), packed natively
-            pack = packAlignments(source, gk, keep_text=write_json)
-            # the records cross PCIe in compact form (~30 bytes per mate instead of 128), like the bench's steps
+            if ingest_decode == "device":
+                decoder = decoders.get()
+                try:
+                    pack = packAlignments(source, gk, keep_text=write_json, decode="device", dev=decoder)
+                finally:
+                    decoders.put(decoder)
+            else:
+                pack = packAlignments(source, gk, keep_text=write_json)
+            # the records cross PCIe in compact form (~30 bytes per mate instead of 128), like the bench's steps (with
+            # the records in HBM already, the compact form is still what the hand-off file holds)
             from .packed import CompactMates
             pack["compact"] = CompactMates(pack["records"], threads=2)
         return name, source, pack
 
     # the next sample is mapped / packed on a helper thread while this one is tabulated and written out
     # (three samples ahead on three threads: the serial stretches of one ingest leave cores to the others)
-    ahead = max(1, int(testHook("ingest_ahead") or 3))       # samples packed ahead of the typing (the hook: tools/ingest_cli_sweep.sh)
     from concurrent.futures import ThreadPoolExecutor
     writer = ThreadPoolExecutor(max_workers=2, thread_name_prefix="gk-write")   # compact hand-off files, off this thread
     writes = []
@@ -134,7 +155,9 @@ def _mapLoop(names, prepare, ahead, gk, gene_len, staging, dindex, index_ref, ex
         if pack is not None:
             # pinned records -> HBM on the copier's stream: the compact words as they are, or the 128-byte records
             compact = pack.pop("compact", None)
-            mates = compact.toDevice(copier, wait=True) if compact is not None else copier.put(pack["records"])
+            mates = pack.pop("mates", None)      # --ingest-decode device: the 128-byte records are in HBM already
+            if mates is None:
+                mates = compact.toDevice(copier, wait=True) if compact is not None else copier.put(pack["records"])
             data = extractVariantFromPacked(pack, gk, dev=dev, dindex=dindex, mates=mates)
             if compact is not None and not write_json and os.environ.get("GK_HANDOFF", "always") != "lazy":
                 # the hand-off as the compact records that are in host memory anyway (70 MB for 2 M reads) instead of the
@@ -421,6 +444,10 @@ def createParser() -> argparse.ArgumentParser:
     p.add_argument("--alignment", action="append",
                    help="Existing name-collated alignments (SAM / SAM.gz / BAM), one per sample: skips hisat2")
     p.add_argument("--no-variant-json", action="store_true", help="Do not write {name}.variant.json")
+    p.add_argument("--ingest-decode", choices=["host", "device"], default="host",
+                   help="Who decodes the alignment records of a .bam sample into packed records: the host (default), or "
+                        "the device for the plain pairs (M and D operations only) with the host taking the rest; the "
+                        "device route needs --no-variant-json (the SAM text is not kept), the results are the same")
     p.add_argument("--novel-discovery", action="store_true",
                    help="After typing, look for novel variants of the called alleles in their reads: writes "
                         "{result}.novel.variant.tsv / .tsv / .fa / .bam / .txt per sample (needs the .no_multi.bam, so "
@@ -629,7 +656,7 @@ def _typeShare(args, lanes, names, reads, my_cn, pick, index, index_ref, cohort_
                          write_json=not args.no_variant_json,
                          keep_records=(pooled_fit or keep_records) and not args.step_skip_typing,
                          keep_text=getattr(args, "novel_discovery", False) and not args.step_skip_typing,
-                         cn_bootstrap=cn_boot)
+                         cn_bootstrap=cn_boot, ingest_decode=getattr(args, "ingest_decode", "host"))
     for i, (_, name, data, depth_file) in enumerate(samples):
         depth_files.append(depth_file)
         if pooled_fit:

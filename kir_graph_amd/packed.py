@@ -339,6 +339,69 @@ def packBam(path: str, index: GkIndex, table: InsTable | None = None, name_sorte
         lib().gk_bam_close(h)
 
 
+def _packBamSplit(path: str, index: GkIndex, table, name_sorted: bool, call):
+    """``packBam`` through one of the split routes: ``call(bam handle, packer)`` -> return code of the entry point.  A
+    packer error (return code -4) is raised by ``_withPacker`` as ``packBam`` raises it; any other failure is raised here."""
+    import ctypes as C
+    from ._lib import check, lib
+    h = C.c_void_p()
+    check(lib().gk_bam_open(path.encode(), int(name_sorted), C.byref(h)))
+    try:
+        n_rec = C.c_int64()
+        check(lib().gk_bam_info(h, C.byref(n_rec), None, None))
+
+        def feed(pk):
+            rc = call(h, pk)
+            if rc not in (0, -4):
+                check(rc)
+
+        return _withPacker(index, table, feed, capacity=n_rec.value)
+    finally:
+        lib().gk_bam_close(h)
+
+
+def packBamPlainHost(path: str, index: GkIndex, table: InsTable | None = None, name_sorted: bool = True):
+    """``packBam`` through the split route of the device ingest with the kernel's decoder run on the host
+    (``gk_bam_pack_plain_host``): the rehearsal of ``packBamDevice`` where there is no GPU, for the tests.  Same
+    4-tuple; ``counts["decode"] = {"route": "plain_host", "plain_pairs", "host_pairs"}``."""
+    import ctypes as C
+    from ._lib import lib
+    n_plain, n_host = C.c_int64(), C.c_int64()
+    rec, table, pair_lines, counts = _packBamSplit(
+        path, index, table, name_sorted,
+        lambda h, pk: lib().gk_bam_pack_plain_host(h, pk, C.byref(n_plain), C.byref(n_host)))
+    counts["decode"] = {"route": "plain_host", "plain_pairs": n_plain.value, "host_pairs": n_host.value}
+    return rec, table, pair_lines, counts
+
+
+def packBamDevice(path: str, index: GkIndex, dev, table: InsTable | None = None, name_sorted: bool = True,
+                  keep_device: bool = False):
+    """``packBam`` with the plain pairs (M and D ops only, nothing beyond ``gk_mate``) decoded by a kernel of ``dev``
+    and the rest by the host decoder (``gk_bam_pack_device``, csrc/gk_ingest_decode.hip): the same 4-tuple, the same
+    exceptions.  ``counts["decode"] = {"route": "device" | "host", "device_pairs", "host_pairs"}`` -- ``"host"`` when
+    the host decoded every pair of a file that has pairs (a file too large for the device's free memory goes that way
+    whole).  ``keep_device``:
+    ``counts["mates"]`` is a ``DeviceBuffer`` of ``MATE_DTYPE`` owned by ``dev`` with the same records, ready when the
+    call returns.  ``dev`` is used by one thread at a time."""
+    import ctypes as C
+    from ._lib import DeviceBuffer, lib
+    n_dev, n_host, ptr = C.c_int64(), C.c_int64(), C.c_uint64()
+    try:
+        rec, table, pair_lines, counts = _packBamSplit(
+            path, index, table, name_sorted,
+            lambda h, pk: lib().gk_bam_pack_device(dev.ctx, h, pk, C.byref(ptr) if keep_device else None,
+                                                   C.byref(n_dev), C.byref(n_host)))
+    except BaseException:
+        if ptr.value:
+            lib().gk_free(dev.ctx, ptr.value)
+        raise
+    counts["decode"] = {"route": "device" if n_dev.value or not n_host.value else "host",
+                        "device_pairs": n_dev.value, "host_pairs": n_host.value}
+    if keep_device:
+        counts["mates"] = DeviceBuffer.adopt(dev, ptr.value, len(rec), MATE_DTYPE)   # the entry point's block
+    return rec, table, pair_lines, counts
+
+
 def bamChunks(path: str, chunk_bytes: int = 1 << 24, name_sorted: bool = True):
     """SAM text of a ``.bam`` file in query-name order, as byte chunks of whole lines.
 
